@@ -7,7 +7,8 @@ One "step" = AD refresh {g, A_e, H} + KKT lhs/rhs assembly + regularized LDLᵀ
 back-substitution, i.e. interior_point.hpp:809-812 + :426-482, on inputs already
 resident in HBM (the seeded interior state of SURVEY.md §8d).
 
-  python bench.py --gpus N --steps K --warmup W [--workload single|batch512]
+  python bench.py --gpus N --steps K --warmup W [--workload single|batch512|gfold]
+                  [--dump-outputs DIR] [--full]
 
 --gpus N > 1 without a torchrun environment re-executes this script under
 `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU, RCCL); under a
@@ -20,12 +21,17 @@ launcher the flag must equal WORLD_SIZE.  Workloads:
   batch512  (BASELINE config 4) 512 independent cart-pole N=500 problems, problem b seeded
             with SEED + b, sharded contiguously over the ranks (sleipnir_amd.dist.shard_range:
             64 per GPU at 8 GPUs; multistart.hpp:45-74 hands whole solves to threads the same
-            way); the per-problem {status, delta, gamma} table is all-gathered at the end.
+            way); under --full the per-problem {status, delta, gamma} table is all-gathered at the end.
 The only collectives are the barrier, the MAX of the elapsed time and that gather.
 
-The timed region is `--repeats` (default 5) blocks of EXACTLY K steps, each bracketed by
-barrier + synchronize on both sides and MAX-reduced over the ranks; the line reports the
-MEDIAN block (all block times are in `block_ms`).
+A plain run sets up, warms up, times ONE block of exactly K steps (bracketed by barrier +
+synchronize on both sides and MAX-reduced over the ranks), writes the last step's outputs if
+--dump-outputs is given and prints the line.  Everything else the benchmark measures or checks
+runs under --full only: the per-kernel and roofline probes, the inertia check, the per-problem
+table, the warm setup, the batch probes, the whole solves and the CPU baseline.  Under --full
+the timed region is `--repeats` (default 5) blocks of exactly K steps, short blocks repeated
+until they cover ~50 ms, and the line reports the MEDIAN block (all block times are in
+`block_ms`).
 """
 from __future__ import annotations
 
@@ -46,6 +52,7 @@ from tests.support import models
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 PROFILE_TAG = "r06"    # profiles/<tag>_traffic.json feeds roofline.traffic
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much
 
 
 def cpu_baseline(N: int, dt: float, budget_s: float = 15.0):
@@ -143,6 +150,24 @@ def make_system(sa, cases, N, problem_ids, device, kind="cart_pole"):
                      np.stack([s_[2] for s_ in st]), np.stack([s_[3] for s_ in st]),
                      np.array([s_[4] for s_ in st]))
     return pp, system, {"model": t_model, "compile_and_upload": t_compile}
+
+
+def dump_outputs(out_dir: Path, system, ids, status):
+    """What the timed path hands its caller after its last step, one row per problem of this rank in
+    problem order, as float64 .npy files: the Newton step p = (p_x, p_y), p_s, p_z, the (delta, gamma)
+    the inertia-correcting loop settled on, and the status of the steps (0 = every factorization
+    succeeded).  A batch whose rows exceed DUMP_LIMIT_BYTES keeps a fixed, seeded sample of its
+    problems; problem_ids.npy says which."""
+    arrays = {"p": system.get("p"), "p_s": system.get("p_s"), "p_z": system.get("p_z"),
+              "regularization": system.regularization(), "status": status.astype(np.float64),
+              "problem_ids": np.asarray(ids, dtype=np.float64)}
+    row_bytes = sum(a[0].nbytes for a in arrays.values())
+    keep = min(len(ids), DUMP_LIMIT_BYTES // row_bytes)
+    rows = np.arange(len(ids)) if keep == len(ids) else np.sort(
+        np.random.default_rng(0).choice(len(ids), keep, replace=False))
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a[rows]))
 
 
 def kernel_groups(system, iters):
@@ -274,8 +299,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5, help="timed K-step blocks (at least; short blocks are repeated until they cover ~50 ms); the median is reported")
-    ap.add_argument("--fixed-repeats", action="store_true", help="exactly --repeats blocks, however short")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed K-step blocks; the median is reported (default 1; --full: 5 at least, short blocks "
+                         "are repeated until they cover ~50 ms)")
+    ap.add_argument("--fixed-repeats", action="store_true", help="--full: exactly --repeats blocks, however short")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: per-kernel and roofline probes, the inertia "
+                         "check, the per-problem table, warm setup, batch probes, whole solves, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (rank 0's problems) to DIR/<name>.npy")
     ap.add_argument("--workload", choices=["single", "batch512", "gfold"], default="single")
     ap.add_argument("--N", type=int, default=None, help="horizon (single: 1000, batch512: 500)")
     ap.add_argument("--batch", type=int, default=None,
@@ -283,12 +315,12 @@ def main():
     ap.add_argument("--per-gpu", action="store_true",
                     help="batch512: --batch problems on EVERY rank (weak scaling) instead of --batch problems "
                          "sharded over the ranks (strong scaling, BASELINE config 4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-batched", "--no-batched-roofline", dest="no_batched", action="store_true",
-                    help="skip the after-the-timed-region batch probes (64 x N=500, 512 x N=1000) that "
+                    help="--full without the after-the-timed-region batch probes (64 x N=500, 512 x N=1000) that "
                          "carry the HBM-roofline evidence; profiling passes use this so that the "
                          "rocprofv3 averages are per-launch numbers of the timed workload")
-    ap.add_argument("--no-whole-solve", action="store_true")
+    ap.add_argument("--no-whole-solve", action="store_true", help="--full without the whole solves")
     ap.add_argument("--spawn-check", action="store_true",
                     help="launch self-test (runs without a GPU, gloo): every rank joins the process group, "
                          "rank 0 prints how many ranks answered and how the batch would be sharded")
@@ -357,10 +389,12 @@ def main():
     system.newton_steps(args.warmup)
     blocks = []
     failed = np.zeros(B, dtype=np.int32)
-    # Every block times EXACTLY K steps; the median of the blocks is reported.  A block of few steps is short
-    # (K = 20 at N=1000: under a millisecond, where one host hiccup is 5 %: VERDICT r04), so short blocks are
-    # repeated until the blocks together cover ~50 ms (the same on every rank: decided from rank-maximum times).
-    repeats = max(1, args.repeats)
+    # Every block times EXACTLY K steps; the median of the blocks is reported.  A plain run times one block, so
+    # that --steps is the number of timed steps.  Under --full a block of few steps is short (K = 20 at N=1000:
+    # under a millisecond, where one host hiccup is 5 %: VERDICT r04), so short blocks are repeated until the
+    # blocks together cover ~50 ms (the same on every rank: decided from rank-maximum times).
+    min_repeats = max(1, args.repeats if args.repeats is not None else (5 if args.full else 1))
+    repeats = min_repeats
     done = 0
     while done < repeats:
         barrier()
@@ -372,10 +406,50 @@ def main():
         failed |= info_step
         barrier()
         done += 1
-        if done == max(1, args.repeats) and not args.fixed_repeats:
+        if done == min_repeats and args.full and not args.fixed_repeats:
             repeats = min(200, max(repeats, int(np.ceil(0.05 / max(1e-6, float(np.median(blocks)))))))
     assert np.all(failed == 0), "factorization failed in the timed region"
     elapsed = float(np.median(blocks))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), system, ids, failed)
+
+    workload = ("%s N=%d, %d problem(s) per GPU (replicas), seeded interior "
+                "IPM state, inputs resident in HBM" % ("cart-pole direct transcription" if args.workload == "single"
+                                                       else "g-fold powered-descent OCP", N, B)) if args.workload != "batch512" else (
+                "batch of %d independent cart-pole N=%d problems (seed + b), sharded contiguously: %d on "
+                "rank 0, inputs resident in HBM" % (total_problems, N, B))
+    out = {
+        "metric": "Newton steps/sec, %s N=%d" % ("g-fold OCP" if args.workload == "gfold" else
+                                                 "cart-pole direct-transcription", N),
+        "value": total_problems * args.steps / elapsed,
+        "unit": "Newton steps/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "timing": {"repeats": len(blocks), "statistic": "median of the K-step blocks",
+                   "block_ms": [1e3 * b for b in blocks]},
+        "config": {"workload": workload, "problems_total": total_problems,
+                   "n": n, "m_e": me, "m_i": mi, "nnz_lhs": info["nnz_lhs"],
+                   "nnz_L": info["nnz_L"], "etree_height": info["etree_height"],
+                   "ldlt_levels": info.get("ldlt_levels"), "ldlt_supernodes": info.get("ldlt_supernodes"),
+                   "ldlt_rounds": info["ldlt_rounds"], "ldlt_tasks": info["ldlt_tasks"],
+                   "tape_tasks": info["tape_tasks"], "tape_nodes": info["tape_nodes"],
+                   "tape_slots": info["tape_slots"],
+                   "multi_gpu": "replicas only" if args.workload != "batch512" else
+                                ("%d problems on every rank, no data-path collective" % B if args.per_gpu else
+                                 "problems sharded, no data-path collective")},
+        "setup_s": setup_s,
+    }
+    if not args.full:
+        system.close()
+        pp.close()
+        if rank == 0:
+            print(json.dumps(out))
+        comm.close()
+        return
+
+    single = args.workload in ("single", "gfold") and B == 1
 
     # per-problem results of the last step, in problem order (the only data-path-adjacent
     # collective: an all-gather of B x 4 doubles per rank)
@@ -440,7 +514,6 @@ def main():
                 # workgroup for the sweep's separable sums — counts once: the grid launched most often)
                 traffic_by_group[grp] = sum(max(tj[k].values(), key=lambda e: e.get("launches_sampled", 0))["hbm_bytes_per_launch"]
                                             for k in names)
-        single = args.workload in ("single", "gfold") and B == 1
         roofline = {
             "bound": "hbm", "kernel": dom,
             "kernel_symbol": ("ldlt_mf_step_kernel<.., false>"
@@ -467,37 +540,9 @@ def main():
                      "<.., true> is dispatched beside the sweep, and its row's span includes waiting for it") if single else
                     f"{B} problems of N={N} per launch on this rank",
         }
-        workload = ("%s N=%d, %d problem(s) per GPU (replicas), seeded interior "
-                    "IPM state, inputs resident in HBM" % ("cart-pole direct transcription" if args.workload == "single"
-                                                           else "g-fold powered-descent OCP", N, B)) if args.workload != "batch512" else (
-                    "batch of %d independent cart-pole N=%d problems (seed + b), sharded contiguously: %d on "
-                    "rank 0, inputs resident in HBM" % (total_problems, N, B))
-        out = {
-            "metric": "Newton steps/sec, %s N=%d" % ("g-fold OCP" if args.workload == "gfold" else
-                                                     "cart-pole direct-transcription", N),
-            "value": total_problems * args.steps / elapsed,
-            "unit": "Newton steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "timing": {"repeats": len(blocks), "statistic": "median of the K-step blocks",
-                       "block_ms": [1e3 * b for b in blocks]},
-            "config": {"workload": workload, "problems_total": total_problems,
-                       "n": n, "m_e": me, "m_i": mi, "nnz_lhs": info["nnz_lhs"],
-                       "nnz_L": info["nnz_L"], "etree_height": info["etree_height"],
-                       "ldlt_levels": info.get("ldlt_levels"), "ldlt_supernodes": info.get("ldlt_supernodes"),
-                       "ldlt_rounds": info["ldlt_rounds"], "ldlt_tasks": info["ldlt_tasks"],
-                       "tape_tasks": info["tape_tasks"], "tape_nodes": info["tape_nodes"],
-                       "tape_slots": info["tape_slots"],
-                       "multi_gpu": "replicas only" if args.workload != "batch512" else
-                                    ("%d problems on every rank, no data-path collective" % B if args.per_gpu else
-                                     "problems sharded, no data-path collective")},
-            "ms_per_ldlt_factor": groups["ldlt_factor"][0],
-            "ms_per_ldlt_solve": groups["ldlt_solve"][0],
-            "setup_s": setup_s,
-            "roofline": roofline,
-        }
+        out["ms_per_ldlt_factor"] = groups["ldlt_factor"][0]
+        out["ms_per_ldlt_solve"] = groups["ldlt_solve"][0]
+        out["roofline"] = roofline
         if args.workload == "batch512":
             out["per_problem"] = {
                 "columns": ["problem", "status", "delta", "gamma"],

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 O=$PWD/gpurun_out
 mkdir -p $O
-FAST="--no-cpu-baseline --no-batched --no-whole-solve"
+FAST="--full --no-cpu-baseline --no-batched --no-whole-solve"
 for v in "all:" "none:SLPX_FUSE_LAUNCHES=0"; do
   name=${v%%:*}; envs=${v#*:}
   rm -rf $O/prof_$name

@@ -3,7 +3,7 @@
 #   bash profiles/b64_probe.sh > gpurun_out/b64_probe.txt
 for env in "A=0" "SLPX_TASK_ENTRIES=256" "SLPX_TASK_ENTRIES=384" "SLPX_TASK_ENTRIES=768" "SLPX_LDLT_IL=0" "SLPX_LDLT_IL=0 SLPX_TASK_ENTRIES=2048" "SLPX_LDLT_IL=0 SLPX_SINGLE_LAUNCH=1"; do
   echo -n "64 x N=500 $env: "
-  env $env timeout 300 python bench.py --workload batch512 --batch 64 --N 500 --steps 50 --warmup 5 2>/dev/null | python -c "
+  env $env timeout 300 python bench.py --full --workload batch512 --batch 64 --N 500 --steps 50 --warmup 5 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

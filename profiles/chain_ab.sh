@@ -4,7 +4,7 @@
 for N in ${CHAIN_AB_N:-1000 5000 300 100}; do
   for v in "SLPX_CHAIN_TAPE=0" "SLPX_CHAIN_TAPE=1" "SLPX_CHAIN_TAPE=0" "SLPX_CHAIN_TAPE=1"; do
     echo -n "N=$N $v: "
-    env $v timeout 300 python bench.py --N $N --steps 2000 --warmup 200 --no-cpu-baseline --no-batched --no-whole-solve 2>/dev/null | python -c "
+    env $v timeout 300 python bench.py --full --N $N --steps 2000 --warmup 200 --no-cpu-baseline --no-batched --no-whole-solve 2>/dev/null | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

@@ -4,9 +4,9 @@
     python profiles/collect.py <round-tag> <stats-dir> <pmc-fetch-dir> <pmc-write-dir>
 
 Inputs (made on the GPU box, see profiles/README.md for the exact commands):
-  stats-dir      rocprofv3 --kernel-trace --stats --output-format csv  -- python bench.py
-  pmc-fetch-dir  rocprofv3 --pmc FETCH_SIZE  --output-format csv       -- python bench.py --steps 20 ...
-  pmc-write-dir  rocprofv3 --pmc WRITE_SIZE  --output-format csv       -- python bench.py --steps 20 ...
+  stats-dir      rocprofv3 --kernel-trace --stats --output-format csv  -- python bench.py --full
+  pmc-fetch-dir  rocprofv3 --pmc FETCH_SIZE  --output-format csv       -- python bench.py --full --steps 20 ...
+  pmc-write-dir  rocprofv3 --pmc WRITE_SIZE  --output-format csv       -- python bench.py --full --steps 20 ...
 (counters in their own passes, never together with a trace: MI355X_MICROARCH.md "rocprofv3 PMC
 slots": FETCH_SIZE takes 3 of the 4 TCC slots, WRITE_SIZE 2.)
 

@@ -11,9 +11,9 @@ O=$R/gpurun_out
 N=$O/profiles_new
 rm -rf $O/prof $O/pmc_fetch $O/pmc_write $N
 mkdir -p $N
-FAST="--no-cpu-baseline --no-batched --no-whole-solve"
-# 0. unprofiled reference run of the exact default command
-timeout 900 python bench.py > $O/bench_unprofiled.log 2> $O/bench_unprofiled.err
+FAST="--full --no-cpu-baseline --no-batched --no-whole-solve"
+# 0. unprofiled reference run of the whole benchmark
+timeout 900 python bench.py --full > $O/bench_unprofiled.log 2> $O/bench_unprofiled.err
 grep '^{' $O/bench_unprofiled.log | tail -1 > $N/${TAG}_bench_unprofiled.json
 # 1. kernel stats of the default workload (single N=1000 problem; the after-the-region batch
 #    probes and the whole solve are left out so that the averages are per-launch numbers of it)

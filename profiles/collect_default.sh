@@ -2,9 +2,9 @@ set -x
 export TMPDIR=/tmp
 R=$PWD; O=$R/gpurun_out; N=$O/profiles_new; TAG=r03
 rm -rf $O/prof $O/pmc_fetch $O/pmc_write; mkdir -p $N
-FAST="--no-cpu-baseline --no-batched --no-whole-solve"
+FAST="--full --no-cpu-baseline --no-batched --no-whole-solve"
 # the default workload's evidence alone (collect_all.sh steps 0-2): unprofiled default command, kernel trace, counters
-timeout 900 python bench.py > $O/bench_unprofiled.log 2> $O/bench_unprofiled.err
+timeout 900 python bench.py --full > $O/bench_unprofiled.log 2> $O/bench_unprofiled.err
 grep '^{' $O/bench_unprofiled.log | tail -1 > $N/${TAG}_bench_unprofiled.json
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python bench.py $FAST > $O/bench_profiled.log 2> $O/bench_profiled.err
 grep '^{' $O/bench_profiled.log | tail -1 > $N/${TAG}_bench.json

@@ -6,6 +6,7 @@ set -u
 R=$(cd "$(dirname "$0")/.." && pwd)
 REP=${1:-3}
 shift || true
+set -- --full "$@"  # (the roofline read below is in --full lines only)
 export PYTHONPATH=$R
 # (the test-support libraries link the libslpx they were built beside: they are rebuilt for the library under test
 # and removed afterwards, so that the next user builds them against the tree's again)

@@ -9,7 +9,7 @@ TAG=${1:-r05}
 export PYTHONPATH=$R TMPDIR=/tmp
 O=$R/gpurun_out
 mkdir -p $O
-FAST="--no-cpu-baseline --no-batched --no-whole-solve --steps 20 --warmup 2 --repeats 1 --fixed-repeats"
+FAST="--full --no-cpu-baseline --no-batched --no-whole-solve --steps 20 --warmup 2 --repeats 1 --fixed-repeats"
 rm -rf $O/pmc_a $O/pmc_b
 timeout 600 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS --output-format csv -d $O/pmc_a -- python $R/bench.py $FAST > $O/pmc_a.log 2>&1
 timeout 600 rocprofv3 --pmc SQ_WAVES SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES --output-format csv -d $O/pmc_b -- python $R/bench.py $FAST > $O/pmc_b.log 2>&1

@@ -65,7 +65,8 @@ class Report(ctypes.Structure):
 
 def build(force: bool = False, verbose: bool = False) -> Path:
     """Compile libslpx.so for gfx950 with hipcc (cross-compiles without a GPU)."""
-    cmd = ["make", "-C", str(_PKG / "csrc"), "-j", str(os.cpu_count() or 4)]
+    # (at most 16 jobs: a shared build host may count far more CPUs than one build may use)
+    cmd = ["make", "-C", str(_PKG / "csrc"), "-j", str(min(16, os.cpu_count() or 4))]
     if force:
         subprocess.run(cmd + ["clean"], check=True, capture_output=not verbose)
     res = subprocess.run(cmd, capture_output=True, text=True)

@@ -20,7 +20,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parents[1]
-FAST = ["--steps", "3", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--no-batched", "--no-whole-solve"]
+# (--full: the per-problem table is not part of a plain run's line)
+FAST = ["--full", "--steps", "3", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--no-batched",
+        "--no-whole-solve"]
 
 
 def _free_port():
