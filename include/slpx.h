@@ -160,6 +160,20 @@ int slpx_problem_solve(slpx_problem* p, const slpx_options* opt, slpx_report* re
  * (spy, ABI version 4, is read only when the caller's struct holds it). */
 int slpx_problem_solve_sized(slpx_problem* p, const slpx_options* opt, uint32_t options_bytes, slpx_report* report);
 void slpx_problem_get_duals(const slpx_problem* p, double* s, double* y, double* z);
+/* Batched whole solves: B instances of this problem from x0[B][n] (decision-variable order), each as
+ * slpx_problem_solve would run from that start (its own scaling, barrier parameter, filter, regularization
+ * memory, restoration, exit), with the options shared; options as slpx_problem_solve_sized, except that
+ * `spy` and `diagnostics` are ignored.  The timeout applies to the whole batch: instances still running
+ * when it expires report TIMEOUT.  The values of the problem's variables are not changed.  Outputs may be
+ * NULL: status[B] (ExitStatus), x[B][n], s[B][m_i], y[B][m_e], z[B][m_i], cost[B] (unscaled f at the end),
+ * iterations[B], restorations[B]; report = batch totals and wall-clock phases (delta, gamma, final_error: the
+ * largest over the instances).  Returns 0, or -100 +
+ * slpx_last_error() (no device, batch <= 0, x0 NULL, callbacks registered).  The batch system is compiled
+ * on first use and kept with the problem, one per batch size.  An addition within ABI version 6: callers
+ * detect it by the symbol's presence (dlsym). */
+int slpx_problem_solve_batch(slpx_problem* p, int32_t batch, const double* x0, const slpx_options* opt,
+                             uint32_t options_bytes, int32_t* status, double* x, double* s, double* y, double* z,
+                             double* cost, int32_t* iterations, int32_t* restorations, slpx_report* report);
 /* feasibility_restoration (solver/util/feasibility_restoration.hpp:347-628) on its own: from the
  * iterate (x[n], s[m_i], y[m_e], z[m_i], mu) — all in/out but mu — build the restoration model,
  * run `steps` iterations of its interior-point loop, leave it the way the reference does when its

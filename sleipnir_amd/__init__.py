@@ -162,6 +162,10 @@ def lib() -> ctypes.CDLL:
     sig("slpx_ipm_trial", ctypes.c_int, vp, f64, ctypes.c_int, vp)
     sig("slpx_ipm_commit", ctypes.c_int, vp, f64, f64, ctypes.c_int)
     sig("slpx_ipm_errors", ctypes.c_int, vp, vp, vp)
+    # an addition within ABI version 6, bound where the library has it
+    if hasattr(L, "slpx_problem_solve_batch"):
+        sig("slpx_problem_solve_batch", ctypes.c_int, vp, i32, vp, ctypes.POINTER(Options), ctypes.c_uint32, vp, vp, vp,
+            vp, vp, vp, vp, vp, ctypes.POINTER(Report))
     _lib = L
     return L
 
@@ -249,6 +253,31 @@ class Problem:
         if status == -100:
             raise SlpxError(lib().slpx_last_error().decode())
         return status, {f[0]: getattr(rep, f[0]) for f in Report._fields_}
+
+    def solve_batch(self, x0, tolerance=1e-8, max_iterations=5000, timeout=0.0, feasible_ipm=False):
+        """B instances from the rows of x0 (B x n), each as solve() from that start
+        (slpx_problem_solve_batch).  Returns a dict of arrays: status, x, s, y, z, cost, iterations,
+        restorations, and the batch's report."""
+        L = lib()
+        if not hasattr(L, "slpx_problem_solve_batch"):
+            raise SlpxError(f"{LIB_PATH} has no slpx_problem_solve_batch")
+        n, me, mi = self.dims
+        x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).reshape(-1, n) if n else
+                                  np.zeros((len(x0), 0)))
+        B = x0.shape[0]
+        out = {"status": np.zeros(B, dtype=np.int32), "x": np.zeros((B, n)), "s": np.zeros((B, mi)),
+               "y": np.zeros((B, me)), "z": np.zeros((B, mi)), "cost": np.zeros(B),
+               "iterations": np.zeros(B, dtype=np.int32), "restorations": np.zeros(B, dtype=np.int32)}
+        opt = Options(tolerance, max_iterations, timeout, int(feasible_ipm), 0, 0)
+        rep = Report()
+        rc = L.slpx_problem_solve_batch(self._h, B, x0.ctypes.data if B else None, ctypes.byref(opt),
+                                        ctypes.sizeof(Options), *(out[k].ctypes.data for k in
+                                        ("status", "x", "s", "y", "z", "cost", "iterations", "restorations")),
+                                        ctypes.byref(rep))
+        if rc != 0:
+            raise SlpxError(L.slpx_last_error().decode())
+        out["report"] = {f[0]: getattr(rep, f[0]) for f in Report._fields_}
+        return out
 
     def restoration_steps(self, x, s, y, z, mu, steps, tolerance=1e-8, max_iterations=5000):
         """feasibility_restoration from the given iterate, `steps` iterations (slpx_problem_restoration_steps)."""

@@ -143,6 +143,47 @@ int slpx_problem_solve_sized(slpx_problem* p, const slpx_options* o, uint32_t op
   return rc == 0 ? status : rc;
 }
 
+int slpx_problem_solve_batch(slpx_problem* p, int32_t batch, const double* x0, const slpx_options* o, uint32_t options_bytes,
+                             int32_t* status, double* x, double* sv, double* y, double* z, double* cost, int32_t* iterations,
+                             int32_t* restorations, slpx_report* report) {
+  (void)options_bytes;  // (every member read here predates `spy`, the only one a shorter struct lacks)
+  return guard([&] {
+    if (p == nullptr) throw std::runtime_error("slpx_problem_solve_batch: null problem");
+    if (batch <= 0) throw std::runtime_error("slpx_problem_solve_batch: batch must be positive");
+    if (x0 == nullptr) throw std::runtime_error("slpx_problem_solve_batch: x0 is null");
+    if (p->problem.has_callbacks())
+      throw std::runtime_error("slpx_problem_solve_batch: the problem has iteration callbacks registered");
+    if (slpx_device_count() < 1) throw std::runtime_error("slpx_problem_solve_batch: no HIP device");
+    slp::Options opt;
+    if (o) {  // (spy and diagnostics are not read)
+      opt.tolerance = o->tolerance;
+      opt.max_iterations = o->max_iterations;
+      if (o->timeout > 0) opt.timeout = o->timeout;
+      opt.feasible_ipm = o->feasible_ipm != 0;
+    }
+    const slpx::BatchSolveResult r = p->problem.solve_batch(batch, x0, opt);
+    const size_t B = static_cast<size_t>(batch);
+    for (size_t b = 0; b < B; ++b) {
+      if (status) status[b] = static_cast<int32_t>(r.status[b]);
+      if (cost) cost[b] = r.cost[b];
+      if (iterations) iterations[b] = r.iterations[b];
+      if (restorations) restorations[b] = r.restorations[b];
+    }
+    if (x) std::copy(r.x.begin(), r.x.end(), x);
+    if (sv) std::copy(r.s.begin(), r.s.end(), sv);
+    if (y) std::copy(r.y.begin(), r.y.end(), y);
+    if (z) std::copy(r.z.begin(), r.z.end(), z);
+    if (report) {
+      const auto& q = r.report;
+      *report = slpx_report{q.iterations,   q.factorizations, q.solves,        q.value_sweeps,
+                            q.delta,        q.gamma,          q.final_error,   q.t_setup,
+                            q.t_kkt_build,  q.t_kkt_decomp,   q.t_kkt_solve,   q.t_line_search,
+                            q.t_ad_refresh, q.t_total,        0.0,             q.restorations,
+                            q.restoration_iterations, q.t_restoration_setup, q.t_restoration};
+    }
+  });
+}
+
 int slpx_problem_restoration_steps(slpx_problem* p, const slpx_options* o, double* x, double* sv, double* y,
                                    double* z, double mu, int32_t steps) {
   int status = -100;

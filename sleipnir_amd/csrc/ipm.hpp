@@ -21,10 +21,12 @@
 #pragma once
 
 
+#include <chrono>
 #include <functional>
 #include <limits>
 #include <vector>
 
+#include "ipm_decide.h"
 #include "newton.hpp"
 
 namespace slpx {
@@ -110,6 +112,18 @@ ExitStatus feasibility_restoration_steps(NewtonSystem& sys, const std::vector<do
                                          std::vector<double>& s, std::vector<double>& y,
                                          std::vector<double>& z, double mu, int steps,
                                          SolveReport* report = nullptr);
+
+// feasibility_restoration as interior_point() enters it (interior_point.hpp:721-771), for a caller that runs the
+// outer iteration itself (the batched driver, ipm_batch.cpp): the iterate (x, s, y, z) and barrier parameter mu of
+// the outer problem, c_e, c_i, g at x, its constraint violation, and `outer_accepts(entry, D_phi)` — the outer
+// filter's verdict on a restoration iterate.  `scales` must be installed on the device; x, s, y, z in/out.
+ExitStatus feasibility_restoration_handoff(NewtonSystem& sys, const std::vector<double>& scales,
+                                           const std::function<bool(const FilterEntry&, double)>& outer_accepts,
+                                           const Options& options, std::vector<double>& x, std::vector<double>& s,
+                                           std::vector<double>& y, std::vector<double>& z, double mu, int& iterations,
+                                           SolveReport& report, std::chrono::steady_clock::time_point solve_start,
+                                           const std::vector<double>& c_e, const std::vector<double>& c_i,
+                                           const std::vector<double>& g, double initial_violation);
 
 // x in/out.  `scales` = [d_f, d_ce.., d_ci..] already installed on the device.
 ExitStatus interior_point(NewtonSystem& sys, const std::vector<double>& scales,

@@ -1,0 +1,258 @@
+// Launch wrappers of the batched interior-point kernels (ipm_batch_kernels.h).
+#include "ipm_batch.hpp"
+
+#include "ipm_batch_kernels.h"
+
+namespace slpx {
+
+namespace {
+int chunks(int work) { return (work + kBatchThreads - 1) / kBatchThreads; }
+size_t at_least_1(size_t k) { return k ? k : 1; }
+}  // namespace
+
+BatchIpmDevice::BatchIpmDevice(NewtonSystem& sys_) : sys(sys_) {
+  const NlpStructure& s = sys.structure();
+  B = sys.batch();
+  n = s.n;
+  m_e = s.m_e;
+  m_i = s.m_i;
+  dim = n + m_e;
+  ns = s.n_scales();
+  nV = s.nV;
+  mu.assign(B, 0.0);
+  tau.assign(B, 0.0);
+  alpha.assign(B, 0.0);
+  alpha_z.assign(B, 0.0);
+  alpha_soc.assign(B, 0.0);
+  mode.assign(B, 0);
+  s_from_ci.assign(B, 0);
+  first.assign(B, 0);
+  active.assign(B, 0);
+  m_scale_idx.upload(s.V_scale_idx);
+  m_is_static.upload(s.V_is_static);
+  m_static_raw.upload(s.V_static_raw);
+  m_scales.alloc(static_cast<size_t>(B) * ns);
+  for (auto* b : {&m_active, &m_s_from_ci, &m_first}) b->alloc(B);
+  m_mode.alloc(B);
+  for (auto* b : {&m_mu, &m_tau, &m_alpha, &m_alpha_z, &m_alpha_soc}) b->alloc(B);
+  m_out.alloc(static_cast<size_t>(B) * kBatchErrN);
+  const size_t Bn = at_least_1(static_cast<size_t>(B) * n), Be = at_least_1(static_cast<size_t>(B) * m_e),
+               Bi = at_least_1(static_cast<size_t>(B) * m_i);
+  for (auto* b : {&m_x, &m_tx, &m_sx}) b->alloc(Bn);
+  for (auto* b : {&m_y, &m_ty, &m_sy, &m_tce, &m_sce}) b->alloc(Be);
+  for (auto* b : {&m_s, &m_z, &m_ts, &m_tz, &m_ss, &m_sz, &m_ps, &m_pz, &m_tci, &m_scims, &m_t}) b->alloc(Bi);
+  m_p.alloc(static_cast<size_t>(B) * dim);
+  m_Vcur.alloc(static_cast<size_t>(B) * nV);
+}
+
+void BatchIpmDevice::upload() {
+  hipStream_t st = sys.device().stream();
+  auto put = [&](auto& buf, const auto& v) {
+    SLPX_HIP_CHECK(hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, st));
+  };
+  put(m_active, active);
+  put(m_mu, mu);
+  put(m_tau, tau);
+  put(m_alpha, alpha);
+  put(m_alpha_z, alpha_z);
+  put(m_alpha_soc, alpha_soc);
+  put(m_mode, mode);
+  put(m_s_from_ci, s_from_ci);
+  put(m_first, first);
+  // (pageable sources: the host may change its vectors once the copies are through)
+  SLPX_HIP_CHECK(hipStreamSynchronize(st));
+}
+
+void BatchIpmDevice::set_scales(const std::vector<double>& scales) {
+  if (scales.size() != m_scales.n) throw std::runtime_error("BatchIpmDevice::set_scales: wrong length");
+  SLPX_HIP_CHECK(hipMemcpy(m_scales.p, scales.data(), scales.size() * sizeof(double), hipMemcpyHostToDevice));
+}
+
+void BatchIpmDevice::set_iterate(const std::vector<double>& x, const std::vector<double>& s, const std::vector<double>& y,
+                                 const std::vector<double>& z) {
+  auto put = [](DevBuf<double>& d, const std::vector<double>& h) {
+    if (!h.empty()) SLPX_HIP_CHECK(hipMemcpy(d.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  };
+  put(m_x, x);
+  put(m_s, s);
+  put(m_y, y);
+  put(m_z, z);
+}
+
+void BatchIpmDevice::get_iterate(std::vector<double>& x, std::vector<double>& s, std::vector<double>& y,
+                                 std::vector<double>& z) {
+  DeviceNlp& dev = sys.device();
+  x.resize(static_cast<size_t>(B) * n);
+  s.resize(static_cast<size_t>(B) * m_i);
+  y.resize(static_cast<size_t>(B) * m_e);
+  z.resize(static_cast<size_t>(B) * m_i);
+  if (!x.empty()) dev.download(m_x.p, x.data(), x.size());
+  if (!s.empty()) dev.download(m_s.p, s.data(), s.size());
+  if (!y.empty()) dev.download(m_y.p, y.data(), y.size());
+  if (!z.empty()) dev.download(m_z.p, z.data(), z.size());
+}
+
+void BatchIpmDevice::get_instance(int b, std::vector<double>& x, std::vector<double>& s, std::vector<double>& y,
+                                  std::vector<double>& z, std::vector<double>& V) {
+  DeviceNlp& dev = sys.device();
+  x.resize(n);
+  s.resize(m_i);
+  y.resize(m_e);
+  z.resize(m_i);
+  V.resize(nV);
+  if (n) dev.download(m_x.p + static_cast<size_t>(b) * n, x.data(), n);
+  if (m_i) dev.download(m_s.p + static_cast<size_t>(b) * m_i, s.data(), m_i);
+  if (m_e) dev.download(m_y.p + static_cast<size_t>(b) * m_e, y.data(), m_e);
+  if (m_i) dev.download(m_z.p + static_cast<size_t>(b) * m_i, z.data(), m_i);
+  dev.download(m_Vcur.p + static_cast<size_t>(b) * nV, V.data(), nV);
+}
+
+void BatchIpmDevice::put_instance(int b, const std::vector<double>& x, const std::vector<double>& s,
+                                  const std::vector<double>& y, const std::vector<double>& z) {
+  auto put = [](double* d, const std::vector<double>& h) {
+    if (!h.empty()) SLPX_HIP_CHECK(hipMemcpy(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  };
+  put(m_x.p + static_cast<size_t>(b) * n, x);
+  put(m_s.p + static_cast<size_t>(b) * m_i, s);
+  put(m_y.p + static_cast<size_t>(b) * m_e, y);
+  put(m_z.p + static_cast<size_t>(b) * m_i, z);
+}
+
+void BatchIpmDevice::scale_V(int count) {
+  DeviceNlp& dev = sys.device();
+  hipLaunchKernelGGL(batch_scale_V_kernel, dim3(chunks(count), B), dim3(kBatchThreads), 0, dev.stream(), dev.d_V(), nV,
+                     count, m_scale_idx.p, m_is_static.p, m_static_raw.p, m_scales.p, ns, m_active.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+}
+
+void BatchIpmDevice::download_out(size_t per_instance, std::vector<double>& out) {
+  out.resize(static_cast<size_t>(B) * per_instance);
+  sys.device().download(m_out.p, out.data(), out.size());
+}
+
+void BatchIpmDevice::errors(const double* V, bool trial, std::vector<double>& err) {
+  DeviceNlp& dev = sys.device();
+  const BatchIter it = trial ? BatchIter{m_tx.p, m_ts.p, m_ty.p, m_tz.p} : BatchIter{m_x.p, m_s.p, m_y.p, m_z.p};
+  hipLaunchKernelGGL(batch_errors_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(), V, nV, nV, it, m_mu.p,
+                     m_scales.p, ns, m_active.p, m_out.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  download_out(kBatchErrN, err);
+}
+
+void BatchIpmDevice::refresh(std::vector<double>& err) {
+  DeviceNlp& dev = sys.device();
+  hipStream_t st = dev.stream();
+  hipLaunchKernelGGL(batch_load_state_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), dev.d_x(),
+                     sys.structure().n_inputs(), BatchIter{m_x.p, m_s.p, m_y.p, m_z.p}, m_scales.p, ns, dev.d_s(), dev.d_y(),
+                     dev.d_z(), 1, m_active.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  dev.sweep_full();
+  scale_V(nV);
+  SLPX_HIP_CHECK(hipMemcpyAsync(m_Vcur.p, dev.d_V(), m_Vcur.n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  errors(m_Vcur.p, false, err);
+}
+
+void BatchIpmDevice::newton_direction(std::vector<double>& dir) {
+  DeviceNlp& dev = sys.device();
+  hipStream_t st = dev.stream();
+  SLPX_HIP_CHECK(hipMemcpyAsync(m_p.p, dev.d_p(), m_p.n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (m_i) {
+    SLPX_HIP_CHECK(hipMemcpyAsync(m_ps.p, dev.d_ps(), static_cast<size_t>(B) * m_i * sizeof(double), hipMemcpyDeviceToDevice, st));
+    SLPX_HIP_CHECK(hipMemcpyAsync(m_pz.p, dev.d_pz(), static_cast<size_t>(B) * m_i * sizeof(double), hipMemcpyDeviceToDevice, st));
+  }
+  hipLaunchKernelGGL(batch_direction_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), m_Vcur.p, nV, m_s.p, m_z.p, m_p.p,
+                     m_ps.p, m_pz.p, m_mu.p, m_tau.p, m_active.p, m_out.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  download_out(3, dir);
+}
+
+void BatchIpmDevice::trial_values(std::vector<double>& met) {
+  DeviceNlp& dev = sys.device();
+  hipStream_t st = dev.stream();
+  BatchTrialArgs A{};
+  A.cur = BatchIter{m_x.p, m_s.p, m_y.p, m_z.p};
+  A.trial = BatchIter{m_tx.p, m_ts.p, m_ty.p, m_tz.p};
+  A.soc = BatchIter{m_sx.p, m_ss.p, m_sy.p, m_sz.p};
+  A.p = m_p.p;
+  A.ps = m_ps.p;
+  A.pz = m_pz.p;
+  A.mode = m_mode.p;
+  A.s_from_ci = m_s_from_ci.p;
+  A.alpha = m_alpha.p;
+  A.alpha_z = m_alpha_z.p;
+  A.in = dev.d_x();
+  A.in_stride = sys.structure().n_inputs();
+  A.S = m_scales.p;
+  A.ns = ns;
+  A.with_duals = 0;
+  hipLaunchKernelGGL(batch_trial_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), A, m_active.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  dev.sweep_values();
+  scale_V(sys.structure().off_g);
+  hipLaunchKernelGGL(batch_trial_metrics_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), dev.d_V(), nV, m_s_from_ci.p,
+                     m_mode.p, m_ts.p, m_tce.p, m_tci.p, m_active.p, m_out.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  download_out(4, met);
+}
+
+void BatchIpmDevice::soc_step(std::vector<double>& sd) {
+  DeviceNlp& dev = sys.device();
+  hipStream_t st = dev.stream();
+  BatchSocArgs A{};
+  A.V = m_Vcur.p;
+  A.v_stride = nV;
+  A.cur = BatchIter{m_x.p, m_s.p, m_y.p, m_z.p};
+  A.ts = m_ts.p;
+  A.tce = m_tce.p;
+  A.tci = m_tci.p;
+  A.alpha_soc = m_alpha_soc.p;
+  A.mu = m_mu.p;
+  A.first = m_first.p;
+  A.sce = m_sce.p;
+  A.scims = m_scims.p;
+  A.t = m_t.p;
+  A.rhs = dev.d_rhs();
+  hipLaunchKernelGGL(batch_soc_rhs_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), A, m_active.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  dev.solve();  // (every instance's factor; the slices of the others are not read)
+  hipLaunchKernelGGL(batch_soc_direction_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), m_Vcur.p, nV, dev.d_p(),
+                     BatchIter{m_x.p, m_s.p, m_y.p, m_z.p}, m_scims.p, m_mu.p, m_tau.p, BatchIter{m_sx.p, m_ss.p, m_sy.p, m_sz.p},
+                     m_active.p, m_out.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  download_out(2, sd);
+}
+
+void BatchIpmDevice::kkt_fallback(std::vector<double>& err_cur, std::vector<double>& err_trial) {
+  DeviceNlp& dev = sys.device();
+  errors(m_Vcur.p, false, err_cur);
+  BatchTrialArgs A{};
+  A.cur = BatchIter{m_x.p, m_s.p, m_y.p, m_z.p};
+  A.trial = BatchIter{m_tx.p, m_ts.p, m_ty.p, m_tz.p};
+  A.soc = BatchIter{m_sx.p, m_ss.p, m_sy.p, m_sz.p};
+  A.p = m_p.p;
+  A.ps = m_ps.p;
+  A.pz = m_pz.p;
+  A.mode = m_mode.p;
+  A.s_from_ci = m_s_from_ci.p;
+  A.alpha = m_alpha.p;
+  A.alpha_z = m_alpha_z.p;
+  A.in = dev.d_x();
+  A.in_stride = sys.structure().n_inputs();
+  A.S = m_scales.p;
+  A.ns = ns;
+  A.with_duals = 1;
+  hipLaunchKernelGGL(batch_trial_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(), A, m_active.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  dev.sweep_full();
+  scale_V(nV);
+  errors(dev.d_V(), true, err_trial);
+}
+
+void BatchIpmDevice::commit() {
+  DeviceNlp& dev = sys.device();
+  hipLaunchKernelGGL(batch_commit_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(),
+                     BatchIter{m_tx.p, m_ts.p, m_ty.p, m_tz.p}, BatchIter{m_x.p, m_s.p, m_y.p, m_z.p}, m_mu.p, m_active.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace slpx

@@ -243,11 +243,15 @@ std::vector<FactorInfo> NewtonSystem::compute(bool solve_speculatively) {
 }
 
 // mode 0: factorization attempts only; 1: each attempt followed by solve + backsub.
-std::vector<FactorInfo> NewtonSystem::compute_impl(int mode) {
+std::vector<FactorInfo> NewtonSystem::compute(bool solve_speculatively, const std::vector<uint8_t>& mask) {
+  if (static_cast<int>(mask.size()) != m_opt.batch) throw std::runtime_error("NewtonSystem::compute: mask length");
+  return compute_impl(solve_speculatively ? 1 : 0, &mask);
+}
+std::vector<FactorInfo> NewtonSystem::compute_impl(int mode, const std::vector<uint8_t>* mask) {
   const bool solve_speculatively = mode >= 1;
   const int B = m_opt.batch;
   m_last_twin_launches = m_last_twin_taken = 0;
-  if (mode == 1 && B == 1 && m_twin_attempts && m_dev->twin_available()) return compute_twin();
+  if (mode == 1 && B == 1 && m_twin_attempts && !mask && m_dev->twin_available()) return compute_twin();
   // With solve_speculatively every factorization attempt is followed at once by the
   // triangular solves and the back-substitution, BEFORE the host has read the inertia
   // counters: the device never idles through the host round trip, and in the usual case
@@ -280,6 +284,7 @@ std::vector<FactorInfo> NewtonSystem::compute_impl(int mode) {
   std::vector<FactorInfo> info(B, FactorInfo::Success);
   std::vector<double> delta(B, 0.0), gamma(B, 0.0);
   std::vector<uint8_t> active(B, 1);
+  if (mask) active = *mask;
   m_last_factorizations = 0;
   const double eps = std::numeric_limits<double>::epsilon();
 
@@ -302,6 +307,7 @@ std::vector<FactorInfo> NewtonSystem::compute_impl(int mode) {
     factor(delta, gamma, active);
     ++m_last_factorizations;
     for (int b = 0; b < B; ++b) {
+      if (!active[b]) continue;
       const bool success = stats[b].n_bad == 0;
       if (success && inertia_ok(stats[b]) && min_abs(stats[b]) >= 1e-4) {
         m_prev_delta[b] = 0.0;
@@ -312,7 +318,7 @@ std::vector<FactorInfo> NewtonSystem::compute_impl(int mode) {
       }
     }
   } else {
-    std::fill(need_loop.begin(), need_loop.end(), 1);
+    need_loop = active;
   }
 
   bool any = false;

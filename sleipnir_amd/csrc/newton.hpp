@@ -87,7 +87,10 @@ class NewtonSystem {
   // Returns per-problem info; fills the regularization that was used.
   // solve_speculatively: also run solve() + backsub() after every attempt (see newton.cpp).
   std::vector<FactorInfo> compute(bool solve_speculatively = false);
-  std::vector<FactorInfo> compute_impl(int mode);
+  // The same for the problems with mask[b] != 0 only (the batched whole solve: instances that finished are
+  // neither factored nor have their regularization memory touched); the others report Success.
+  std::vector<FactorInfo> compute(bool solve_speculatively, const std::vector<uint8_t>& mask);
+  std::vector<FactorInfo> compute_impl(int mode, const std::vector<uint8_t>* mask = nullptr);
   // One factorization of the lhs in device memory with delta = gamma = 0, accepted whenever it
   // has no zero / non-finite pivot and the ideal inertia — no |D| threshold, no regularization
   // memory touched.  For systems that are not KKT systems of the barrier problem: the

@@ -5,8 +5,9 @@
 // One thread per guess like the reference.  The expression graph of libslpx is per thread, so
 // the user's `solve` builds its slp::Problem inside the call (the reference's own test does,
 // multistart_test.cpp:24-43); every solve compiles its own system and runs on its own stream of
-// the device.  For MANY starts of one model the batch interface is the better tool
-// (slpx_system_create(batch = starts): one compiled system, all starts per launch — INTEGRATION.md §5).
+// the device.  For MANY starts of one model a batched solve is the better tool
+// (slp::Problem::solve_batch / slpx_problem_solve_batch: one compiled system, every start's device
+// work in the same launches — INTEGRATION.md §5a).
 #pragma once
 
 #include <algorithm>

@@ -11,6 +11,7 @@
 #pragma once
 
 #include <algorithm>
+#include <chrono>
 #include <cstdint>
 #include <fstream>
 #include <functional>
@@ -22,6 +23,7 @@
 #include <vector>
 
 #include "../ipm.hpp"
+#include "../ipm_batch.hpp"
 #include "../newton.hpp"
 #include "variable.hpp"
 
@@ -247,6 +249,124 @@ class ProblemF64 {
     return status;
   }
 
+  bool has_callbacks() const { return !m_iteration_callbacks.empty() || !m_persistent_iteration_callbacks.empty(); }
+
+  // `batch` instances of this problem from x0 = [batch][n] (decision-variable order), each as solve() would
+  // run from that start (ipm_batch.hpp), all with the same options.  The variables' values are left as they
+  // are.  Problems without inequality constraints run their instances one after another through solve().
+  slpx::BatchSolveResult solve_batch(int batch, const double* x0, const Options& options) {
+    if (batch <= 0) throw std::runtime_error("solve_batch: batch must be positive");
+    if (x0 == nullptr) throw std::runtime_error("solve_batch: x0 is null");
+    if (has_callbacks()) throw std::runtime_error("solve_batch: the problem has callbacks registered");
+    auto& g = detail::G();
+    const size_t B = static_cast<size_t>(batch), n = m_decision_variables.size(), m_e = m_equality_constraints.size(),
+                 m_i = m_inequality_constraints.size();
+    slpx::BatchSolveResult out;
+    out.status.assign(B, ExitStatus::SUCCESS);
+    out.x.assign(x0, x0 + B * n);
+    out.s.assign(B * m_i, 0.0);
+    out.y.assign(B * m_e, 0.0);
+    out.z.assign(B * m_i, 0.0);
+    out.cost.assign(B, m_f ? m_f->value() : 0.0);
+    out.iterations.assign(B, 0);
+    out.restorations.assign(B, 0);
+    // problem.hpp:304-313
+    if (cost_function_type() <= ExpressionType::CONSTANT && equality_constraint_type() <= ExpressionType::CONSTANT &&
+        inequality_constraint_type() <= ExpressionType::CONSTANT)
+      return out;
+    std::vector<double> saved(n);
+    for (size_t i = 0; i < n; ++i) saved[i] = g.val[m_decision_variables[i].expr];
+    auto restore = [&] {
+      for (size_t i = 0; i < n; ++i) g.val[m_decision_variables[i].expr] = saved[i];
+    };
+    compile();
+    if (m_i == 0) {  // newton() / sqp() (problem.hpp:335, 403): the single-problem path, instance by instance
+      // (what solve() leaves in the problem — report, duals, scaling — is put back afterwards; the timeout is the
+      // whole batch's: each solve gets what is left of it)
+      const SolveReport saved_report = m_report;
+      const std::vector<double> saved_scales = m_scales, saved_s = m_s, saved_y = m_y, saved_z = m_z;
+      auto restore_all = [&] {
+        restore();
+        m_report = saved_report;
+        m_scales = saved_scales;
+        m_s = saved_s;
+        m_y = saved_y;
+        m_z = saved_z;
+      };
+      const auto t_start = std::chrono::steady_clock::now();
+      try {
+        for (size_t b = 0; b < B; ++b) {
+          Options opt_b = options;
+          const double used = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+          if (used > options.timeout) {
+            out.status[b] = ExitStatus::TIMEOUT;
+            continue;
+          }
+          opt_b.timeout = options.timeout - used;
+          for (size_t i = 0; i < n; ++i) g.val[m_decision_variables[i].expr] = x0[b * n + i];
+          out.status[b] = solve(opt_b);
+          for (size_t i = 0; i < n; ++i) out.x[b * n + i] = g.val[m_decision_variables[i].expr];
+          std::copy(m_y.begin(), m_y.end(), out.y.begin() + b * m_e);
+          out.cost[b] = m_f ? m_f->value() : 0.0;
+          out.iterations[b] = m_report.iterations;
+          out.restorations[b] = m_report.restorations;
+          out.report.iterations += m_report.iterations;
+          out.report.factorizations += m_report.factorizations;
+          out.report.solves += m_report.solves;
+          out.report.value_sweeps += m_report.value_sweeps;
+          out.report.restorations += m_report.restorations;
+          out.report.restoration_iterations += m_report.restoration_iterations;
+          out.report.final_error = std::max(out.report.final_error, m_report.final_error);
+          out.report.delta = std::max(out.report.delta, m_report.delta);
+          out.report.gamma = std::max(out.report.gamma, m_report.gamma);
+        }
+      } catch (...) {
+        restore_all();
+        throw;
+      }
+      restore_all();
+      out.report.t_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+      return out;
+    }
+    slpx::NewtonSystem& sys = batch_system(batch);
+    // get_bounds conflict test and problem scaling at each instance's x0 (problem.hpp:597-616), from one batched
+    // sweep at unit scales
+    const auto& st = sys.structure();
+    auto& dev = sys.device();
+    std::vector<double> s1(B * std::max<size_t>(1, m_i), 1.0), y0(B * std::max<size_t>(1, m_e), 0.0);
+    std::vector<double> V(B * st.nV);
+    dev.upload_x(x0);
+    dev.upload_duals(s1.data(), y0.data(), s1.data());
+    dev.sweep_full();
+    dev.download_V(V.data());
+    const int ns = st.n_scales();
+    std::vector<double> scales(B * ns);
+    std::vector<uint8_t> run(B, 1);
+    // (the test reads single-variable linear rows only: their coefficients do not depend on x0)
+    const bool conflict = has_conflicting_bounds(std::vector<double>(V.begin(), V.begin() + st.nV));
+    for (size_t b = 0; b < B; ++b) {
+      const std::vector<double> Vb(V.begin() + b * st.nV, V.begin() + (b + 1) * st.nV);
+      const std::vector<double> sc = slpx::compute_problem_scaling(st, Vb);
+      std::copy(sc.begin(), sc.end(), scales.begin() + b * ns);
+      if (conflict) {
+        out.status[b] = ExitStatus::GLOBALLY_INFEASIBLE;
+        run[b] = 0;
+      }
+    }
+    if (!conflict) {
+      const std::vector<double> x0v(x0, x0 + B * n);
+      try {
+        slpx::interior_point_batch(sys, *m_sys, scales, options, x0v, run, out);
+      } catch (...) {
+        reinstall_scaling();
+        throw;
+      }
+      reinstall_scaling();
+    }
+    restore();
+    return out;
+  }
+
   // feasibility_restoration (util/feasibility_restoration.hpp:347-628) from a caller-given
   // iterate, `steps` iterations of it, with the scaling solve() would use (at the variables'
   // current values): the seam the restoration parity tests compare with the oracle at.
@@ -311,7 +431,30 @@ class ProblemF64 {
   const std::vector<double>& inequality_duals() const { return m_z; }
 
  private:
+  // solve_batch's restoration hand-off installs an instance's scaling on the batch-1 system: put the problem's back
+  void reinstall_scaling() {
+    if (!m_sys || !m_sys->has_device()) return;
+    if (static_cast<int>(m_scales.size()) == m_sys->structure().n_scales()) m_sys->device().set_scaling(m_scales);
+    else m_sys->device().set_scaling(std::vector<double>(m_sys->structure().n_scales(), 1.0));
+  }
+
+  // the batch system of solve_batch(): the same model compiled for `batch` instances, tape at unit scales
+  slpx::NewtonSystem& batch_system(int batch) {
+    auto& sys = m_batch_sys[batch];
+    if (!sys) {
+      std::vector<NodeId> xs, ce, ci;
+      for (auto& v : m_decision_variables) xs.push_back(v.expr);
+      for (auto& v : m_equality_constraints) ce.push_back(v.expr);
+      for (auto& v : m_inequality_constraints) ci.push_back(v.expr);
+      slpx::NewtonOptions opt;
+      opt.batch = batch;
+      sys = std::make_unique<slpx::NewtonSystem>(detail::G(), xs, m_f ? m_f->expr : slpx::kNull, ce, ci, opt);
+    }
+    return *sys;
+  }
+
   void invalidate() {
+    m_batch_sys.clear();
     m_sys.reset();
     m_param_snapshot.clear();
   }
@@ -360,6 +503,7 @@ class ProblemF64 {
   std::vector<VariableF64> m_inequality_constraints;
   std::vector<slpx::IterationCallback> m_iteration_callbacks, m_persistent_iteration_callbacks;
   std::unique_ptr<slpx::NewtonSystem> m_sys;
+  std::map<int, std::unique_ptr<slpx::NewtonSystem>> m_batch_sys;  // solve_batch(), keyed by the batch size
   std::vector<std::pair<NodeId, double>> m_param_snapshot;  // (parameter node, value at compile time)
   std::vector<double> m_scales, m_s, m_y, m_z;
   SolveReport m_report;

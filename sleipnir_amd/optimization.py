@@ -10,6 +10,7 @@ no CPU fallback — without a HIP device it raises.
 from __future__ import annotations
 
 import concurrent.futures
+import dataclasses
 import enum
 import math
 
@@ -92,6 +93,22 @@ class IterationInfo:
         return (self._matrix(3, 6, (n, n)) + self._matrix(4, 7, (n, n))).tocsc()
 
 
+@dataclasses.dataclass
+class BatchResult:
+    """What Problem.solve_batch returns: per instance the ExitStatus, the end iterate (x: (B, n),
+    s, z: (B, m_i), y: (B, m_e)), the unscaled cost, the iteration and restoration counts; `report` holds
+    the batch's totals and wall-clock phases."""
+    status: list
+    x: np.ndarray
+    s: np.ndarray
+    y: np.ndarray
+    z: np.ndarray
+    cost: np.ndarray
+    iterations: np.ndarray
+    restorations: np.ndarray
+    report: dict
+
+
 class Problem:
     """problem.hpp:66-720"""
 
@@ -168,6 +185,38 @@ class Problem:
             return ExitStatus.SUCCESS
         status, self.report = self._p.solve(timeout=timeout, **kwargs)
         return ExitStatus(status)
+
+    def solve_batch(self, initial_guesses, **kwargs) -> "BatchResult":
+        """B instances of this problem, one per row of `initial_guesses` (shape (B, n), decision-variable
+        order), each solved as solve() would from that start, in one batched run on the device
+        (slpx_problem_solve_batch).  Keyword arguments: tolerance, max_iterations, timeout, feasible_ipm
+        (the timeout covers the whole batch); diagnostics and spy are accepted and ignored.  The variables'
+        values are left as they are.  Raises SlpxError where the library cannot run a batch (no device,
+        callbacks registered)."""
+        allowed = {"tolerance", "max_iterations", "timeout", "feasible_ipm", "diagnostics", "spy"}
+        for k in kwargs:
+            if k not in allowed:
+                raise KeyError(f"Invalid keyword argument: {k}")
+        kwargs.pop("diagnostics", None)
+        kwargs.pop("spy", None)
+        timeout = kwargs.pop("timeout", 0.0)
+        if timeout is None or math.isinf(timeout):
+            timeout = 0.0
+        guesses = np.asarray(initial_guesses, dtype=np.float64)
+        n = len(self._decision_variables)
+        if guesses.ndim != 2 or guesses.shape[1] != n or guesses.shape[0] < 1:
+            raise ValueError(f"initial_guesses must have shape (B, {n}) with B >= 1")
+        r = self._p.solve_batch(guesses, timeout=timeout, **kwargs)
+        return BatchResult(status=[ExitStatus(int(s)) for s in r["status"]], x=r["x"], s=r["s"], y=r["y"],
+                           z=r["z"], cost=r["cost"], iterations=r["iterations"], restorations=r["restorations"],
+                           report=r["report"])
+
+    def multistart(self, initial_guesses, **kwargs):
+        """multistart.hpp:45-79 as one batched solve: every row of `initial_guesses` a start, then
+        successful solves first, lowest cost among them.  Returns (status, cost, x) of that instance."""
+        r = self.solve_batch(initial_guesses, **kwargs)
+        best = min(range(len(r.status)), key=lambda b: (int(r.status[b] != ExitStatus.SUCCESS), r.cost[b]))
+        return r.status[best], float(r.cost[best]), r.x[best].copy()
 
     def add_callback(self, callback):
         """problem.hpp:690-709: callback(info) -> True to stop (None counts as False)"""
@@ -318,7 +367,8 @@ def multistart(solve, initial_guesses):
     """python/src/sleipnir/optimization/__init__.py:6-31 (multistart.hpp:45-79): every initial
     guess on its own thread — the expression graph of libslpx is per thread, so `solve` builds its
     problem inside the call like the reference's tests do — then successful solves first, lowest
-    cost among them.  `solve(guess)` returns (status, cost, variables)."""
+    cost among them.  `solve(guess)` returns (status, cost, variables).  For many starts of ONE model,
+    Problem.multistart / Problem.solve_batch solve them all in one batched run instead."""
     with concurrent.futures.ThreadPoolExecutor(max_workers=len(initial_guesses)) as executor:
         futures = [executor.submit(solve, guess) for guess in initial_guesses]
         results = [f.result() for f in concurrent.futures.as_completed(futures)]
