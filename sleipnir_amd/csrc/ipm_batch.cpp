@@ -304,8 +304,6 @@ void interior_point_batch(NewtonSystem& sys, NewtonSystem& single, const std::ve
         }
       }
       if (launch_for([](const Instance& I) { return I.running && I.phase == Phase::KktEval; })) {
-        for (int b = 0; b < B; ++b) bd.s_from_ci[b] = 0;  // (the full step's s, :697)
-        bd.upload();
         bd.kkt_fallback(err_cur, err_trial);
         for (int b = 0; b < B; ++b) {
           if (!bd.active[b]) continue;

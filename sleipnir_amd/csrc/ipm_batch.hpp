@@ -69,6 +69,7 @@ struct BatchIpmDevice {
   void commit();
 
  private:
+  friend struct BatchIpmProbe;  // (the test-only probe, tests/support/batchcheck.cpp, reads the buffers below)
   DevBuf<int32_t> m_scale_idx, m_mode;
   DevBuf<uint8_t> m_is_static, m_active, m_s_from_ci, m_first;
   DevBuf<double> m_static_raw, m_scales, m_mu, m_tau, m_alpha, m_alpha_z, m_alpha_soc, m_out;

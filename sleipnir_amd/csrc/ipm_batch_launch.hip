@@ -1,4 +1,6 @@
 // Launch wrappers of the batched interior-point kernels (ipm_batch_kernels.h).
+#include <algorithm>
+
 #include "ipm_batch.hpp"
 
 #include "ipm_batch_kernels.h"
@@ -224,6 +226,9 @@ void BatchIpmDevice::soc_step(std::vector<double>& sd) {
 
 void BatchIpmDevice::kkt_fallback(std::vector<double>& err_cur, std::vector<double>& err_trial) {
   DeviceNlp& dev = sys.device();
+  // the full step's s is s + alpha_max p_s, never the trial c_i (:697)
+  std::fill(s_from_ci.begin(), s_from_ci.end(), uint8_t{0});
+  upload();
   errors(m_Vcur.p, false, err_cur);
   BatchTrialArgs A{};
   A.cur = BatchIter{m_x.p, m_s.p, m_y.p, m_z.p};
