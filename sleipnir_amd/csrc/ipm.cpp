@@ -1,7 +1,6 @@
 #include "ipm.hpp"
 
-#include "ipm_decide.h"
-#include "ipm_host.hpp"
+#include "ipm_line_search.hpp"
 #include "restoration.hpp"
 
 #include <algorithm>
@@ -15,6 +14,8 @@ namespace slpx {
 namespace {
 
 using namespace ipm_host;
+using Want = LineSearch::Want;
+using End = LineSearch::End;
 
 }  // namespace
 
@@ -77,9 +78,8 @@ ExitStatus ipm_core_host(NewtonSystem& sys, const Vec& scales,
   if (m_e > n) return finish(ExitStatus::TOO_FEW_DOFS);  // :274
   if (!all_finite(V.data(), st.nV)) return finish(ExitStatus::NONFINITE_INITIAL_GUESS);  // :283-286
 
-  const double mu_min = scales[0] * options.tolerance / 10.0;  // :294
-  constexpr double tau_min = 0.99;
-  double tau = tau_min;
+  const double mu_min = barrier_floor(scales[0], options.tolerance);
+  double tau = kTauMin;
 
   double f = cur.f();
   Vec c_e(cur.c_e(), cur.c_e() + m_e), c_i(cur.c_i(), cur.c_i() + m_i);
@@ -90,15 +90,8 @@ ExitStatus ipm_core_host(NewtonSystem& sys, const Vec& scales,
     return v;
   };
   Filter filter{violation(c_e, c_i, s)};  // :303
-
-  auto update_barrier = [&] {  // :308-333
-    mu = std::max(mu_min, std::min(0.2 * mu, std::pow(mu, 1.5)));
-    tau = std::max(tau_min, 1.0 - mu);
-    filter.reset();
-  };
-
-  constexpr double alpha_reduction_factor = 0.5, alpha_min = 1e-7;
   int full_step_rejected_counter = 0;
+  LineSearch ls;
   const bool identity = scaling_is_identity(st, scales);
   auto E0_of = [&](const Vec& gg, const Vec& ce, const Vec& ci, const Vec& ss, const Vec& yy,
                    const Vec& zz) {
@@ -171,11 +164,6 @@ ExitStatus ipm_core_host(NewtonSystem& sys, const Vec& scales,
     rep.t_kkt_solve += since(t0);
 
     t0 = clk::now();
-    double alpha_max = ftb(s, p_s, tau);  // :488
-    double alpha = alpha_max;
-    bool call_feasibility_restoration = alpha < alpha_min;
-    double alpha_z = ftb(z, p_z, tau);  // :497
-
     const FilterEntry current_entry = make_entry(f, s, c_e.data(), m_e, c_i.data(), mu);
     double D_phi = 0.0;  // :508-509
     for (int i = 0; i < n; ++i) D_phi += g[i] * p_x[i];
@@ -184,125 +172,92 @@ ExitStatus ipm_core_host(NewtonSystem& sys, const Vec& scales,
       for (int j = 0; j < m_i; ++j) t += (1.0 / s[j]) * p_s[j];
       D_phi -= mu * t;
     }
+    ls.start(filter, full_step_rejected_counter, mu, current_entry, ftb(s, p_s, tau), ftb(z, p_z, tau), D_phi);  // :488, :497
 
-    auto read_trial = [&] {
+    // f, c_e, c_i at trial_x; the trial point's four numbers for the line search
+    auto trial_values = [&] {
+      eval_values(trial_x);
       trial_f = Vtrial[st.off_f];
       std::copy(Vtrial.begin() + st.off_ce, Vtrial.begin() + st.off_ce + m_e, trial_c_e.begin());
       std::copy(Vtrial.begin() + st.off_ci, Vtrial.begin() + st.off_ci + m_i, trial_c_i.begin());
     };
+    auto trial_out = [&] {
+      const bool finite = std::isfinite(trial_f) && all_finite(trial_c_e.data(), m_e) && all_finite(trial_c_i.data(), m_i);
+      double logsum = 0.0;
+      for (int j = 0; j < m_i; ++j) logsum += std::log(trial_s[j]);
+      return IpmTrialOut{trial_f, violation(trial_c_e, trial_c_i, trial_s), logsum, finite ? 1.0 : 0.0};
+    };
+    Vec soc_px(n), soc_ps(m_i), soc_py(m_e), soc_pz(m_i), c_e_soc, cims_soc(m_i);  // the corrected direction, its c_e, c_i - s
 
-    while (true) {  // :512
-      trial_x = axpy(x, alpha, p_x);
-      eval_values(trial_x);
-      read_trial();
-      bool all_pos = true;
-      for (double v : c_i) all_pos = all_pos && v > 0.0;
-      if (options.feasible_ipm && all_pos) trial_s = trial_c_i;
-      else trial_s = axpy(s, alpha, p_s);
-      trial_y = axpy(y, alpha_z, p_y);
-      trial_z = axpy(z, alpha_z, p_z);
-
-      if (!std::isfinite(trial_f) || !all_finite(trial_c_e.data(), m_e) ||
-          !all_finite(trial_c_i.data(), m_i)) {
-        alpha *= alpha_reduction_factor;
-        if (alpha < alpha_min) {
-          call_feasibility_restoration = true;
-          break;
+    while (ls.want != Want::Done) switch (ls.want) {
+      case Want::Eval: {  // :513-528
+        trial_x = axpy(x, ls.t_alpha, p_x);
+        trial_values();
+        bool all_pos = true;
+        for (double v : c_i) all_pos = all_pos && v > 0.0;
+        if (options.feasible_ipm && all_pos) trial_s = trial_c_i;
+        else trial_s = axpy(s, ls.t_alpha, p_s);
+        trial_y = axpy(y, ls.t_alpha_z, p_y);
+        trial_z = axpy(z, ls.t_alpha_z, p_z);
+        ls.on_trial(trial_out());
+        break;
+      }
+      case Want::SocSolve: {  // :601-633: new rhs, SAME factorization
+        if (ls.soc_first) {
+          c_e_soc = c_e;
+          for (int j = 0; j < m_i; ++j) cims_soc[j] = c_i[j] - s[j];
         }
-        continue;
-      }
-
-      FilterEntry trial_entry = make_entry(trial_f, trial_s, trial_c_e.data(), m_e, trial_c_i.data(), mu);
-      if (filter.try_add(current_entry, trial_entry, D_phi, alpha)) break;
-
-      const double prev_violation = violation(c_e, c_i, s);
-      double next_violation = violation(trial_c_e, trial_c_i, trial_s);
-
-      // second-order corrections (:566-668): new rhs, SAME factorization
-      if (alpha == alpha_max && next_violation >= prev_violation) {
-        Vec soc_px = p_x, soc_ps = p_s, soc_py = p_y, soc_pz = p_z;
-        double alpha_soc = alpha, alpha_z_soc = alpha_z;
-        Vec c_e_soc = c_e, cims_soc(m_i);
-        for (int j = 0; j < m_i; ++j) cims_soc[j] = c_i[j] - s[j];
-        double soc_violation = next_violation;
-        bool step_acceptable = false;
-        for (int it = 0; it < 5 && !step_acceptable; ++it) {
-          for (int j = 0; j < m_e; ++j) c_e_soc[j] = alpha_soc * c_e_soc[j] + trial_c_e[j];
-          for (int j = 0; j < m_i; ++j) cims_soc[j] = alpha_soc * cims_soc[j] + trial_c_i[j] - trial_s[j];
-          // rhs (:613-616) is O(nnz(A)) host work on the downloaded Jacobians
-          Vec rhs(dim, 0.0);
-          {
-            Vec t(m_i);
-            for (int j = 0; j < m_i; ++j) {
-              const double sinv = 1.0 / s[j];
-              t[j] = mu * sinv - (sinv * z[j]) * cims_soc[j];
-            }
-            for (int i = 0; i < n; ++i) rhs[i] = -g[i];
-            add_At_v(st.Ae, cur.Ae(), nullptr, y.data(), 1.0, rhs);
-            add_At_v(st.Ai, cur.Ai(), nullptr, t.data(), 1.0, rhs);
-            for (int j = 0; j < m_e; ++j) rhs[n + j] = -c_e_soc[j];
+        for (int j = 0; j < m_e; ++j) c_e_soc[j] = ls.alpha_soc * c_e_soc[j] + trial_c_e[j];
+        for (int j = 0; j < m_i; ++j) cims_soc[j] = ls.alpha_soc * cims_soc[j] + trial_c_i[j] - trial_s[j];
+        // rhs (:613-616) is O(nnz(A)) host work on the downloaded Jacobians
+        Vec rhs(dim, 0.0);
+        {
+          Vec t(m_i);
+          for (int j = 0; j < m_i; ++j) {
+            const double sinv = 1.0 / s[j];
+            t[j] = mu * sinv - (sinv * z[j]) * cims_soc[j];
           }
-          SLPX_HIP_CHECK(hipMemcpyAsync(dev.d_rhs(), rhs.data(), dim * sizeof(double),
-                                        hipMemcpyHostToDevice, dev.stream()));
-          dev.solve();
-          ++rep.solves;
-          dev.download(dev.d_p(), p.data(), dim);
-          std::copy(p.begin(), p.begin() + n, soc_px.begin());
-          for (int j = 0; j < m_e; ++j) soc_py[j] = -p[n + j];
-          {  // p_s, p_z with the corrected c_i - s (:479-480)
-            Vec aipx(m_i, 0.0);
-            for (int c = 0; c < n; ++c)
-              for (int q = st.Ai.colptr[c]; q < st.Ai.colptr[c + 1]; ++q)
-                aipx[st.Ai.rowidx[q]] += cur.Ai()[q] * soc_px[c];
-            for (int j = 0; j < m_i; ++j) {
-              const double sinv = 1.0 / s[j];
-              soc_ps[j] = cims_soc[j] + aipx[j];
-              soc_pz[j] = mu * sinv - z[j] - (sinv * z[j]) * soc_ps[j];
-            }
-          }
-          alpha_soc = ftb(s, soc_ps, tau);
-          alpha_z_soc = ftb(z, soc_pz, tau);
-          trial_x = axpy(x, alpha_soc, soc_px);
-          trial_s = axpy(s, alpha_soc, soc_ps);
-          trial_y = axpy(y, alpha_z_soc, soc_py);
-          trial_z = axpy(z, alpha_z_soc, soc_pz);
-          eval_values(trial_x);
-          read_trial();
-          FilterEntry soc_entry = make_entry(trial_f, trial_s, trial_c_e.data(), m_e, trial_c_i.data(), mu);
-          if (filter.try_add(current_entry, soc_entry, D_phi, alpha)) {
-            p_x = soc_px;
-            p_s = soc_ps;
-            p_y = soc_py;
-            p_z = soc_pz;
-            alpha = alpha_soc;
-            alpha_z = alpha_z_soc;
-            step_acceptable = true;
-            break;
-          }
-          next_violation = violation(trial_c_e, trial_c_i, trial_s);
-          if (next_violation > 0.99 * soc_violation) break;
-          soc_violation = next_violation;
+          for (int i = 0; i < n; ++i) rhs[i] = -g[i];
+          add_At_v(st.Ae, cur.Ae(), nullptr, y.data(), 1.0, rhs);
+          add_At_v(st.Ai, cur.Ai(), nullptr, t.data(), 1.0, rhs);
+          for (int j = 0; j < m_e; ++j) rhs[n + j] = -c_e_soc[j];
         }
-        if (step_acceptable) break;
+        SLPX_HIP_CHECK(hipMemcpyAsync(dev.d_rhs(), rhs.data(), dim * sizeof(double),
+                                      hipMemcpyHostToDevice, dev.stream()));
+        dev.solve();
+        ++rep.solves;
+        dev.download(dev.d_p(), p.data(), dim);
+        std::copy(p.begin(), p.begin() + n, soc_px.begin());
+        for (int j = 0; j < m_e; ++j) soc_py[j] = -p[n + j];
+        {  // p_s, p_z with the corrected c_i - s (:479-480)
+          Vec aipx(m_i, 0.0);
+          for (int c = 0; c < n; ++c)
+            for (int q = st.Ai.colptr[c]; q < st.Ai.colptr[c + 1]; ++q)
+              aipx[st.Ai.rowidx[q]] += cur.Ai()[q] * soc_px[c];
+          for (int j = 0; j < m_i; ++j) {
+            const double sinv = 1.0 / s[j];
+            soc_ps[j] = cims_soc[j] + aipx[j];
+            soc_pz[j] = mu * sinv - z[j] - (sinv * z[j]) * soc_ps[j];
+          }
+        }
+        ls.on_soc_solve(ftb(s, soc_ps, tau), ftb(z, soc_pz, tau));
+        break;
       }
-
-      if (alpha == alpha_max) ++full_step_rejected_counter;
-      // :677-684
-      if (full_step_rejected_counter >= 4 &&
-          filter.max_constraint_violation > current_entry.constraint_violation / 10.0 &&
-          filter.last_rejection_due_to_filter()) {
-        filter.max_constraint_violation *= 0.1;
-        filter.reset();
-        continue;
-      }
-      alpha *= alpha_reduction_factor;
-      if (alpha < alpha_min) {  // :691-716
+      case Want::SocEval:
+        trial_x = axpy(x, ls.t_alpha, soc_px);
+        trial_s = axpy(s, ls.t_alpha, soc_ps);
+        trial_y = axpy(y, ls.t_alpha_z, soc_py);
+        trial_z = axpy(z, ls.t_alpha_z, soc_pz);
+        trial_values();
+        ls.on_trial(trial_out());
+        break;
+      case Want::KktEval: {  // :692-706
         const double current_kkt = kkt_error_impl<ErrType::ONE_NORM>(
             st, g, cur.Ae(), c_e.data(), cur.Ai(), c_i.data(), s, y, z, mu, nullptr);
-        trial_x = axpy(x, alpha_max, p_x);
-        trial_s = axpy(s, alpha_max, p_s);
-        trial_y = axpy(y, alpha_z, p_y);
-        trial_z = axpy(z, alpha_z, p_z);
+        trial_x = axpy(x, ls.t_alpha, p_x);
+        trial_s = axpy(s, ls.t_alpha, p_s);
+        trial_y = axpy(y, ls.t_alpha_z, p_y);
+        trial_z = axpy(z, ls.t_alpha_z, p_z);
         // needs g, A_e, A_i at the trial point: full sweep into a scratch copy
         Vec Vkeep = V;
         refresh_full(trial_x, trial_y, trial_z);
@@ -312,20 +267,19 @@ ExitStatus ipm_core_host(NewtonSystem& sys, const Vec& scales,
         trial_f = tv.f();
         std::copy(tv.c_e(), tv.c_e() + m_e, trial_c_e.begin());
         std::copy(tv.c_i(), tv.c_i() + m_i, trial_c_i.begin());
-        const double next_kkt = kkt_error_impl<ErrType::ONE_NORM>(
-            st, tv.g_dense(), tv.Ae(), trial_c_e.data(), tv.Ai(), trial_c_i.data(), trial_s,
-            trial_y, trial_z, mu, nullptr);
-        if (next_kkt <= 0.999 * current_kkt) break;
-        call_feasibility_restoration = true;
+        ls.on_kkt_errors(current_kkt, kkt_error_impl<ErrType::ONE_NORM>(st, tv.g_dense(), tv.Ae(), trial_c_e.data(), tv.Ai(),
+                                                                        trial_c_i.data(), trial_s, trial_y, trial_z, mu, nullptr));
         break;
       }
+      case Want::Done: break;
     }
+    const double alpha = ls.alpha, alpha_z = ls.alpha_z;
     rep.t_line_search += since(t0);
 
-    if (call_feasibility_restoration) {  // :721-771
+    if (ls.call_feasibility_restoration) {  // :721-771
       if (in_feasibility_restoration) return finish(ExitStatus::FEASIBILITY_RESTORATION_FAILED);
 
-      const FilterEntry initial_entry = make_entry(f, s, c_e.data(), m_e, c_i.data(), mu);
+      const FilterEntry initial_entry = current_entry;
       // Leave restoration once the outer filter accepts the restoration iterate and the violation dropped by 10 %
       // (:729-752); the restoration iteration reduces the outer problem's quantities at its iterate on the device
       auto outer_accepts = [&](const FilterEntry& trial_entry, double D_phi_restoration) {
@@ -334,25 +288,19 @@ ExitStatus ipm_core_host(NewtonSystem& sys, const Vec& scales,
       const ExitStatus fr_status = feasibility_restoration(sys, scales, callbacks, outer_accepts, options, x, s, y, z, mu, iterations,
                                                            rep, solve_start, c_e, c_i, g, initial_entry.constraint_violation);
       if (fr_status != ExitStatus::SUCCESS) return finish(fr_status);
-      eval_values(x);
-      read_trial();
-      f = trial_f;
-      c_e = trial_c_e;
-      c_i = trial_c_i;
+      trial_x = x;
+      trial_values();
     } else {
-      if (alpha == alpha_max) full_step_rejected_counter = 0;
       x = trial_x;
       s = trial_s;
       y = trial_y;
       z = trial_z;
-      for (int j = 0; j < m_i; ++j) {  // :797-801
-        constexpr double kappa = 1e10;
-        z[j] = std::clamp(z[j], 1.0 / kappa * mu / s[j], kappa * mu / s[j]);
-      }
-      f = trial_f;
-      c_e = trial_c_e;
-      c_i = trial_c_i;
+      for (int j = 0; j < m_i; ++j)  // :797-801
+        z[j] = std::clamp(z[j], 1.0 / kKappa * mu / s[j], kKappa * mu / s[j]);
     }
+    f = trial_f;
+    c_e = trial_c_e;
+    c_i = trial_c_i;
 
     // AD refresh (:809-812)
     t0 = clk::now();
@@ -361,24 +309,11 @@ ExitStatus ipm_core_host(NewtonSystem& sys, const Vec& scales,
     rep.t_ad_refresh += since(t0);
 
     E_0 = E0_of(g, c_e, c_i, s, y, z);
-    if (E_0 > options.tolerance) {  // :819-832
-      auto E_mu_of = [&] {
-        return kkt_error_impl<ErrType::INF_NORM_SCALED>(st, g, cur.Ae(), c_e.data(), cur.Ai(),
-                                                        c_i.data(), s, y, z, mu, nullptr);
-      };
-      double E_mu = E_mu_of();
-      while (mu > mu_min && E_mu <= 10.0 * mu) {
-        update_barrier();
-        E_mu = E_mu_of();
-      }
-    }
-    if (options.diagnostics) {  // one line per iteration (print_iteration_diagnostics.hpp, condensed)
-      std::fprintf(stderr,
-                   "%4d  err %.3e  f %.6e  |c| %.3e  mu %.1e  delta %.3e  gamma %.3e  alpha %.2e  "
-                   "alpha_z %.2e  nfact %d\n",
-                   iterations, E_0, f, violation(c_e, c_i, s), mu, rep.delta, rep.gamma, alpha, alpha_z,
-                   sys.last_factorizations());
-    }
+    if (E_0 > options.tolerance)  // :819-832
+      update_barrier_parameter(mu, mu_min, tau, filter, [&](double m) {
+        return kkt_error_impl<ErrType::INF_NORM_SCALED>(st, g, cur.Ae(), c_e.data(), cur.Ai(), c_i.data(), s, y, z, m, nullptr);
+      });
+    if (options.diagnostics) print_iteration(iterations, E_0, f, violation(c_e, c_i, s), mu, rep, alpha, alpha_z, sys.last_factorizations());
     ++iterations;
     rep.final_error = E_0;
     if (iterations >= options.max_iterations) return finish(ExitStatus::MAX_ITERATIONS_EXCEEDED);
@@ -470,36 +405,15 @@ ExitStatus ipm_core_resident(NewtonSystem& sys, const Vec& scales,
   if (m_e > n) return finish(ExitStatus::TOO_FEW_DOFS);                        // :274
   if (cur.finite == 0.0) return finish(ExitStatus::NONFINITE_INITIAL_GUESS);  // :283-286
 
-  const double mu_min = scales[0] * options.tolerance / 10.0;  // :294
-  constexpr double tau_min = 0.99;
-  double tau = tau_min;
+  const double mu_min = barrier_floor(scales[0], options.tolerance);
+  double tau = kTauMin;
   Filter filter{cur.viol};  // :303
-  auto update_barrier = [&] {  // :308-333
-    mu = std::max(mu_min, std::min(0.2 * mu, std::pow(mu, 1.5)));
-    tau = std::max(tau_min, 1.0 - mu);
-    filter.reset();
-  };
-
-  constexpr double alpha_reduction_factor = 0.5, alpha_min = 1e-7;
-  constexpr double s_max = 100.0;
   int full_step_rejected_counter = 0;
+  LineSearch ls;
   const bool identity = scaling_is_identity(st, scales);
   const char* lookahead_env = std::getenv("SLPX_IPM_LOOKAHEAD");
   const bool lookahead = lookahead_env == nullptr || lookahead_env[0] != '0';
-  // util/kkt_error.hpp:92-146 from the reduced scalars
-  auto E_mu_of = [&](const IpmErrOut& e, double m) {
-    const double s_d = std::max(s_max, (e.y1 + e.z1) / double(m_e + m_i)) / s_max;
-    const double s_c = std::max(s_max, e.z1 / double(m_i)) / s_max;
-    const double comp = m_i ? std::max(std::abs(e.sz_max - m), std::abs(e.sz_min - m)) : 0.0;
-    return std::max({e.dual_inf / s_d, comp / s_c, e.ce_inf, e.cis_inf});
-  };
-  auto E0_of = [&](const IpmErrOut& e) {
-    if (identity) return E_mu_of(e, 0.0);
-    const double s_d = std::max(s_max, (e.y1_u + e.z1_u) / double(m_e + m_i)) / s_max;
-    const double s_c = std::max(s_max, e.z1_u / double(m_i)) / s_max;
-    return std::max({e.dual_inf_u / s_d, e.sz_max_u / s_c, e.ce_inf_u, e.cis_inf_u});
-  };
-  double E_0 = E0_of(cur);  // :361-362
+  double E_0 = ipm_E_0(cur, m_e, m_i, identity);  // :361-362
   rep.t_setup = since(t_setup);
 
   // ---- the pipelined common iteration (ipm_decide.h) ----
@@ -548,12 +462,7 @@ ExitStatus ipm_core_resident(NewtonSystem& sys, const Vec& scales,
   };
 
   while (E_0 > options.tolerance) {
-    // :387-408 infeasibility / divergence checks
-    if (m_e > 0 && std::sqrt(cur.aetce_sq) < 1e-6 && std::sqrt(cur.ce_sq) > 1e-2)
-      return finish(ExitStatus::LOCALLY_INFEASIBLE);
-    if (m_i > 0 && std::sqrt(cur.aitcp_sq) < 1e-6 && std::sqrt(cur.cp_sq) > 1e-6)
-      return finish(ExitStatus::LOCALLY_INFEASIBLE);
-    if (cur.x_inf > 1e10 || cur.s_inf > 1e10 || cur.finite == 0.0) return finish(ExitStatus::DIVERGING_ITERATES);
+    if (const ExitStatus exit = infeasible_or_diverging(cur, m_e, m_i); exit != ExitStatus::SUCCESS) return finish(exit);  // :387-408
 
     if (!callbacks.empty()) {
       pull_state();
@@ -648,14 +557,9 @@ ExitStatus ipm_core_resident(NewtonSystem& sys, const Vec& scales,
         host_current = false;
         filter_on_device = true;
         cur = H.err_ahead;
-        E_0 = E0_of(cur);
-        if (options.diagnostics) {
-          std::fprintf(stderr,
-                       "%4d  err %.3e  f %.6e  |c| %.3e  mu %.1e  delta %.3e  gamma %.3e  alpha %.2e  "
-                       "alpha_z %.2e  nfact %d\n",
-                       iterations, E_0, cur.f, cur.viol, mu, rep.delta, rep.gamma, H.dir.alpha_max, H.dir.alpha_z,
-                       sys.last_factorizations());
-        }
+        E_0 = ipm_E_0(cur, m_e, m_i, identity);
+        if (options.diagnostics)
+          print_iteration(iterations, E_0, cur.f, cur.viol, mu, rep, H.dir.alpha_max, H.dir.alpha_z, sys.last_factorizations());
         ++iterations;
         rep.final_error = E_0;
         slot ^= 1;
@@ -685,98 +589,43 @@ ExitStatus ipm_core_resident(NewtonSystem& sys, const Vec& scales,
     rep.gamma = sys.constraint_jacobian_regularization()[0];
 
     t0 = clk::now();
-    const double alpha_max = H.dir.alpha_max;  // :488
-    double alpha = alpha_max;
-    double alpha_z = H.dir.alpha_z;  // :497
-    const double D_phi = H.dir.D_phi;  // :508-509
-    bool call_feasibility_restoration = alpha < alpha_min;
     const FilterEntry current_entry{cur.f - mu * cur.logsum, cur.viol};
-    double alpha_commit = alpha;
-    bool commit_s_from_ci = s_from_ci;
-    bool have_trial = true;  // the speculative chain already evaluated alpha_max
-    bool trial_is_ahead = ahead;  // ... as the complete look-ahead iterate
-    bool took_lookahead = false;
+    ls.start(filter, full_step_rejected_counter, mu, current_entry, H.dir.alpha_max, H.dir.alpha_z, H.dir.D_phi);  // :488-509
+    bool have_trial = true;       // the speculative chain already evaluated alpha_max
+    bool took_lookahead = false;  // ... as the complete look-ahead iterate, and the filter took it
 
-    while (true) {  // :512
-      if (!have_trial) {
-        dev.ipm_trial_point(alpha);
-        dev.sweep_values_trial();
-        dev.ipm_trial_metrics(alpha, s_from_ci);
-        dev.wait_published();
-        ++rep.value_sweeps;
-      }
-      have_trial = false;
-      alpha_commit = alpha;
-      const bool from_ahead = trial_is_ahead;
-      trial_is_ahead = false;
-      IpmTrialOut tr = from_ahead ? IpmTrialOut{H.err_ahead.f, H.err_ahead.viol, H.err_ahead.logsum, H.err_ahead.finite} : H.trial;
-
-      if (tr.finite == 0.0) {
-        alpha *= alpha_reduction_factor;
-        if (alpha < alpha_min) {
-          call_feasibility_restoration = true;
-          break;
-        }
-        continue;
-      }
-
-      const FilterEntry trial_entry{tr.f - mu * tr.logsum, tr.viol};
-      if (filter.try_add(current_entry, trial_entry, D_phi, alpha)) {
-        took_lookahead = from_ahead;
-        break;
-      }
-
-      const double prev_violation = cur.viol;
-      double next_violation = tr.viol;
-
-      // second-order corrections (:566-668): new rhs, SAME factorization, all on the device
-      if (alpha == alpha_max && next_violation >= prev_violation) {
-        dev.ipm_save_direction();
-        double alpha_soc = alpha, alpha_z_soc = alpha_z;
-        double soc_violation = next_violation;
-        bool step_acceptable = false;
-        for (int it = 0; it < 5 && !step_acceptable; ++it) {
-          dev.ipm_soc_accumulate(alpha_soc, it == 0, it == 0 && s_from_ci);
-          dev.ipm_soc_rhs();
-          dev.solve();
-          ++rep.solves;
-          dev.ipm_soc_backsub();
-          dev.ipm_direction(tau);  // step sizes of the corrected direction + its trial point
+    while (ls.want != Want::Done) switch (ls.want) {
+      case Want::Eval: {
+        const bool from_ahead = have_trial && ahead;
+        if (!have_trial) {
+          dev.ipm_trial_point(ls.t_alpha);
           dev.sweep_values_trial();
-          dev.ipm_trial_metrics(-1.0, false);
+          dev.ipm_trial_metrics(ls.t_alpha, s_from_ci);
           dev.wait_published();
           ++rep.value_sweeps;
-          alpha_soc = H.dir.alpha_max;
-          alpha_z_soc = H.dir.alpha_z;
-          tr = H.trial;
-          const FilterEntry soc_entry{tr.f - mu * tr.logsum, tr.viol};
-          if (filter.try_add(current_entry, soc_entry, D_phi, alpha)) {
-            alpha = alpha_soc;
-            alpha_z = alpha_z_soc;
-            alpha_commit = alpha_soc;
-            commit_s_from_ci = false;
-            step_acceptable = true;
-            break;
-          }
-          next_violation = tr.viol;
-          if (next_violation > 0.99 * soc_violation) break;
-          soc_violation = next_violation;
         }
-        if (step_acceptable) break;
-        dev.ipm_restore_direction();
+        have_trial = false;
+        ls.on_trial(from_ahead ? IpmTrialOut{H.err_ahead.f, H.err_ahead.viol, H.err_ahead.logsum, H.err_ahead.finite} : H.trial);
+        took_lookahead = from_ahead && ls.end == End::Newton;
+        break;
       }
-
-      if (alpha == alpha_max) ++full_step_rejected_counter;
-      // :677-684
-      if (full_step_rejected_counter >= 4 &&
-          filter.max_constraint_violation > current_entry.constraint_violation / 10.0 &&
-          filter.last_rejection_due_to_filter()) {
-        filter.max_constraint_violation *= 0.1;
-        filter.reset();
-        continue;
-      }
-      alpha *= alpha_reduction_factor;
-      if (alpha < alpha_min) {  // :691-716 — rare: on the host, with the iterate pulled over
+      case Want::SocSolve:  // :601-633: new rhs, SAME factorization, all on the device
+        if (ls.soc_first) dev.ipm_save_direction();
+        dev.ipm_soc_accumulate(ls.alpha_soc, ls.soc_first, ls.soc_first && s_from_ci);
+        dev.ipm_soc_rhs();
+        dev.solve();
+        ++rep.solves;
+        dev.ipm_soc_backsub();
+        dev.ipm_direction(tau);  // step sizes of the corrected direction + its trial point
+        dev.sweep_values_trial();
+        dev.ipm_trial_metrics(-1.0, false);
+        dev.wait_published();
+        ++rep.value_sweeps;
+        ls.on_soc_solve(H.dir.alpha_max, H.dir.alpha_z);
+        ls.on_trial(H.trial);  // (SocEval: the chain above evaluated the corrected trial point already)
+        if (!ls.on_correction) dev.ipm_restore_direction();  // the corrections failed: back to the Newton direction
+        break;
+      case Want::KktEval: {  // :691-716 — rare: on the host, with the iterate pulled over
         pull_state();
         pull_V();
         VView cv{st, V};
@@ -790,8 +639,8 @@ ExitStatus ipm_core_resident(NewtonSystem& sys, const Vec& scales,
           dev.download(dev.d_ps(), p_s.data(), m_i);
           dev.download(dev.d_pz(), p_z.data(), m_i);
         }
-        const Vec trial_x = axpy(x, alpha_max, p_x), trial_s = axpy(s, alpha_max, p_s),
-                  trial_y = axpy(y, alpha_z, p_y), trial_z = axpy(z, alpha_z, p_z);
+        const Vec trial_x = axpy(x, ls.t_alpha, p_x), trial_s = axpy(s, ls.t_alpha, p_s),
+                  trial_y = axpy(y, ls.t_alpha_z, p_y), trial_z = axpy(z, ls.t_alpha_z, p_z);
         // needs g, A_e, A_i at the trial point: full sweep there, then put the iterate back
         dev.upload_x(trial_x.data());
         dev.upload_duals(s.data(), trial_y.data(), trial_z.data());
@@ -804,18 +653,14 @@ ExitStatus ipm_core_resident(NewtonSystem& sys, const Vec& scales,
         // accepts, read it
         dev.sweep_full();
         VView tv{st, Vt};
-        const double next_kkt = kkt_error_impl<ErrType::ONE_NORM>(st, tv.g_dense(), tv.Ae(), tv.c_e(), tv.Ai(),
-                                                                  tv.c_i(), trial_s, trial_y, trial_z, mu,
-                                                                  nullptr);
-        if (next_kkt <= 0.999 * current_kkt) {
-          alpha_commit = alpha_max;
-          commit_s_from_ci = false;
-          break;
-        }
-        call_feasibility_restoration = true;
+        ls.on_kkt_errors(current_kkt, kkt_error_impl<ErrType::ONE_NORM>(st, tv.g_dense(), tv.Ae(), tv.c_e(), tv.Ai(), tv.c_i(),
+                                                                        trial_s, trial_y, trial_z, mu, nullptr));
         break;
       }
+      default: break;
     }
+    const double alpha = ls.alpha, alpha_z = ls.alpha_z;
+    const bool call_feasibility_restoration = ls.call_feasibility_restoration;
     rep.t_line_search += since(t0);
 
     t0 = clk::now();
@@ -838,11 +683,10 @@ ExitStatus ipm_core_resident(NewtonSystem& sys, const Vec& scales,
       if (fr_status != ExitStatus::SUCCESS) return finish(fr_status);
       push_state();
     } else {
-      if (alpha == alpha_max) full_step_rejected_counter = 0;
       if (took_lookahead) {
         dev.ipm_accept_lookahead();  // :775-801 happened in ipm_lookahead_kernel; the buffers change roles
-      } else {
-        dev.ipm_commit(alpha_commit, alpha_z, commit_s_from_ci);  // :775-801
+      } else {  // :775-801; the feasible-IPM choice of s holds for a trial point along the Newton direction only
+        dev.ipm_commit(ls.end == End::Fallback ? ls.alpha_max : alpha, alpha_z, s_from_ci && ls.end == End::Newton);
       }
       host_current = false;
     }
@@ -858,21 +702,10 @@ ExitStatus ipm_core_resident(NewtonSystem& sys, const Vec& scales,
     }
     rep.t_ad_refresh += since(t0);
 
-    E_0 = E0_of(cur);
-    if (E_0 > options.tolerance) {  // :819-832
-      double E_mu = E_mu_of(cur, mu);
-      while (mu > mu_min && E_mu <= 10.0 * mu) {
-        update_barrier();
-        E_mu = E_mu_of(cur, mu);
-      }
-    }
-    if (options.diagnostics) {
-      std::fprintf(stderr,
-                   "%4d  err %.3e  f %.6e  |c| %.3e  mu %.1e  delta %.3e  gamma %.3e  alpha %.2e  "
-                   "alpha_z %.2e  nfact %d\n",
-                   iterations, E_0, cur.f, cur.viol, mu, rep.delta, rep.gamma, alpha, alpha_z,
-                   sys.last_factorizations());
-    }
+    E_0 = ipm_E_0(cur, m_e, m_i, identity);
+    if (E_0 > options.tolerance)  // :819-832
+      update_barrier_parameter(mu, mu_min, tau, filter, [&](double m) { return ipm_E_mu(cur, m, m_e, m_i); });
+    if (options.diagnostics) print_iteration(iterations, E_0, cur.f, cur.viol, mu, rep, alpha, alpha_z, sys.last_factorizations());
     ++iterations;
     rep.final_error = E_0;
     if (iterations >= options.max_iterations) return finish(ExitStatus::MAX_ITERATIONS_EXCEEDED);
@@ -971,9 +804,8 @@ bool lagrange_multiplier_estimate(NewtonSystem& sys, const Vec& V, const Vec& s,
     for (int q = st.Ai.colptr[c]; q < st.Ai.colptr[c + 1]; ++q) aid[st.Ai.rowidx[q]] += cur.Ai()[q] * p[c];
   z.assign(m_i, 0.0);
   for (int j = 0; j < m_i; ++j) {
-    constexpr double kappa = 1e10;
     const double zj = mu / s[j] - aid[j] / (s[j] * s[j]);
-    z[j] = std::clamp(zj, 1.0 / kappa * mu / s[j], kappa * mu / s[j]);  // :125-130
+    z[j] = std::clamp(zj, 1.0 / kKappa * mu / s[j], kKappa * mu / s[j]);  // :125-130
   }
   return true;
 }
@@ -1136,31 +968,13 @@ ExitStatus restoration_core(NewtonSystem& sys, FrDevice& fr, const std::vector<I
   FrErrOut cur = H.err;
   if (cur.e.finite == 0.0) return finish(ExitStatus::NONFINITE_INITIAL_GUESS);  // :283-286
 
-  const double mu_min = options.tolerance / 10.0;  // :294 (the restoration cost is not scaled)
-  constexpr double tau_min = 0.99;
-  double tau = tau_min;
+  const double mu_min = barrier_floor(1.0, options.tolerance);  // (the restoration cost is not scaled)
+  double tau = kTauMin;
   Filter filter{cur.e.viol};  // :303
-  auto update_barrier = [&] {  // :308-333
-    mu = std::max(mu_min, std::min(0.2 * mu, std::pow(mu, 1.5)));
-    tau = std::max(tau_min, 1.0 - mu);
-    filter.reset();
-  };
-  constexpr double alpha_reduction_factor = 0.5, alpha_min = 1e-7;
-  constexpr double s_max = 100.0;
   int full_step_rejected_counter = 0;
-  // util/kkt_error.hpp:92-146 from the reduced scalars (the scaling {1, d_ce, [d_ci, 1...]} is never the identity here)
-  auto E_mu_of = [&](const IpmErrOut& e, double m) {
-    const double s_d = std::max(s_max, (e.y1 + e.z1) / double(m_e + mi_ext)) / s_max;
-    const double s_c = std::max(s_max, e.z1 / double(mi_ext)) / s_max;
-    const double comp = std::max(std::abs(e.sz_max - m), std::abs(e.sz_min - m));
-    return std::max({e.dual_inf / s_d, comp / s_c, e.ce_inf, e.cis_inf});
-  };
-  auto E0_of = [&](const IpmErrOut& e) {
-    const double s_d = std::max(s_max, (e.y1_u + e.z1_u) / double(m_e + mi_ext)) / s_max;
-    const double s_c = std::max(s_max, e.z1_u / double(mi_ext)) / s_max;
-    return std::max({e.dual_inf_u / s_d, e.sz_max_u / s_c, e.ce_inf_u, e.cis_inf_u});
-  };
-  double E_0 = E0_of(cur.e);  // :361-362
+  LineSearch ls;
+  // (the error measures: m_i + M inequality rows; the scaling {1, d_ce, [d_ci, 1...]} is never the identity here)
+  double E_0 = ipm_E_0(cur.e, m_e, mi_ext, /*identity_scaling=*/false);  // :361-362
   rep.t_setup += since(t_setup);
 
   RestorationView view;
@@ -1168,10 +982,7 @@ ExitStatus restoration_core(NewtonSystem& sys, FrDevice& fr, const std::vector<I
   bool previous_took_first_attempt = true;  // ... of the regularization policy
 
   while (E_0 > options.tolerance) {
-    // :387-408
-    if (m_e > 0 && std::sqrt(cur.e.aetce_sq) < 1e-6 && std::sqrt(cur.e.ce_sq) > 1e-2) return finish(ExitStatus::LOCALLY_INFEASIBLE);
-    if (std::sqrt(cur.e.aitcp_sq) < 1e-6 && std::sqrt(cur.e.cp_sq) > 1e-6) return finish(ExitStatus::LOCALLY_INFEASIBLE);
-    if (cur.e.x_inf > 1e10 || cur.e.s_inf > 1e10 || cur.e.finite == 0.0) return finish(ExitStatus::DIVERGING_ITERATES);
+    if (const ExitStatus exit = infeasible_or_diverging(cur.e, m_e, mi_ext); exit != ExitStatus::SUCCESS) return finish(exit);  // :387-408
 
     if (!user_callbacks.empty()) {
       pull_state();
@@ -1228,95 +1039,50 @@ ExitStatus restoration_core(NewtonSystem& sys, FrDevice& fr, const std::vector<I
     rep.gamma = sys.constraint_jacobian_regularization()[0];
 
     t0 = clk::now();
-    const double alpha_max = H.dir.alpha_max;  // :488
-    double alpha = alpha_max;
-    double alpha_z = H.dir.alpha_z;  // :497
-    const double D_phi = H.dir.D_phi;  // :508-509
-    bool failed = alpha < alpha_min;
     const FilterEntry current_entry{cur.e.f - mu * cur.e.logsum, cur.e.viol};
+    ls.start(filter, full_step_rejected_counter, mu, current_entry, H.dir.alpha_max, H.dir.alpha_z, H.dir.D_phi);  // :488-509
     static const bool fr_debug = std::getenv("SLPX_FR_DEBUG") != nullptr;
     if (fr_debug) {
       std::fprintf(stderr, "fr: it %d mu %.3e delta %.1e gamma %.1e nfact %d | alpha_max %.3e alpha_z %.3e D_phi %.3e emin %.3e | cur f %.6e viol %.6e logsum %.6e | trial f %.6e viol %.6e logsum %.6e fin %g\n",
-                   iterations, mu, delta, rep.gamma, sys.last_factorizations(), alpha_max, alpha_z, D_phi, H.dir.eliminated_min_pivot, cur.e.f, cur.e.viol,
+                   iterations, mu, delta, rep.gamma, sys.last_factorizations(), ls.alpha_max, ls.alpha_z, H.dir.D_phi, H.dir.eliminated_min_pivot, cur.e.f, cur.e.viol,
                    cur.e.logsum, H.err_ahead.e.f, H.err_ahead.e.viol, H.err_ahead.e.logsum, H.err_ahead.e.finite);
     }
-    double alpha_commit = alpha;
-    bool have_trial = true;
-    bool trial_is_ahead = true, took_lookahead = false;
+    bool have_trial = true;       // the chain behind the step evaluated alpha_max, as the complete look-ahead iterate
+    bool took_lookahead = false;  // ... and the filter took it
 
-    while (!failed) {  // :512
-      if (!have_trial) {
-        fr.trial_point(alpha);
-        dev.sweep_values_trial();
-        fr.trial_metrics(alpha, mu);
-        fr.wait_published();
-        ++rep.value_sweeps;
-      }
-      have_trial = false;
-      alpha_commit = alpha;
-      const bool from_ahead = trial_is_ahead;
-      trial_is_ahead = false;
-      IpmTrialOut tr = from_ahead ? IpmTrialOut{H.err_ahead.e.f, H.err_ahead.e.viol, H.err_ahead.e.logsum, H.err_ahead.e.finite} : H.trial;
-
-      if (tr.finite == 0.0) {
-        alpha *= alpha_reduction_factor;
-        if (alpha < alpha_min) failed = true;
-        continue;
-      }
-      const FilterEntry trial_entry{tr.f - mu * tr.logsum, tr.viol};
-      if (filter.try_add(current_entry, trial_entry, D_phi, alpha)) {
-        took_lookahead = from_ahead;
-        break;
-      }
-
-      const double prev_violation = cur.e.viol;
-      double next_violation = tr.viol;
-      // second-order corrections (:566-668): new right-hand side, SAME factorization
-      if (alpha == alpha_max && next_violation >= prev_violation) {
-        fr.save_direction();
-        double alpha_soc = alpha, alpha_z_soc = alpha_z;
-        double soc_violation = next_violation;
-        bool step_acceptable = false;
-        for (int it = 0; it < 5 && !step_acceptable; ++it) {
-          fr.soc_accumulate(alpha_soc, it == 0);
-          fr.build(delta, mu, /*soc=*/true, /*rhs_only=*/true);
-          dev.solve();
-          ++rep.solves;
-          fr.expand(delta, mu, tau, /*soc=*/true);
+    // (a step below the floor fails this phase at once: there is no restoration to call from here)
+    while (!ls.call_feasibility_restoration && ls.want != Want::Done) switch (ls.want) {
+      case Want::Eval: {
+        const bool from_ahead = have_trial;
+        if (!have_trial) {
+          fr.trial_point(ls.t_alpha);
           dev.sweep_values_trial();
-          fr.trial_metrics(-1.0, mu);
+          fr.trial_metrics(ls.t_alpha, mu);
           fr.wait_published();
           ++rep.value_sweeps;
-          alpha_soc = H.dir.alpha_max;
-          alpha_z_soc = H.dir.alpha_z;
-          tr = H.trial;
-          const FilterEntry soc_entry{tr.f - mu * tr.logsum, tr.viol};
-          if (filter.try_add(current_entry, soc_entry, D_phi, alpha)) {
-            alpha = alpha_soc;
-            alpha_z = alpha_z_soc;
-            alpha_commit = alpha_soc;
-            step_acceptable = true;
-            break;
-          }
-          next_violation = tr.viol;
-          if (next_violation > 0.99 * soc_violation) break;
-          soc_violation = next_violation;
         }
-        if (step_acceptable) break;
-        fr.restore_direction();
-      }
-
-      if (alpha == alpha_max) ++full_step_rejected_counter;
-      // :677-684
-      if (full_step_rejected_counter >= 4 && filter.max_constraint_violation > current_entry.constraint_violation / 10.0 &&
-          filter.last_rejection_due_to_filter()) {
-        filter.max_constraint_violation *= 0.1;
-        filter.reset();
         have_trial = false;
-        continue;
+        ls.on_trial(from_ahead ? IpmTrialOut{H.err_ahead.e.f, H.err_ahead.e.viol, H.err_ahead.e.logsum, H.err_ahead.e.finite} : H.trial);
+        took_lookahead = from_ahead && ls.end == End::Newton;
+        break;
       }
-      alpha *= alpha_reduction_factor;
-      if (alpha < alpha_min) {  // :691-716 — rare: on the host, with the iterate pulled over
+      case Want::SocSolve:  // :601-633: new right-hand side, SAME factorization
+        if (ls.soc_first) fr.save_direction();
+        fr.soc_accumulate(ls.alpha_soc, ls.soc_first);
+        fr.build(delta, mu, /*soc=*/true, /*rhs_only=*/true);
+        dev.solve();
+        ++rep.solves;
+        fr.expand(delta, mu, tau, /*soc=*/true);
+        dev.sweep_values_trial();
+        fr.trial_metrics(-1.0, mu);
+        fr.wait_published();
+        ++rep.value_sweeps;
+        ls.on_soc_solve(H.dir.alpha_max, H.dir.alpha_z);
+        ls.on_trial(H.trial);  // (SocEval: the chain above evaluated the corrected trial point already)
+        if (!ls.on_correction) fr.restore_direction();  // the corrections failed: back to the Newton direction
+        break;
+      case Want::KktEval: {  // :691-716 — rare: on the host, with the iterate pulled over
+        const double alpha_max = ls.t_alpha, alpha_z = ls.t_alpha_z;
         host_current = false;
         pull_state();
         Vo.resize(st.nV);
@@ -1350,25 +1116,22 @@ ExitStatus restoration_core(NewtonSystem& sys, FrDevice& fr, const std::vector<I
         dev.upload_x(X.data());
         dev.upload_duals(S.data(), y.data(), Z.data());
         dev.sweep_full();
-        const double next_kkt = restoration_kkt_error_one_norm(st, Vt, Xt, St, yt, Zt, x_r, w, rho, mu);
-        if (next_kkt <= 0.999 * current_kkt) {
-          alpha_commit = alpha_max;
-          break;
-        }
-        failed = true;
+        ls.on_kkt_errors(current_kkt, restoration_kkt_error_one_norm(st, Vt, Xt, St, yt, Zt, x_r, w, rho, mu));
+        break;
       }
+      default: break;
     }
+    const double alpha = ls.alpha, alpha_z = ls.alpha_z;
     rep.t_line_search += since(t0);
-    if (failed) return finish(ExitStatus::FEASIBILITY_RESTORATION_FAILED);  // :721-723
+    if (ls.call_feasibility_restoration) return finish(ExitStatus::FEASIBILITY_RESTORATION_FAILED);  // :721-723
 
     t0 = clk::now();
-    if (alpha == alpha_max) full_step_rejected_counter = 0;
     host_current = false;
     if (took_lookahead) {
       fr.accept_lookahead();  // :775-801 happened in the look-ahead launch; the buffers change roles
       cur = H.err_ahead;      // :809-812 and the norms: already there
     } else {
-      fr.commit(alpha_commit, alpha_z, mu);  // :775-801
+      fr.commit(ls.end == End::Fallback ? ls.alpha_max : alpha, alpha_z, mu);  // :775-801
       // AD refresh (:809-812) and every norm the next decisions need
       dev.sweep_full();
       fr.errors(false, mu);
@@ -1377,19 +1140,11 @@ ExitStatus restoration_core(NewtonSystem& sys, FrDevice& fr, const std::vector<I
     }
     rep.t_ad_refresh += since(t0);
 
-    E_0 = E0_of(cur.e);
-    if (E_0 > options.tolerance) {  // :819-832
-      double E_mu = E_mu_of(cur.e, mu);
-      while (mu > mu_min && E_mu <= 10.0 * mu) {
-        update_barrier();
-        E_mu = E_mu_of(cur.e, mu);
-      }
-    }
-    if (options.diagnostics) {
-      std::fprintf(stderr,
-                   "%4d  err %.3e  f %.6e  |c| %.3e  mu %.1e  delta %.3e  gamma %.3e  alpha %.2e  alpha_z %.2e  nfact %d  (restoration)\n",
-                   iterations, E_0, cur.e.f, cur.e.viol, mu, rep.delta, rep.gamma, alpha, alpha_z, sys.last_factorizations());
-    }
+    E_0 = ipm_E_0(cur.e, m_e, mi_ext, /*identity_scaling=*/false);
+    if (E_0 > options.tolerance)  // :819-832
+      update_barrier_parameter(mu, mu_min, tau, filter, [&](double m) { return ipm_E_mu(cur.e, m, m_e, mi_ext); });
+    if (options.diagnostics)
+      print_iteration(iterations, E_0, cur.e.f, cur.e.viol, mu, rep, alpha, alpha_z, sys.last_factorizations(), "  (restoration)");
     ++iterations;
     if (iterations >= options.max_iterations) return finish(ExitStatus::MAX_ITERATIONS_EXCEEDED);
     if (since(solve_start) > options.timeout) return finish(ExitStatus::TIMEOUT);
@@ -1536,8 +1291,8 @@ ExitStatus sqp_core(NewtonSystem& sys, const Vec& scales, const std::vector<Iter
   double f = cur.f();
   Vec c_e(cur.c_e(), cur.c_e() + m_e);
   Filter filter{norm_1(c_e.data(), m_e)};  // :220
-  constexpr double alpha_reduction_factor = 0.5, alpha_min = 1e-7;
   int full_step_rejected_counter = 0;
+  LineSearch ls;
   const bool identity = scaling_is_identity(st, scales);
   auto E0_of = [&](const Vec& gg, const Vec& ce, const Vec& yy) {
     return kkt_error_impl<ErrType::INF_NORM_SCALED>(st, gg, cur.Ae(), ce.data(), nullptr, nullptr, none, yy, none,
@@ -1548,9 +1303,13 @@ ExitStatus sqp_core(NewtonSystem& sys, const Vec& scales, const std::vector<Iter
 
   Vec p(dim), p_x(n), p_y(m_e), trial_x, trial_y, trial_c_e(m_e);
   double trial_f = 0.0;
-  auto read_trial = [&] {
+  // f, c_e at trial_x: the trial point's numbers for the line search (no slacks: no barrier term)
+  auto trial_out = [&] {
+    eval_values(trial_x);
     trial_f = Vtrial[st.off_f];
     std::copy(Vtrial.begin() + st.off_ce, Vtrial.begin() + st.off_ce + m_e, trial_c_e.begin());
+    const bool finite = std::isfinite(trial_f) && all_finite(trial_c_e.data(), m_e);
+    return IpmTrialOut{trial_f, norm_1(trial_c_e.data(), m_e), 0.0, finite ? 1.0 : 0.0};
   };
   auto solve_step = [&](Vec& px, Vec& py) {
     dev.download(dev.d_p(), p.data(), dim);
@@ -1593,96 +1352,61 @@ ExitStatus sqp_core(NewtonSystem& sys, const Vec& scales, const std::vector<Iter
     rep.t_kkt_solve += since(t0);
 
     t0 = clk::now();
-    constexpr double alpha_max = 1.0;
-    double alpha = alpha_max;
-    bool call_feasibility_restoration = false;
     const FilterEntry current_entry{f, norm_1(c_e.data(), m_e)};
     double D_phi = 0.0;  // :360
     for (int i = 0; i < n; ++i) D_phi += g[i] * p_x[i];
+    // The interior-point line search with alpha_max = 1 and no barrier term.  y moves with the primal step: this
+    // driver reads ls.alpha (ls.t_alpha) alone, and a correction keeps the full step (:435: alpha_soc is never recomputed).
+    ls.start(filter, full_step_rejected_counter, 0.0, current_entry, 1.0, 1.0, D_phi);
+    Vec soc_px(n), soc_py(m_e), c_e_soc;
 
-    while (true) {  // :364
-      trial_x = axpy(x, alpha, p_x);
-      trial_y = axpy(y, alpha, p_y);
-      eval_values(trial_x);
-      read_trial();
-      if (!std::isfinite(trial_f) || !all_finite(trial_c_e.data(), m_e)) {  // :373-384
-        alpha *= alpha_reduction_factor;
-        if (alpha < alpha_min) {
-          call_feasibility_restoration = true;
-          break;
-        }
-        continue;
+    while (ls.want != Want::Done) switch (ls.want) {
+      case Want::Eval:  // :364-384
+        trial_x = axpy(x, ls.t_alpha, p_x);
+        trial_y = axpy(y, ls.t_alpha, p_y);
+        ls.on_trial(trial_out());
+        break;
+      case Want::SocSolve: {  // :397-468: new bottom rows of the rhs, SAME factorization
+        if (ls.soc_first) c_e_soc = c_e;
+        for (int j = 0; j < m_e; ++j) c_e_soc[j] = ls.alpha_soc * c_e_soc[j] + trial_c_e[j];  // :435
+        Vec rhs(dim, 0.0);
+        for (int i = 0; i < n; ++i) rhs[i] = -g[i];
+        add_At_v(st.Ae, cur.Ae(), nullptr, y.data(), 1.0, rhs);
+        for (int j = 0; j < m_e; ++j) rhs[n + j] = -c_e_soc[j];
+        SLPX_HIP_CHECK(hipMemcpyAsync(dev.d_rhs(), rhs.data(), dim * sizeof(double), hipMemcpyHostToDevice,
+                                      dev.stream()));
+        dev.solve();
+        ++rep.solves;
+        solve_step(soc_px, soc_py);
+        ls.on_soc_solve(ls.alpha_max, ls.alpha_max);
+        break;
       }
-      if (filter.try_add(current_entry, FilterEntry{trial_f, norm_1(trial_c_e.data(), m_e)}, D_phi, alpha)) break;
-
-      const double prev_violation = norm_1(c_e.data(), m_e);
-      double next_violation = norm_1(trial_c_e.data(), m_e);
-      // second-order corrections (:397-468): new bottom rows of the rhs, SAME factorization
-      if (alpha == alpha_max && next_violation >= prev_violation) {
-        Vec soc_px = p_x, soc_py = p_y, c_e_soc = c_e;
-        const double alpha_soc = alpha;
-        double soc_violation = next_violation;
-        bool step_acceptable = false;
-        for (int it = 0; it < 5 && !step_acceptable; ++it) {
-          for (int j = 0; j < m_e; ++j) c_e_soc[j] = alpha_soc * c_e_soc[j] + trial_c_e[j];  // :435
-          Vec rhs(dim, 0.0);
-          for (int i = 0; i < n; ++i) rhs[i] = -g[i];
-          add_At_v(st.Ae, cur.Ae(), nullptr, y.data(), 1.0, rhs);
-          for (int j = 0; j < m_e; ++j) rhs[n + j] = -c_e_soc[j];
-          SLPX_HIP_CHECK(hipMemcpyAsync(dev.d_rhs(), rhs.data(), dim * sizeof(double), hipMemcpyHostToDevice,
-                                        dev.stream()));
-          dev.solve();
-          ++rep.solves;
-          solve_step(soc_px, soc_py);
-          trial_x = axpy(x, alpha_soc, soc_px);
-          trial_y = axpy(y, alpha_soc, soc_py);
-          eval_values(trial_x);
-          read_trial();
-          if (filter.try_add(current_entry, FilterEntry{trial_f, norm_1(trial_c_e.data(), m_e)}, D_phi, alpha)) {
-            p_x = soc_px;
-            p_y = soc_py;
-            alpha = alpha_soc;
-            step_acceptable = true;
-            break;
-          }
-          constexpr double kappa_soc = 0.99;
-          next_violation = norm_1(trial_c_e.data(), m_e);
-          if (next_violation > kappa_soc * soc_violation) break;
-          soc_violation = next_violation;
-        }
-        if (step_acceptable) break;
-      }
-      if (alpha == alpha_max) ++full_step_rejected_counter;  // :472-474
-      if (full_step_rejected_counter >= 4 && filter.max_constraint_violation > current_entry.constraint_violation / 10.0 &&
-          filter.last_rejection_due_to_filter()) {  // :478-485
-        filter.max_constraint_violation *= 0.1;
-        filter.reset();
-        continue;
-      }
-      alpha *= alpha_reduction_factor;
-      if (alpha < alpha_min) {  // :492-517
+      case Want::SocEval:
+        trial_x = axpy(x, ls.t_alpha, soc_px);
+        trial_y = axpy(y, ls.t_alpha, soc_py);
+        ls.on_trial(trial_out());
+        break;
+      case Want::KktEval: {  // :492-517
         const double current_kkt = kkt_error_impl<ErrType::ONE_NORM>(st, g, cur.Ae(), c_e.data(), nullptr, nullptr, none,
                                                                      y, none, 0.0, nullptr);
-        trial_x = axpy(x, alpha_max, p_x);
-        trial_y = axpy(y, alpha_max, p_y);
+        trial_x = axpy(x, ls.t_alpha, p_x);
+        trial_y = axpy(y, ls.t_alpha, p_y);
         Vec Vt(st.nV);
         dev.upload_x(trial_x.data());
         dev.upload_duals(none.data(), trial_y.data(), none.data());
         dev.sweep_full();
         dev.download_V(Vt.data());
         VView tv{st, Vt};
-        trial_f = tv.f();
-        std::copy(tv.c_e(), tv.c_e() + m_e, trial_c_e.begin());
-        const double next_kkt = kkt_error_impl<ErrType::ONE_NORM>(st, tv.g_dense(), tv.Ae(), tv.c_e(), nullptr, nullptr,
-                                                                  none, trial_y, none, 0.0, nullptr);
-        if (next_kkt <= 0.999 * current_kkt) break;
-        call_feasibility_restoration = true;
+        ls.on_kkt_errors(current_kkt, kkt_error_impl<ErrType::ONE_NORM>(st, tv.g_dense(), tv.Ae(), tv.c_e(), nullptr, nullptr,
+                                                                        none, trial_y, none, 0.0, nullptr));
         break;
       }
+      case Want::Done: break;
     }
+    const double alpha = ls.alpha;
     rep.t_line_search += since(t0);
 
-    if (call_feasibility_restoration) {  // :521-556
+    if (ls.call_feasibility_restoration) {  // :521-556
       refresh_full(x, y);  // the device V describes x again (the fallback above moved it)
       const double f_x = cur.f();
       const FilterEntry initial_entry{f_x, norm_1(c_e.data(), m_e)};
@@ -1699,7 +1423,6 @@ ExitStatus sqp_core(NewtonSystem& sys, const Vec& scales, const std::vector<Iter
       if (fr_status != ExitStatus::SUCCESS) return fr_status;
       sys.set_gamma_min(1e-10);
     } else {
-      if (alpha == 1.0) full_step_rejected_counter = 0;
       x = trial_x;
       y = trial_y;
     }
@@ -1712,8 +1435,7 @@ ExitStatus sqp_core(NewtonSystem& sys, const Vec& scales, const std::vector<Iter
     E_0 = E0_of(g, c_e, y);
     rep.final_error = E_0;
     if (options.diagnostics)
-      std::fprintf(stderr, "%4d  err %.3e  f %.6e  |c| %.3e  mu %.1e  delta %.3e  gamma %.3e  alpha %.2e  alpha_z %.2e  nfact %d  (sqp)\n",
-                   iterations, E_0, f, norm_1(c_e.data(), m_e), 0.0, rep.delta, rep.gamma, alpha, alpha, sys.last_factorizations());
+      print_iteration(iterations, E_0, f, norm_1(c_e.data(), m_e), 0.0, rep, alpha, alpha, sys.last_factorizations(), "  (sqp)");
     ++iterations;
     if (iterations >= options.max_iterations) return ExitStatus::MAX_ITERATIONS_EXCEEDED;
     if (since(solve_start) > options.timeout) return ExitStatus::TIMEOUT;
@@ -1752,7 +1474,8 @@ ExitStatus newton_core(NewtonSystem& sys, const Vec& scales, const std::vector<I
   if (!all_finite(V.data(), st.nV)) return ExitStatus::NONFINITE_INITIAL_GUESS;  // :125-127
   double f = cur.f();
   Filter filter{0.0};  // :131
-  constexpr double alpha_reduction_factor = 0.5, alpha_min = 1e-20;  // :138-139
+  // (a search of its own, newton.hpp:201-243: no corrections, no restoration to fall back on, a floor of 1e-20)
+  constexpr double alpha_min = 1e-20;  // :138-139
   const bool identity = scaling_is_identity(st, scales);
   auto E0_of = [&](const Vec& gg) {
     return kkt_error_impl<ErrType::INF_NORM_SCALED>(st, gg, nullptr, nullptr, nullptr, nullptr, none, none, none, 0.0,
@@ -1788,12 +1511,12 @@ ExitStatus newton_core(NewtonSystem& sys, const Vec& scales, const std::vector<I
       trial_x = axpy(x, alpha, p_x);
       trial_f = eval_f(trial_x);
       if (!std::isfinite(trial_f)) {
-        alpha *= alpha_reduction_factor;
+        alpha *= kAlphaReduction;
         if (alpha < alpha_min) return ExitStatus::LINE_SEARCH_FAILED;
         continue;
       }
       if (filter.try_add(FilterEntry{f, 0.0}, FilterEntry{trial_f, 0.0}, D_phi, alpha)) break;
-      alpha *= alpha_reduction_factor;
+      alpha *= kAlphaReduction;
       if (alpha < alpha_min) {
         const double current_kkt = norm_1(g.data(), n);
         trial_x = axpy(x, alpha_max, p_x);
@@ -1803,7 +1526,7 @@ ExitStatus newton_core(NewtonSystem& sys, const Vec& scales, const std::vector<I
         dev.download_V(Vt.data());
         VView tv{st, Vt};
         const Vec tg = tv.g_dense();
-        if (norm_1(tg.data(), n) <= 0.999 * current_kkt) {
+        if (norm_1(tg.data(), n) <= kFallbackDecrease * current_kkt) {
           trial_f = tv.f();
           break;
         }
@@ -1817,9 +1540,7 @@ ExitStatus newton_core(NewtonSystem& sys, const Vec& scales, const std::vector<I
     g = cur.g_dense();
     E_0 = E0_of(g);
     rep.final_error = E_0;
-    if (options.diagnostics)
-      std::fprintf(stderr, "%4d  err %.3e  f %.6e  |c| %.3e  mu %.1e  delta %.3e  gamma %.3e  alpha %.2e  alpha_z %.2e  nfact %d  (newton)\n",
-                   iterations, E_0, f, 0.0, 0.0, rep.delta, 0.0, alpha, alpha, sys.last_factorizations());
+    if (options.diagnostics) print_iteration(iterations, E_0, f, 0.0, 0.0, rep, alpha, alpha, sys.last_factorizations(), "  (newton)");
     ++iterations;
     if (iterations >= options.max_iterations) return ExitStatus::MAX_ITERATIONS_EXCEEDED;
     if (since(solve_start) > options.timeout) return ExitStatus::TIMEOUT;

@@ -1,6 +1,7 @@
 // Batched whole solves: B instances of one compiled model, each from its own initial guess, with the
-// options and the compiled structure shared.  Every instance follows the host interior-point driver
-// (ipm.cpp: ipm_core_host, interior_point.hpp:129-878) as Problem::solve() would from its start — its own
+// options and the compiled structure shared.  Every instance follows the interior-point iteration
+// (interior_point.hpp:129-878) as Problem::solve() would from its start, its decisions taken by the code the
+// single-problem drivers share (ipm_line_search.hpp, ipm_decide.h) — its own
 // problem scaling, barrier parameter, filter, δ/γ memory, full-step-rejection counter, iteration count and
 // exit — while the device work of all instances still iterating runs as ONE batched launch per phase:
 // the AD sweeps, the KKT build, the regularized factorization (NewtonSystem::compute with an instance

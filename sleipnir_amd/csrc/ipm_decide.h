@@ -84,6 +84,10 @@ SLPX_DECIDE double ipm_E_mu(const IpmErrOut& e, double m, int m_e, int m_i) {
   constexpr double s_max = 100.0;
   const double s_d = fmax(s_max, (e.y1 + e.z1) / double(m_e + m_i)) / s_max;
   const double s_c = fmax(s_max, e.z1 / double(m_i)) / s_max;
+  // max |s z - m| from max and min of s z.  (The batched driver used to write max(0, sz_max - m, m - sz_min): the
+  // same double for finite sz_max >= sz_min — a - m and m - a are exact negatives of each other, and rounding is
+  // monotone, so fl(sz_max - m) >= fl(sz_min - m): whichever of the two has the larger magnitude is the non-negative
+  // one of {sz_max - m, m - sz_min}, and it is what both forms return.)
   const double comp = m_i ? fmax(fabs(e.sz_max - m), fabs(e.sz_min - m)) : 0.0;
   return ipm_max4(e.dual_inf / s_d, comp / s_c, e.ce_inf, e.cis_inf);
 }

@@ -1259,3 +1259,46 @@ extern "C" void hc_supernode_plan(hc_handle* h, int64_t* out, int32_t cap) {
   out[2] = L.critical_levels;
   for (size_t w = 0; w < L.sn_width_hist.size() && 3 + static_cast<int>(w) < cap; ++w) out[3 + w] = L.sn_width_hist[w];
 }
+
+// ---------------------------------------------------------------------------
+// The filter line search every solver driver runs (sleipnir_amd/csrc/ipm_line_search.hpp), driven by a script: a
+// sequence of searches sharing ONE filter (made for `initial_violation`) and ONE full-step-rejected counter, as the
+// iterations of a solve do.  starts[k] = {alpha_max, alpha_z, D_phi, mu, f, sum ln s, violation} of the k-th search's
+// current iterate and direction; the answers are taken in order, four doubles each: a trial point's
+// {f, violation, sum ln s, finite}, a correction solve's {alpha_soc, alpha_z_soc, -, -}, the fallback's
+// {current error, error at the full step, -, -}.  out rows (8 doubles):
+//   a request  {0 Eval | 1 SocSolve | 2 SocEval | 3 KktEval, t_alpha, t_alpha_z, on_correction, soc_first, alpha_soc, 0, 0}
+//   a search's end  {4, how (LineSearch::End), restoration wanted, alpha, alpha_z, counter, the filter's
+//                    max_constraint_violation, its last rejection was due to the table}
+// Returns the rows (written up to `cap`), or -1 where the answers ran out.
+// ---------------------------------------------------------------------------
+#include "../../sleipnir_amd/csrc/ipm_line_search.hpp"
+
+extern "C" int32_t hc_line_search(double initial_violation, int32_t counter, const double* starts, int32_t n_starts,
+                                  const double* answers, int32_t n_answers, double* out, int32_t cap) {
+  using slpx::ipm_host::LineSearch;
+  using Want = LineSearch::Want;
+  slpx::ipm_host::Filter filter{initial_violation};
+  LineSearch ls;
+  int32_t rows = 0, used = 0;
+  auto put = [&](std::initializer_list<double> row) {
+    if (rows < cap) std::copy(row.begin(), row.end(), out + 8 * static_cast<size_t>(rows));
+    ++rows;
+  };
+  for (int32_t k = 0; k < n_starts; ++k) {
+    const double* s = starts + 7 * static_cast<size_t>(k);
+    ls.start(filter, counter, s[3], FilterEntry{s[4] - s[3] * s[5], s[6]}, s[0], s[1], s[2]);
+    while (ls.want != Want::Done) {
+      put({static_cast<double>(ls.want), ls.t_alpha, ls.t_alpha_z, ls.on_correction ? 1.0 : 0.0, ls.soc_first ? 1.0 : 0.0,
+           ls.alpha_soc, 0.0, 0.0});
+      if (used >= n_answers) return -1;
+      const double* a = answers + 4 * static_cast<size_t>(used++);
+      if (ls.want == Want::SocSolve) ls.on_soc_solve(a[0], a[1]);
+      else if (ls.want == Want::KktEval) ls.on_kkt_errors(a[0], a[1]);
+      else ls.on_trial(IpmTrialOut{a[0], a[1], a[2], a[3]});
+    }
+    put({4.0, static_cast<double>(ls.end), ls.call_feasibility_restoration ? 1.0 : 0.0, ls.alpha, ls.alpha_z,
+         static_cast<double>(counter), filter.max_constraint_violation, filter.last_rejection_due_to_filter() ? 1.0 : 0.0});
+  }
+  return rows;
+}

@@ -74,6 +74,7 @@ def lib():
     sig("hc_solve", None, vp, vp)
     sig("hc_solve_after_factor", None, vp, vp)
     sig("hc_backsub", None, vp, vp, vp, d, vp, vp)
+    sig("hc_line_search", i32, d, i32, vp, i32, vp, i32, vp, i32)
     _lib = L
     return L
 
@@ -87,6 +88,32 @@ INFO_KEYS = ["n", "m_e", "m_i", "nV", "nnz_lhs", "nnz_L", "ldlt_rounds", "ldlt_t
 
 def _fa(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def line_search(searches, initial_violation=1.0, counter=0):
+    """The solvers' filter line search (csrc/ipm_line_search.hpp) driven by scripted answers (hostcheck.cpp:
+    hc_line_search).  searches = [(start, answers), ...] sharing one filter and one full-step-rejected counter;
+    start = (alpha_max, alpha_z, D_phi, mu, f, sum ln s, violation); an answer is a tuple of up to four numbers.
+    Returns the rows: requests ("eval" | "soc_solve" | "soc_eval" | "kkt", t_alpha, t_alpha_z, on_correction, first
+    round, alpha_soc) and, per search, ("done", how, restoration wanted, alpha, alpha_z, counter, the filter's
+    max_constraint_violation, last rejection due to the table) with how in "none", "newton", "correction", "fallback"."""
+    starts = _fa([s for s, _ in searches]).reshape(-1, 7)
+    flat = [tuple(a) + (0.0,) * (4 - len(a)) for _, ans in searches for a in ans]
+    answers = _fa(flat if flat else np.zeros((0, 4))).reshape(-1, 4)
+    out = np.zeros((4096, 8))
+    rows = lib().hc_line_search(float(initial_violation), int(counter), starts.ctypes.data, len(starts),
+                                answers.ctypes.data, len(answers), out.ctypes.data, len(out))
+    if rows < 0:
+        raise RuntimeError("line_search: the script's answers ran out")
+    kinds = ("eval", "soc_solve", "soc_eval", "kkt")
+    how = ("none", "newton", "correction", "fallback")
+    res = []
+    for r in out[:rows]:
+        if r[0] == 4.0:
+            res.append(("done", how[int(r[1])], bool(r[2]), r[3], r[4], int(r[5]), r[6], bool(r[7])))
+        else:
+            res.append((kinds[int(r[0])], r[1], r[2], bool(r[3]), bool(r[4]), r[5]))
+    return res
 
 
 class HostCheck:
