@@ -81,7 +81,8 @@ __device__ __forceinline__ void ipm_lookahead_body(IpmLookaheadArgs A, double* s
   bool wrong = st.n_bad != 0 || st.n_pos != n || st.n_neg != m_e || st.n_zero != 0;
   if (A.tw.mode != 0) {
     // A twin attempt (ldlt_mf_twin_kernel): the policy's choice between the two, from the same counters the host
-    // reads (NewtonSystem::compute_impl — keep the two in step).  The second attempt stands for the policy's next
+    // reads — ldlt_judge and ldlt_second_stands of ldlt_policy.hpp, restated here: through those functions the
+    // compiler schedules this kernel differently.  The second attempt stands for the policy's next
     // one only if the first failed the way that leads to it: beside the unregularized attempt (mode 2) any failure
     // does (:82-102, also a pivot below 1e-4); in the loop too many negative pivots (mode 1: delta x 10, :127-130) or too
     // many positive ones (mode 3: gamma x 10, :131-135), nothing else.

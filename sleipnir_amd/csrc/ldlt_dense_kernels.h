@@ -3,7 +3,7 @@
 // of steps, small problems) — and so does this library where a column of L does not fit the LDS of a task
 // (ldlt_symbolic.cpp: "a single column exceeds the LDS task budget" used to be a refusal).  One workgroup per
 // problem, the matrix in memory (L2 at these sizes), column k and its scaled copy in LDS for the rank-1 update of
-// step k, no pivoting: the delta / gamma policy loop around it (NewtonSystem::compute_impl,
+// step k, no pivoting: the delta / gamma policy loop around it (ldlt_policy.hpp,
 // sparse_regularized_ldlt.hpp:64-152 = dense_regularized_ldlt.hpp:59-136) asks for the inertia, as everywhere.
 // A slow answer instead of none: ~2 dim barriers and dim^3 / 3 multiply-adds on one CU.
 #pragma once

@@ -90,7 +90,7 @@ __device__ __forceinline__ void mf_wait_for_sweep(const MfDev& Mf, LdltStats* st
         }
       }
       // kLdltChainFailure (device.hpp) in n_bad — bit 30, above anything the counts can reach: the host
-      // (NewtonSystem::compute_impl) redoes the step with the chain off
+      // (NewtonSystem::read_stats_redoing_a_failed_chain) redoes the step with the chain off
       if (seen >> 30) atomicOr(&stats[0].n_bad, kLdltChainFailure);
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // V as the sweep's workgroups left it, not as this XCD's L2 remembers it
     }
@@ -982,7 +982,7 @@ __global__ __launch_bounds__(THREADS) void ldlt_mf_step_kernel(
 // problem has (15 workgroups at N = 100, 69 at N = 500): the second attempt costs nothing but power, and a step
 // whose first attempt fails — every third to fourth interior-point iteration on BASELINE's cart-pole, which
 // regularizes throughout — no longer pays a host round trip and a second launch (~47 us).  Which of the two the
-// policy takes is decided twice from the same counters, by the host (NewtonSystem::compute_impl) and by the
+// policy takes is decided twice from the same counters, by the host (ldlt_run_twin, ldlt_policy.hpp) and by the
 // launch that consumes the direction (ipm_lookahead_kernel), so the result is the sequential policy's bit for bit.
 // Workgroups [0, first_end) are the first attempt's (ride-along sums and tasks), the rest the second's tasks:
 // same plan, same V, their own factor, update slots, x hand-over, direction and counters.

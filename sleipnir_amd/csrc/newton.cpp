@@ -235,9 +235,30 @@ void NewtonSystem::reset_regularization() {
   m_prev_gamma.assign(m_opt.batch, 0.0);
 }
 
-// sparse_regularized_ldlt.hpp:64-152, run for every problem of the batch at once.
-// Each trip through the loop is one device factorization of the still-active
-// problems followed by one small stats read-back.
+// sparse_regularized_ldlt.hpp:64-152 is ldlt_policy.hpp: one LdltPolicy per problem and the loops that run it.  What
+// follows are their launchers: what a factorization attempt is on the device for each kind of caller.
+LdltPolicy NewtonSystem::start_policy(int b, bool skip_first) const {
+  LdltPolicy p;
+  p.start(m_s.n, m_s.m_e, m_prev_delta[b], m_prev_gamma[b], m_gamma_min, skip_first);
+  return p;
+}
+// First attempt (:74-87): when the symbolic phase proved that a pivot is structurally zero the attempt is known to
+// end in NumericalIssue (Eigen reports failure on an exactly-zero pivot), so it is not launched.
+bool NewtonSystem::skip_first() const { return m_opt.skip_structurally_singular_attempt && m_l.structurally_singular_unregularized; }
+
+// The counters of the attempt `once()` has just launched.  A chained step (DeviceNlp::sweep_full_for_step) whose sweep
+// or step kernel gave up waiting for the other reports kLdltChainFailure instead of a silent wrong step: the attempt
+// is redone — V swept again from the unchanged state, the system rebuilt — with the chain off.
+template <class Once>
+void NewtonSystem::read_stats_redoing_a_failed_chain(std::vector<LdltStats>& stats, Once&& once) {
+  m_dev->read_stats(stats);
+  if (m_opt.batch != 1 || (stats[0].n_bad & kLdltChainFailure) == 0) return;
+  m_dev->recover_from_chain_failure();
+  m_dev->build_kkt_for_step(/*with_reduce=*/true);
+  once();
+  m_dev->read_stats(stats);
+}
+
 std::vector<FactorInfo> NewtonSystem::compute(bool solve_speculatively) {
   return compute_impl(solve_speculatively ? 1 : 0);
 }
@@ -247,153 +268,56 @@ std::vector<FactorInfo> NewtonSystem::compute(bool solve_speculatively, const st
   if (static_cast<int>(mask.size()) != m_opt.batch) throw std::runtime_error("NewtonSystem::compute: mask length");
   return compute_impl(solve_speculatively ? 1 : 0, &mask);
 }
+// Every problem of the batch at once: each trip through ldlt_run_batch is one device factorization of the
+// still-active problems followed by one small stats read-back.
 std::vector<FactorInfo> NewtonSystem::compute_impl(int mode, const std::vector<uint8_t>* mask) {
-  const bool solve_speculatively = mode >= 1;
   const int B = m_opt.batch;
   m_last_twin_launches = m_last_twin_taken = 0;
   if (mode == 1 && B == 1 && m_twin_attempts && !mask && m_dev->twin_available()) return compute_twin();
-  // With solve_speculatively every factorization attempt is followed at once by the
-  // triangular solves and the back-substitution, BEFORE the host has read the inertia
-  // counters: the device never idles through the host round trip, and in the usual case
-  // (first attempt accepted) the step is complete when the counters arrive.  A rejected
-  // attempt just has its solve overwritten by the next one.
-  auto factor_once = [&](const std::vector<double>& d, const std::vector<double>& g,
-                         const std::vector<uint8_t>& a) {
-    if (solve_speculatively) {
-      m_dev->factor_solve_publish(d, g, a);
-      if (m_after_attempt) m_after_attempt();
-    } else {
-      m_dev->factor(d, g, a);
-    }
-  };
+  std::vector<uint8_t> active = mask ? *mask : std::vector<uint8_t>(B, 1);
+  std::vector<LdltPolicy> pol(B);
+  for (int b = 0; b < B; ++b)
+    if (active[b]) pol[b] = start_policy(b, skip_first());
+  const std::vector<uint8_t> started = active;
   std::vector<LdltStats> stats;
-  // one attempt and its counters.  A chained step (DeviceNlp::sweep_full_for_step) whose sweep or step
-  // kernel gave up waiting for the other reports kLdltChainFailure instead of a silent wrong step: the
-  // attempt is redone — V swept again from the unchanged state, the system rebuilt — with the chain off.
-  auto factor = [&](const std::vector<double>& d, const std::vector<double>& g, const std::vector<uint8_t>& a) {
-    factor_once(d, g, a);
-    m_dev->read_stats(stats);
-    if (B == 1 && (stats[0].n_bad & kLdltChainFailure) != 0) {
-      m_dev->recover_from_chain_failure();
-      m_dev->build_kkt_for_step(/*with_reduce=*/true);
-      factor_once(d, g, a);
-      m_dev->read_stats(stats);
-    }
-  };
-  const int n = m_s.n, m_e = m_s.m_e;
-  std::vector<FactorInfo> info(B, FactorInfo::Success);
-  std::vector<double> delta(B, 0.0), gamma(B, 0.0);
-  std::vector<uint8_t> active(B, 1);
-  if (mask) active = *mask;
-  m_last_factorizations = 0;
-  const double eps = std::numeric_limits<double>::epsilon();
-
-  auto inertia_ok = [&](const LdltStats& st) {
-    return st.n_pos == n && st.n_neg == m_e && st.n_zero == 0;
-  };
-  auto min_abs = [](const LdltStats& st) {
-    double d;
-    std::memcpy(&d, &st.min_abs_bits, sizeof(d));
-    return d;
-  };
-
-  // First attempt: unregularized (:74-87).  When the symbolic phase proved that a
-  // pivot is structurally zero the attempt is known to end in NumericalIssue
-  // (Eigen reports failure on an exactly-zero pivot), so it is not launched.
-  std::vector<uint8_t> need_loop(B, 0);
-  const bool skip_first = m_opt.skip_structurally_singular_attempt &&
-                          m_l.structurally_singular_unregularized;
-  if (!skip_first) {
-    factor(delta, gamma, active);
-    ++m_last_factorizations;
-    for (int b = 0; b < B; ++b) {
-      if (!active[b]) continue;
-      const bool success = stats[b].n_bad == 0;
-      if (success && inertia_ok(stats[b]) && min_abs(stats[b]) >= 1e-4) {
-        m_prev_delta[b] = 0.0;
-        m_prev_gamma[b] = 0.0;
-        active[b] = 0;
+  m_last_factorizations = ldlt_run_batch(pol, active, !skip_first(), [&](const std::vector<double>& d, const std::vector<double>& g, const std::vector<uint8_t>& a) {
+    // With mode 1 every factorization attempt is followed at once by the triangular solves and the
+    // back-substitution, BEFORE the host has read the inertia counters: the device never idles through the host
+    // round trip, and in the usual case (first attempt accepted) the step is complete when the counters arrive.
+    // A rejected attempt just has its solve overwritten by the next one.
+    auto once = [&] {
+      if (mode == 0) {
+        m_dev->factor(d, g, a);
       } else {
-        need_loop[b] = 1;
+        m_dev->factor_solve_publish(d, g, a);
+        if (m_after_attempt) m_after_attempt();
       }
-    }
-  } else {
-    need_loop = active;
-  }
-
-  bool any = false;
-  for (int b = 0; b < B; ++b) {
-    active[b] = need_loop[b];
-    if (need_loop[b]) {
-      any = true;
-      delta[b] = m_prev_delta[b] == 0.0 ? 1e-4 : std::max(m_prev_delta[b] / 2.0, eps);  // :95-98
-      gamma[b] = m_gamma_min;                                                            // :102
-    }
-  }
-  while (any) {
-    factor(delta, gamma, active);
-    ++m_last_factorizations;
-    any = false;
-    for (int b = 0; b < B; ++b) {
-      if (!active[b]) continue;
-      const LdltStats& st = stats[b];
-      if (st.n_bad == 0) {
-        if (inertia_ok(st)) {  // :109-113
-          m_prev_delta[b] = delta[b];
-          m_prev_gamma[b] = gamma[b];
-          active[b] = 0;
-          continue;
-        } else if (st.n_zero > 0) {  // :114-126
-          if (gamma[b] == 0.0) {
-            gamma[b] = 1e-10;
-          } else {
-            delta[b] *= 10.0;
-            gamma[b] *= 10.0;
-          }
-        } else if (st.n_neg > m_e) {  // :127-130
-          delta[b] *= 10.0;
-        } else if (st.n_pos > n) {  // :131-135
-          gamma[b] = gamma[b] == 0.0 ? 1e-10 : gamma[b] * 10.0;
-        }
-      } else {  // :136-141
-        delta[b] *= 10.0;
-        gamma[b] = gamma[b] == 0.0 ? 1e-10 : gamma[b] * 10.0;
-      }
-      if (delta[b] > 1e20 || gamma[b] > 1e20) {  // :145-150
-        info[b] = FactorInfo::NumericalIssue;
-        m_prev_delta[b] = delta[b];
-        m_prev_gamma[b] = gamma[b];
-        active[b] = 0;
-        continue;
-      }
-      any = true;
-    }
-  }
+    };
+    once();
+    read_stats_redoing_a_failed_chain(stats, once);
+    return stats.data();
+  });
+  std::vector<FactorInfo> info(B, FactorInfo::Success);
+  for (int b = 0; b < B; ++b)
+    if (started[b]) info[b] = remember(b, pol[b]);
   return info;
 }
-
-// The policy loop of compute_impl (sparse_regularized_ldlt.hpp:64-152) for one problem, two attempts per launch:
-// the attempt the loop is at and the one it makes next if this one has too many negative pivots (delta x 10,
-// :127-130) — beside the unregularized first attempt, the first guess (:95-102).  The attempts are judged in the
-// policy's order from their own counters, so the sequence of (delta, gamma) tried, the one accepted and the count of
-// factorizations are the sequential loop's; a second attempt the policy would not have made next is ignored.
-// ipm_lookahead_kernel makes the same choice on the device from the same counters: keep the two in step.
-NewtonSystem::TwinLaunch NewtonSystem::twin_first_launch() const {
-  const double eps = std::numeric_limits<double>::epsilon();
-  const double d = m_prev_delta[0] == 0.0 ? 1e-4 : std::max(m_prev_delta[0] / 2.0, eps);  // :95-98
-  const double g = m_gamma_min;                                                             // :102
-  const bool skip_first = m_opt.skip_structurally_singular_attempt && m_l.structurally_singular_unregularized;
-  if (!skip_first) return TwinLaunch{0.0, 0.0, d, g, 2};
-  if (m_twin_expect == 3) return TwinLaunch{d, g, d, g == 0.0 ? 1e-10 : g * 10.0, 3};
-  return TwinLaunch{d, g, d * 10.0, g, 1};
+FactorInfo NewtonSystem::remember(int b, const LdltPolicy& p) {
+  m_prev_delta[b] = p.prev_delta;
+  m_prev_gamma[b] = p.prev_gamma;
+  return p.info;
 }
+
+// What compute_twin's first launch is, from the policy's memory: ipm_lookahead_kernel makes the choice between its
+// two attempts on the device from the same counters and the same predicates (ldlt_policy.hpp).
+LdltLaunch NewtonSystem::twin_first_launch() const { return start_policy(0, skip_first()).launch(m_twin_expect); }
 
 bool NewtonSystem::begin_speculative_compute(bool gated) {
   if (m_spec.valid || m_opt.batch != 1 || !m_twin_attempts || !m_dev->twin_available()) {
     m_dev->ipm_ride_disarm();
     return false;
   }
-  const TwinLaunch tl = twin_first_launch();
+  const LdltLaunch tl = twin_first_launch();
   const DeviceNlp::LaunchBook book = m_dev->save_book();
   m_dev->build_kkt_for_step(/*with_reduce=*/false);
   m_dev->ipm_gate_next_step(gated);
@@ -417,260 +341,110 @@ void NewtonSystem::cancel_speculative_compute(bool launch_ran) {
   m_spec.valid = false;
 }
 
-std::vector<FactorInfo> NewtonSystem::compute_twin() {
-  const int n = m_s.n, m_e = m_s.m_e;
-  std::vector<FactorInfo> info(1, FactorInfo::Success);
-  m_last_factorizations = 0;
-  const double eps = std::numeric_limits<double>::epsilon();
-  auto good = [&](const LdltStats& st) { return st.n_bad == 0 && st.n_pos == n && st.n_neg == m_e && st.n_zero == 0; };
-  auto min_abs = [](const LdltStats& st) {
-    double d;
-    std::memcpy(&d, &st.min_abs_bits, sizeof(d));
-    return d;
-  };
+// ldlt_run_twin's launcher for the system the device's V, s, y, z describe (set_twin_attempts)
+struct NewtonSystem::TwinLauncher {
+  NewtonSystem& sys;
   std::vector<LdltStats> stats;
-  LdltStats first{}, second{};
-  bool have_second = false;
-  // one launch: (d0, g0) and, if the device can, (d1, g1) beside it
+  LdltStats second_stats{};
   bool first_launch = true;
-  auto launch = [&](double d0, double g0, double d1, double g1, int mode) {
-    // (a later launch of the loop evaluates the system from V again, inside the launch, like the first — the
-    // caller's system IS the one V, s, y, z describe, set_twin_attempts — instead of two assembly launches first)
-    if (!first_launch) m_dev->build_kkt_for_step(/*with_reduce=*/false);
-    first_launch = false;
-    auto once = [&] {
-      have_second = m_dev->factor_solve_publish_twin(d0, g0, d1, g1, mode);
-      if (!have_second) m_dev->factor_solve_publish({d0}, {g0}, {1});
-      if (m_after_attempt) m_after_attempt();
-      m_dev->read_stats(stats);
-    };
-    if (m_spec.valid) {
-      // this launch — the policy's first of this compute — was made ahead (begin_speculative_compute) and has run
-      if (m_spec.launch.d0 != d0 || m_spec.launch.g0 != g0 || m_spec.launch.d1 != d1 || m_spec.launch.g1 != g1 || m_spec.launch.mode != mode)
-        throw std::runtime_error("slpx: the step enqueued ahead is not the one the regularization policy makes");
-      m_spec.valid = false;
-      have_second = m_spec.have_second;
-      m_dev->read_stats(stats);
-    } else {
-      once();
-    }
-    // (a chained step that lost its hand-over — compute_impl's factor(): redone unchained from a fresh sweep.
-    // A twin launch itself is never chained, the single-attempt fallback above can be.)
-    if ((stats[0].n_bad & kLdltChainFailure) != 0) {
-      m_dev->recover_from_chain_failure();
-      m_dev->build_kkt_for_step(/*with_reduce=*/true);
-      once();
-    }
-    if (have_second) ++m_last_twin_launches;
-    first = stats[0];
-    if (have_second) {
-      second = m_dev->read_twin_stats();
-      const bool first_good = good(first) && (mode != 2 || min_abs(first) >= 1e-4);
-      const bool neg = first.n_neg > m_e;
-      const bool second_stands = mode == 2 || (mode == 1 && neg) || (mode == 3 && !neg);
-      const int kind = first_good ? 0
-                       : first.n_bad != 0 ? 5
-                       : first.n_zero > 0 ? 3
-                       : second_stands ? (good(second) ? 1 : 2)
-                                       : 4;
-      ++m_twin_hist[kind];
-    }
-  };
-  auto accept = [&](double d, double g, bool is_second) {
-    m_prev_delta[0] = d;
-    m_prev_gamma[0] = g;
-    if (is_second) {
-      m_dev->adopt_twin();
-      ++m_last_twin_taken;
-    }
-    return info;
-  };
-  // the loop's answer to a failed attempt (:114-141); true: it was "too many negative pivots"
-  // (returns which of the loop's answers it was: 1 too many negative pivots, 3 too many positive — the numbers of
-  // the launch modes whose second attempt stands for that answer, IpmTwin::mode —, 0 anything else)
-  auto advance = [&](const LdltStats& st, double& d, double& g) {
-    int answer = 0;
-    if (st.n_bad == 0) {
-      if (st.n_zero > 0) {
-        if (g == 0.0) {
-          g = 1e-10;
-        } else {
-          d *= 10.0;
-          g *= 10.0;
-        }
-      } else if (st.n_neg > m_e) {
-        d *= 10.0;
-        answer = 1;
-      } else if (st.n_pos > n) {
-        g = g == 0.0 ? 1e-10 : g * 10.0;
-        answer = 3;
-      }
-    } else {
-      d *= 10.0;
-      g = g == 0.0 ? 1e-10 : g * 10.0;
-    }
-    return answer;
-  };
-  auto gave_up = [&](double d, double g) {  // :145-150
-    if (!(d > 1e20 || g > 1e20)) return false;
-    info[0] = FactorInfo::NumericalIssue;
-    m_prev_delta[0] = d;
-    m_prev_gamma[0] = g;
-    return true;
-  };
 
-  double d = m_prev_delta[0] == 0.0 ? 1e-4 : std::max(m_prev_delta[0] / 2.0, eps);  // :95-98
-  double g = m_gamma_min;                                                             // :102
-  bool second_is_current = false;  // `second` holds the attempt at (d, g)
-  const bool skip_first = m_opt.skip_structurally_singular_attempt && m_l.structurally_singular_unregularized;
-  if (!skip_first) {  // :74-87
-    launch(0.0, 0.0, d, g, 2);
-    ++m_last_factorizations;
-    if (good(first) && min_abs(first) >= 1e-4) return accept(0.0, 0.0, false);
-    second_is_current = have_second;
-  }
-  // Which answer the second attempt of a launch stands for: the one the loop's first attempt drew in the LAST
-  // compute() (a phase of the solve that needs a larger gamma needs it iteration after iteration — the loop starts
-  // from gamma_min every time, :102), too many negative pivots otherwise and for the later launches of a loop.
-  int expect = m_twin_expect;
-  bool loop_first = true;
-  while (true) {
-    if (!second_is_current) {
-      if (expect == 3) launch(d, g, d, g == 0.0 ? 1e-10 : g * 10.0, 3);
-      else launch(d, g, d * 10.0, g, 1);
-      ++m_last_factorizations;
-      if (good(first)) {
-        if (loop_first) m_twin_expect = 1;
-        return accept(d, g, false);
-      }
-      const int answer = advance(first, d, g);
-      if (loop_first && answer != 0) m_twin_expect = answer;
-      loop_first = false;
-      if (gave_up(d, g)) return info;
-      second_is_current = have_second && answer == expect;  // (d, g) is now what the second attempt was made with
-      expect = 1;
-      if (!second_is_current) continue;
+  bool launch(const LdltLaunch& tl) {
+    DeviceNlp& dev = *sys.m_dev;
+    // (a later launch of the loop evaluates the system from V again, inside the launch, like the first — instead of
+    // two assembly launches first)
+    if (!first_launch) dev.build_kkt_for_step(/*with_reduce=*/false);
+    first_launch = false;
+    bool have_second = false;
+    auto once = [&] {
+      have_second = dev.factor_solve_publish_twin(tl.d0, tl.g0, tl.d1, tl.g1, tl.mode);
+      if (!have_second) dev.factor_solve_publish({tl.d0}, {tl.g0}, {1});
+      if (sys.m_after_attempt) sys.m_after_attempt();
+    };
+    if (sys.m_spec.valid) {
+      // this launch — the policy's first of this compute — was made ahead (begin_speculative_compute) and has run
+      if (sys.m_spec.launch != tl) throw std::runtime_error("slpx: the step enqueued ahead is not the one the regularization policy makes");
+      sys.m_spec.valid = false;
+      have_second = sys.m_spec.have_second;
+    } else {
+      once();
     }
-    second_is_current = false;
-    ++m_last_factorizations;
-    if (good(second)) return accept(d, g, true);
-    advance(second, d, g);
-    if (gave_up(d, g)) return info;
+    // (a twin launch itself is never chained, the single-attempt fallback of once() can be)
+    sys.read_stats_redoing_a_failed_chain(stats, once);
+    if (!have_second) return false;
+    second_stats = dev.read_twin_stats();
+    const int n = sys.m_s.n, m_e = sys.m_s.m_e;
+    const LdltVerdict v = ldlt_judge(stats[0], n, m_e, tl.mode == 2);
+    ++sys.m_twin_hist[v == kLdltAccepted || v == kLdltFailed ? v
+                      : v == kLdltZeroPivots               ? 3
+                      : !ldlt_second_stands(tl.mode, v)     ? 4
+                                                            : (ldlt_ideal(second_stats, n, m_e) ? 1 : 2)];
+    return true;
   }
+  const LdltStats& first() const { return stats[0]; }
+  const LdltStats& second() const { return second_stats; }
+  void adopt_second() { sys.m_dev->adopt_twin(); }
+};
+
+std::vector<FactorInfo> NewtonSystem::compute_twin() {
+  LdltPolicy pol = start_policy(0, skip_first());
+  TwinLauncher launcher{*this};
+  return finish_twin_run(pol, ldlt_run_twin(pol, launcher, &m_twin_expect));
+}
+std::vector<FactorInfo> NewtonSystem::finish_twin_run(const LdltPolicy& pol, const LdltTwinRun& run) {
+  m_last_factorizations = pol.factorizations;
+  m_last_twin_launches = run.launches;
+  m_last_twin_taken = run.taken;
+  return {remember(0, pol)};
 }
 
-std::vector<FactorInfo> NewtonSystem::compute_hooked(const AttemptHooks& hooks) {
-  if (m_opt.batch != 1) throw std::runtime_error("slpx: compute_hooked handles one problem");
-  const int n = m_s.n, m_e = m_s.m_e;
-  std::vector<FactorInfo> info(1, FactorInfo::Success);
-  m_last_factorizations = 0;
-  m_last_twin_launches = m_last_twin_taken = 0;
-  m_hooked_chain_valid = false;
-  const double eps = std::numeric_limits<double>::epsilon();
+// ldlt_run_twin's launcher for a caller that writes the system of every attempt itself (AttemptHooks)
+struct NewtonSystem::HookedLauncher {
+  NewtonSystem& sys;
+  const AttemptHooks& hooks;
+  const bool twin;
   std::vector<LdltStats> stats;
-  LdltStats first{}, second{};
-  bool have_second = false, chain_behind_first = false;
-  const bool twin = static_cast<bool>(hooks.prepare_second) && m_dev->twin_available();
-  // one launch: (d0, g0) and, where the device can, (d1, g1) beside it
-  auto launch = [&](double d0, double g0, double d1, double g1, int mode) {
-    have_second = false;
+  LdltStats second_stats{};
+  bool first_launch = true;
+
+  bool launch(const LdltLaunch& tl) {
+    DeviceNlp& dev = *sys.m_dev;
+    bool have_second = false;
     if (twin) {
       const double *lhs2 = nullptr, *rhs2 = nullptr;
       if (hooks.prepare_pair) {
-        hooks.prepare_pair(d0, g0, d1, g1, &lhs2, &rhs2);
+        hooks.prepare_pair(tl.d0, tl.g0, tl.d1, tl.g1, &lhs2, &rhs2);
       } else {
-        hooks.prepare(d0, g0);
-        hooks.prepare_second(d1, g1, &lhs2, &rhs2);
+        hooks.prepare(tl.d0, tl.g0);
+        hooks.prepare_second(tl.d1, tl.g1, &lhs2, &rhs2);
       }
-      have_second = m_dev->factor_solve_publish_twin_written(d0, g0, d1, g1, mode, lhs2, rhs2);
+      have_second = dev.factor_solve_publish_twin_written(tl.d0, tl.g0, tl.d1, tl.g1, tl.mode, lhs2, rhs2);
     } else {
-      hooks.prepare(d0, g0);
+      hooks.prepare(tl.d0, tl.g0);
     }
-    if (!have_second) m_dev->factor_solve_publish({d0}, {g0}, {1});
+    if (!have_second) dev.factor_solve_publish({tl.d0}, {tl.g0}, {1});
     // (`after` behind the FIRST launch only: a caller that expects its first attempt to be taken; the launches of a
     // ladder would each drag a chain nobody reads)
-    chain_behind_first = false;
-    if (hooks.after && m_last_factorizations == 0) {
-      hooks.after(d0, g0);
-      chain_behind_first = true;
-    }
-    m_dev->read_stats(stats);
-    first = stats[0];
-    if (have_second) {
-      second = m_dev->read_twin_stats();
-      ++m_last_twin_launches;
-    }
-  };
-  auto good = [&](const LdltStats& st) { return st.n_bad == 0 && st.n_pos == n && st.n_neg == m_e && st.n_zero == 0; };
-  auto min_abs = [](const LdltStats& st) {
-    double d;
-    std::memcpy(&d, &st.min_abs_bits, sizeof(d));
-    return d;
-  };
-  auto accept = [&](double d, double g, bool is_second) {
-    m_prev_delta[0] = d;
-    m_prev_gamma[0] = g;
-    if (is_second) {
-      m_dev->adopt_twin();
-      ++m_last_twin_taken;
-    }
-    m_hooked_chain_valid = chain_behind_first && !is_second;
-    return info;
-  };
-  // the loop's answer to a failed attempt (:114-141); 1: it was "too many negative pivots" — what a launch's second
-  // attempt (delta x 10) stands for
-  auto advance = [&](const LdltStats& st, double& d, double& g) {
-    int answer = 0;
-    if (st.n_bad == 0) {
-      if (st.n_zero > 0) {
-        if (g == 0.0) {
-          g = 1e-10;
-        } else {
-          d *= 10.0;
-          g *= 10.0;
-        }
-      } else if (st.n_neg > m_e) {
-        d *= 10.0;
-        answer = 1;
-      } else if (st.n_pos > n) {
-        g = g == 0.0 ? 1e-10 : g * 10.0;
-      }
-    } else {
-      d *= 10.0;
-      g = g == 0.0 ? 1e-10 : g * 10.0;
-    }
-    return answer;
-  };
-  auto gave_up = [&](double d, double g) {  // :145-150
-    if (!(d > 1e20 || g > 1e20)) return false;
-    info[0] = FactorInfo::NumericalIssue;
-    m_prev_delta[0] = d;
-    m_prev_gamma[0] = g;
-    return true;
-  };
-  double d = m_prev_delta[0] == 0.0 ? 1e-4 : std::max(m_prev_delta[0] / 2.0, eps);  // :95-98
-  double g = m_gamma_min;                                                             // :102
-  launch(0.0, 0.0, d, g, 2);  // :74-87 — beside it the loop's first guess
-  ++m_last_factorizations;
-  if (good(first) && min_abs(first) >= 1e-4 && (!hooks.eliminated_min_pivot || hooks.eliminated_min_pivot() >= 1e-4))
-    return accept(0.0, 0.0, false);
-  bool second_is_current = have_second;  // `second` holds the attempt at (d, g)
-  while (true) {
-    if (!second_is_current) {
-      launch(d, g, d * 10.0, g, 1);
-      ++m_last_factorizations;
-      if (good(first)) return accept(d, g, false);
-      const int answer = advance(first, d, g);
-      if (gave_up(d, g)) return info;
-      second_is_current = have_second && answer == 1;  // (d, g) is now what the second attempt was made with
-      if (!second_is_current) continue;
-    }
-    second_is_current = false;
-    ++m_last_factorizations;
-    if (good(second)) return accept(d, g, true);
-    advance(second, d, g);
-    if (gave_up(d, g)) return info;
+    if (hooks.after && first_launch) hooks.after(tl.d0, tl.g0);
+    first_launch = false;
+    dev.read_stats(stats);
+    if (have_second) second_stats = dev.read_twin_stats();
+    return have_second;
   }
+  const LdltStats& first() const { return stats[0]; }
+  const LdltStats& second() const { return second_stats; }
+  void adopt_second() { sys.m_dev->adopt_twin(); }
+};
+
+std::vector<FactorInfo> NewtonSystem::compute_hooked(const AttemptHooks& hooks) {
+  if (m_opt.batch != 1) throw std::runtime_error("slpx: compute_hooked handles one problem");
+  m_hooked_chain_valid = false;
+  LdltPolicy pol = start_policy(0, /*skip_first=*/false);
+  HookedLauncher launcher{*this, hooks, static_cast<bool>(hooks.prepare_second) && m_dev->twin_available()};
+  const double extra = hooks.eliminated_min_pivot ? hooks.eliminated_min_pivot() : std::numeric_limits<double>::infinity();
+  // (later launches hold the attempt and its delta x 10 only: no memory of what the loop's first attempt drew)
+  const LdltTwinRun run = ldlt_run_twin(pol, launcher, nullptr, extra);
+  m_hooked_chain_valid = hooks.after && pol.factorizations == 1;  // the accepted attempt is the one `after` followed
+  return finish_twin_run(pol, run);
 }
 
 bool NewtonSystem::factor_unregularized() {
@@ -681,10 +455,7 @@ bool NewtonSystem::factor_unregularized() {
   std::vector<LdltStats> stats;
   m_dev->read_stats(stats);
   ++m_last_factorizations;
-  for (int b = 0; b < B; ++b)
-    if (stats[b].n_bad != 0 || stats[b].n_pos != m_s.n || stats[b].n_neg != m_s.m_e || stats[b].n_zero != 0)
-      return false;
-  return true;
+  return std::all_of(stats.begin(), stats.begin() + B, [&](const LdltStats& st) { return ldlt_ideal(st, m_s.n, m_s.m_e); });
 }
 
 std::vector<FactorInfo> NewtonSystem::newton_step(bool refresh_ad) {

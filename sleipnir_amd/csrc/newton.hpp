@@ -4,9 +4,9 @@
 // Counterpart of what interior_point() holds across iterations in the reference:
 // the matrix callbacks (interior_point.hpp:199-237), `RegularizedLDLT solver`
 // (:338-352) and the per-iteration Newton step (:426-482).  The δ/γ inertia-
-// correction loop (util/sparse_regularized_ldlt.hpp:82-151) stays on the host so
-// its decisions can be compared one-to-one with the oracle; every numeric
-// factorization attempt inside it is a device launch.
+// correction loop (util/sparse_regularized_ldlt.hpp:82-151) is ldlt_policy.hpp: it
+// stays on the host so its decisions can be compared one-to-one with the oracle;
+// this class launches the numeric factorization attempts it asks for.
 #pragma once
 
 #include <functional>
@@ -17,6 +17,7 @@
 
 #include "device.hpp"
 #include "kkt_plan.hpp"
+#include "ldlt_policy.hpp"
 #include "ldlt_symbolic.hpp"
 #include "nlp.hpp"
 
@@ -29,9 +30,6 @@ struct NewtonOptions {
   int device = 0;
   bool skip_structurally_singular_attempt = true;
 };
-
-// Eigen::ComputationInfo stand-in
-enum class FactorInfo : int { Success = 0, NumericalIssue = 1 };
 
 class FrDevice;
 
@@ -162,7 +160,7 @@ class NewtonSystem {
   KktPlan m_k;
   LdltPlan m_l;
   std::unique_ptr<DeviceNlp> m_dev;
-  double m_gamma_min = 1e-10;
+  double m_gamma_min = kLdltDefaultGammaMin;
   std::vector<double> m_prev_delta, m_prev_gamma;
   int m_last_factorizations = 0;
   std::function<void()> m_after_attempt;
@@ -170,16 +168,21 @@ class NewtonSystem {
   int m_last_twin_launches = 0, m_last_twin_taken = 0;
   bool m_hooked_chain_valid = false;  // compute_hooked: `after` ran behind the attempt that was accepted
   long m_twin_hist[6] = {0, 0, 0, 0, 0, 0};
-  int m_twin_expect = 1;  // what the loop's first attempt drew last time (compute_twin): 1 negative pivots, 3 positive
+  int m_twin_expect = kLdltTooManyNegative;  // what the loop's first launch drew last time (compute_twin): negative pivots or positive
+  // the policy state of problem b from its memory, and the memory from a state that is done
+  LdltPolicy start_policy(int b, bool skip_first) const;
+  FactorInfo remember(int b, const LdltPolicy& p);
+  bool skip_first() const;
+  template <class Once>
+  void read_stats_redoing_a_failed_chain(std::vector<LdltStats>& stats, Once&& once);
+  struct TwinLauncher;
+  struct HookedLauncher;
   std::vector<FactorInfo> compute_twin();
-  struct TwinLaunch {
-    double d0, g0, d1, g1;
-    int mode;
-  };
-  TwinLaunch twin_first_launch() const;  // what compute_twin's first launch is, from the policy's memory
+  std::vector<FactorInfo> finish_twin_run(const LdltPolicy& pol, const LdltTwinRun& run);
+  LdltLaunch twin_first_launch() const;
   struct Speculative {
     bool valid = false, have_second = false;
-    TwinLaunch launch{};
+    LdltLaunch launch{};
     DeviceNlp::LaunchBook book{};
   } m_spec;
   std::vector<int32_t> m_user_lhs_map;

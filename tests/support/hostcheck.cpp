@@ -1302,3 +1302,112 @@ extern "C" int32_t hc_line_search(double initial_violation, int32_t counter, con
   }
   return rows;
 }
+
+// ---------------------------------------------------------------------------
+// The regularization policy every factorization driver runs (csrc/ldlt_policy.hpp), driven without a device: the
+// loops NewtonSystem::compute / compute_twin / compute_hooked run (ldlt_run_batch, ldlt_run_twin), with launchers that
+// answer every attempt from a scripted inertia RESPONSE instead of a factorization.
+//   driver: 0 one attempt per launch (B problems, `mask` or none), 1 twin (reads and writes *twin_expect), 2 hooked
+//   decline: bit k set = the device makes the k-th launch of a twin driver a single attempt
+//   eliminated_min_pivot: the hooked driver's, NaN for none
+//   mem: (prev_delta, prev_gamma) per problem, in and out
+//   table / table_ptr: problem b's response is rows table_ptr[b] .. table_ptr[b + 1] of 8 doubles
+//     {delta below, gamma below, only where gamma == 0, n_pos, n_neg, n_zero, n_bad, min |D|}; the first row that matches
+// out: attempts judged, in order {problem, delta, gamma, 1 if it was a launch's second}; launches of a twin driver
+//   {d0, g0, d1, g1, mode, held two}; info per problem; counts {last_factorizations, last_twin_launches,
+//   last_twin_taken}.  Returns the attempts (written up to cap), -1: an attempt no row answers, -2: no end in sight.
+// ---------------------------------------------------------------------------
+#include "../../sleipnir_amd/csrc/ldlt_policy.hpp"
+
+namespace {
+struct RegScript {
+  const double* table;
+  const int32_t* table_ptr;
+  double* attempts;
+  double* launches;
+  int32_t cap, n_attempts = 0, n_launches = 0;
+  bool unanswered = false;
+  LdltStats respond(int b, double delta, double gamma, bool second) {
+    if (n_attempts < cap) {
+      double* o = attempts + 4 * static_cast<size_t>(n_attempts);
+      o[0] = b, o[1] = delta, o[2] = gamma, o[3] = second;
+    }
+    if (++n_attempts > 4096) throw std::runtime_error("no end in sight");
+    return look_up(b, delta, gamma);
+  }
+  LdltStats look_up(int b, double delta, double gamma) {
+    for (int32_t r = table_ptr[b]; r < table_ptr[b + 1]; ++r) {
+      const double* t = table + 8 * static_cast<size_t>(r);
+      if (!(delta < t[0] && gamma < t[1]) || (t[2] != 0.0 && gamma != 0.0)) continue;
+      LdltStats st{static_cast<int32_t>(t[3]), static_cast<int32_t>(t[4]), static_cast<int32_t>(t[5]), static_cast<int32_t>(t[6]), 0};
+      std::memcpy(&st.min_abs_bits, &t[7], sizeof(double));
+      return st;
+    }
+    unanswered = true;
+    return LdltStats{0, 0, 0, 1, 0};
+  }
+};
+// what ldlt_run_twin asks of a launcher; the attempts are recorded where the loop reads their counters
+struct ScriptedTwinLauncher {
+  RegScript& S;
+  uint32_t decline;
+  LdltLaunch tl{};
+  int32_t k = 0;
+  bool launch(const LdltLaunch& l) {
+    tl = l;
+    const bool two = ((decline >> k++) & 1u) == 0;
+    if (S.n_launches < S.cap) {
+      double* o = S.launches + 6 * static_cast<size_t>(S.n_launches);
+      o[0] = l.d0, o[1] = l.g0, o[2] = l.d1, o[3] = l.g1, o[4] = l.mode, o[5] = two;
+    }
+    ++S.n_launches;
+    return two;
+  }
+  LdltStats first() { return S.respond(0, tl.d0, tl.g0, false); }
+  LdltStats second() { return S.respond(0, tl.d1, tl.g1, true); }
+  int adopted = 0;
+  void adopt_second() { ++adopted; }
+};
+}  // namespace
+
+extern "C" int32_t hc_reg_policy(int32_t n, int32_t m_e, int32_t B, int32_t driver, double gamma_min, int32_t skip_first,
+                                 uint32_t decline, double eliminated_min_pivot, double* mem, const uint8_t* mask,
+                                 const double* table, const int32_t* table_ptr, int32_t* twin_expect, double* attempts,
+                                 double* launches, int32_t cap, int32_t* info, int32_t* counts) {
+  RegScript S{table, table_ptr, attempts, launches, cap};
+  std::vector<LdltPolicy> pol(B);
+  std::vector<uint8_t> active(B, 1);
+  if (mask) active.assign(mask, mask + B);
+  const std::vector<uint8_t> started = active;
+  for (int b = 0; b < B; ++b)
+    if (active[b]) pol[b].start(n, m_e, mem[2 * b], mem[2 * b + 1], gamma_min, skip_first != 0 && driver != 2);
+  counts[0] = counts[1] = counts[2] = 0;
+  try {
+    if (driver == 0) {
+      std::vector<LdltStats> stats(B);
+      counts[0] = ldlt_run_batch(pol, active, skip_first == 0, [&](const std::vector<double>& d, const std::vector<double>& g, const std::vector<uint8_t>& a) {
+        for (int b = 0; b < B; ++b)
+          if (a[b]) stats[b] = S.respond(b, d[b], g[b], false);
+        return stats.data();
+      });
+    } else {
+      ScriptedTwinLauncher L{S, decline};
+      const LdltTwinRun run = driver == 1 ? ldlt_run_twin(pol[0], L, twin_expect)
+                                          : ldlt_run_twin(pol[0], L, nullptr, std::isnan(eliminated_min_pivot) ? INFINITY : eliminated_min_pivot);
+      if (L.adopted != run.taken) return -3;
+      counts[0] = pol[0].factorizations;
+      counts[1] = run.launches;
+      counts[2] = run.taken;
+    }
+  } catch (const std::runtime_error&) {
+    return -2;
+  }
+  if (S.unanswered) return -1;
+  for (int b = 0; b < B; ++b) {
+    info[b] = static_cast<int32_t>(started[b] ? pol[b].info : FactorInfo::Success);
+    if (!started[b]) continue;
+    mem[2 * b] = pol[b].prev_delta;
+    mem[2 * b + 1] = pol[b].prev_gamma;
+  }
+  return S.n_attempts;
+}

@@ -75,6 +75,7 @@ def lib():
     sig("hc_solve_after_factor", None, vp, vp)
     sig("hc_backsub", None, vp, vp, vp, d, vp, vp)
     sig("hc_line_search", i32, d, i32, vp, i32, vp, i32, vp, i32)
+    sig("hc_reg_policy", i32, i32, i32, i32, i32, d, i32, ctypes.c_uint32, d, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp)
     _lib = L
     return L
 
@@ -114,6 +115,44 @@ def line_search(searches, initial_violation=1.0, counter=0):
         else:
             res.append((kinds[int(r[0])], r[1], r[2], bool(r[3]), bool(r[4]), r[5]))
     return res
+
+
+def reg_policy(n, m_e, problems, driver="sequential", gamma_min=1e-10, skip_first=False, decline=0,
+               eliminated_min_pivot=None, mask=None, twin_expect=1):
+    """One compute() of the regularization policy (csrc/ldlt_policy.hpp) under the loop of a driver — "sequential"
+    (any number of problems, optionally masked), "twin" or "hooked" (one problem) — with scripted inertia counters
+    (hostcheck.cpp: hc_reg_policy).  problems = [((prev_delta, prev_gamma), response), ...]; a response is a list of
+    rows (delta below, gamma below, only where gamma == 0, n_pos, n_neg, n_zero, n_bad, min |D|), the first row that
+    matches answers an attempt.  decline: bit k set = the k-th launch of a twin driver holds one attempt only.
+    Returns a dict: attempts (per problem, the (delta, gamma) judged in order), seconds (the attempts, over all
+    problems, that were a launch's second), last_was_second, launches ((d0, g0, d1, g1, mode, held two) of a twin driver), info and
+    memory per problem, factorizations, twin_launches, twin_taken, twin_expect."""
+    B = len(problems)
+    mem = _fa([m for m, _ in problems]).reshape(B, 2).copy()
+    table = _fa([row for _, resp in problems for row in resp]).reshape(-1, 8)
+    table_ptr = np.ascontiguousarray(np.cumsum([0] + [len(resp) for _, resp in problems]), dtype=np.int32)
+    msk = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+    expect = np.array([twin_expect], dtype=np.int32)
+    cap = 4096
+    attempts, launches = np.zeros((cap, 4)), np.zeros((cap, 6))
+    info, counts = np.zeros(B, dtype=np.int32), np.zeros(3, dtype=np.int32)
+    rows = lib().hc_reg_policy(n, m_e, B, ("sequential", "twin", "hooked").index(driver), float(gamma_min), int(skip_first),
+                               int(decline), float("nan") if eliminated_min_pivot is None else float(eliminated_min_pivot),
+                               mem.ctypes.data, None if msk is None else msk.ctypes.data, table.ctypes.data,
+                               table_ptr.ctypes.data, expect.ctypes.data, attempts.ctypes.data, launches.ctypes.data, cap,
+                               info.ctypes.data, counts.ctypes.data)
+    if rows < 0:
+        raise RuntimeError({-1: "reg_policy: an attempt no row of the response answers",
+                            -2: "reg_policy: the loop does not end", -3: "reg_policy: adopted and taken differ"}[rows])
+    att = attempts[:rows]
+    n_launches = int(np.count_nonzero(launches[:, 4]))
+    return {"attempts": [[(r[1], r[2]) for r in att if int(r[0]) == b] for b in range(B)],
+            "seconds": [(r[1], r[2]) for r in att if r[3] != 0.0],
+            "last_was_second": bool(rows and att[-1][3] != 0.0),
+            "launches": [(r[0], r[1], r[2], r[3], int(r[4]), bool(r[5])) for r in launches[:n_launches]],
+            "info": [int(v) for v in info], "memory": [tuple(m) for m in mem],
+            "factorizations": int(counts[0]), "twin_launches": int(counts[1]), "twin_taken": int(counts[2]),
+            "twin_expect": int(expect[0])}
 
 
 class HostCheck:
