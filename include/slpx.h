@@ -162,7 +162,9 @@ int slpx_problem_solve_sized(slpx_problem* p, const slpx_options* opt, uint32_t 
 void slpx_problem_get_duals(const slpx_problem* p, double* s, double* y, double* z);
 /* Batched whole solves: B instances of this problem from x0[B][n] (decision-variable order), each as
  * slpx_problem_solve would run from that start (its own scaling, barrier parameter, filter, regularization
- * memory, restoration, exit), with the options shared; options as slpx_problem_solve_sized, except that
+ * memory, restoration, exit), with the options shared.  The solver follows the kinds of constraints present, as
+ * slpx_problem_solve does (Newton without constraints, SQP with equality constraints only, interior point otherwise),
+ * and each of the three runs all instances in lockstep on the device; options as slpx_problem_solve_sized, except that
  * `spy` and `diagnostics` are ignored.  The timeout applies to the whole batch: instances still running
  * when it expires report TIMEOUT.  The values of the problem's variables are not changed.  Outputs may be
  * NULL: status[B] (ExitStatus), x[B][n], s[B][m_i], y[B][m_e], z[B][m_i], cost[B] (unscaled f at the end),
@@ -174,6 +176,11 @@ void slpx_problem_get_duals(const slpx_problem* p, double* s, double* y, double*
 int slpx_problem_solve_batch(slpx_problem* p, int32_t batch, const double* x0, const slpx_options* opt,
                              uint32_t options_bytes, int32_t* status, double* x, double* s, double* y, double* z,
                              double* cost, int32_t* iterations, int32_t* restorations, slpx_report* report);
+/* The last slpx_problem_solve_batch of this problem: out[4] = {batch, lockstep rounds (batched Newton-step
+ * computations of the outer loop), instances handed to the batch-1 system for restoration,
+ * driver: 0 none needed (constant problem / conflicting bounds), 1 interior point, 2 SQP, 3 Newton}.
+ * Returns 0, -1 if no batch has been solved.  An addition within ABI version 6, detected like the one above. */
+int slpx_problem_batch_stats(const slpx_problem* p, int64_t* out);
 /* feasibility_restoration (solver/util/feasibility_restoration.hpp:347-628) on its own: from the
  * iterate (x[n], s[m_i], y[m_e], z[m_i], mu) — all in/out but mu — build the restoration model,
  * run `steps` iterations of its interior-point loop, leave it the way the reference does when its

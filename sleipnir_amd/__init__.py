@@ -166,6 +166,8 @@ def lib() -> ctypes.CDLL:
     if hasattr(L, "slpx_problem_solve_batch"):
         sig("slpx_problem_solve_batch", ctypes.c_int, vp, i32, vp, ctypes.POINTER(Options), ctypes.c_uint32, vp, vp, vp,
             vp, vp, vp, vp, vp, ctypes.POINTER(Report))
+    if hasattr(L, "slpx_problem_batch_stats"):
+        sig("slpx_problem_batch_stats", ctypes.c_int, vp, vp)
     _lib = L
     return L
 
@@ -257,7 +259,9 @@ class Problem:
     def solve_batch(self, x0, tolerance=1e-8, max_iterations=5000, timeout=0.0, feasible_ipm=False):
         """B instances from the rows of x0 (B x n), each as solve() from that start
         (slpx_problem_solve_batch).  Returns a dict of arrays: status, x, s, y, z, cost, iterations,
-        restorations, and the batch's report."""
+        restorations, the batch's report, and how the batch ran (slpx_problem_batch_stats): rounds (lockstep
+        Newton-step computations), handoffs (instances handed to the batch-1 system for restoration) and
+        driver (0 none needed, 1 interior point, 2 SQP, 3 Newton)."""
         L = lib()
         if not hasattr(L, "slpx_problem_solve_batch"):
             raise SlpxError(f"{LIB_PATH} has no slpx_problem_solve_batch")
@@ -277,7 +281,18 @@ class Problem:
         if rc != 0:
             raise SlpxError(L.slpx_last_error().decode())
         out["report"] = {f[0]: getattr(rep, f[0]) for f in Report._fields_}
+        out["rounds"], out["handoffs"], out["driver"] = self.batch_stats()[1:]
         return out
+
+    def batch_stats(self):
+        """(batch, rounds, handoffs, driver) of the last solve_batch (slpx_problem_batch_stats)."""
+        L = lib()
+        if not hasattr(L, "slpx_problem_batch_stats"):
+            raise SlpxError(f"{LIB_PATH} has no slpx_problem_batch_stats")
+        st = np.zeros(4, dtype=np.int64)
+        if L.slpx_problem_batch_stats(self._h, st.ctypes.data) != 0:
+            raise SlpxError("no batch has been solved")
+        return tuple(int(v) for v in st)
 
     def restoration_steps(self, x, s, y, z, mu, steps, tolerance=1e-8, max_iterations=5000):
         """feasibility_restoration from the given iterate, `steps` iterations (slpx_problem_restoration_steps)."""

@@ -163,6 +163,10 @@ int slpx_problem_solve_batch(slpx_problem* p, int32_t batch, const double* x0, c
     }
     const slpx::BatchSolveResult r = p->problem.solve_batch(batch, x0, opt);
     const size_t B = static_cast<size_t>(batch);
+    p->batch_stats[0] = batch;
+    p->batch_stats[1] = r.rounds;
+    p->batch_stats[2] = r.handoffs;
+    p->batch_stats[3] = r.driver;
     for (size_t b = 0; b < B; ++b) {
       if (status) status[b] = static_cast<int32_t>(r.status[b]);
       if (cost) cost[b] = r.cost[b];
@@ -182,6 +186,12 @@ int slpx_problem_solve_batch(slpx_problem* p, int32_t batch, const double* x0, c
                             q.restoration_iterations, q.t_restoration_setup, q.t_restoration};
     }
   });
+}
+
+int slpx_problem_batch_stats(const slpx_problem* p, int64_t* out) {
+  if (p == nullptr || out == nullptr || p->batch_stats[0] == 0) return -1;
+  std::copy(p->batch_stats, p->batch_stats + 4, out);
+  return 0;
 }
 
 int slpx_problem_restoration_steps(slpx_problem* p, const slpx_options* o, double* x, double* sv, double* y,

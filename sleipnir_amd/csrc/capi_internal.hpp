@@ -19,5 +19,7 @@ struct slpx_system {
 struct slpx_problem {
   slp::Problem<double> problem;
   double t_compile = 0.0;
+  // slpx_problem_batch_stats: the last slpx_problem_solve_batch (batch = 0: none yet)
+  int64_t batch_stats[4] = {0, 0, 0, 0};
   std::unique_ptr<slpx_system> borrowed;  // slpx_problem_system()
 };

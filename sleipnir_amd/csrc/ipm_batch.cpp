@@ -33,22 +33,6 @@ struct Instance {
   LineSearch ls;  // where the instance stands in its line search: the device work it waits for
 };
 
-// the reductions of batch_errors_kernel (BatchErr) as the fields the shared decisions read
-IpmErrOut err_of(const double* e) {
-  IpmErrOut o{};
-  o.dual_inf_u = e[BE_DUALU_INF], o.sz_max_u = e[BE_COMPU_INF], o.ce_inf_u = e[BE_CEU_INF], o.cis_inf_u = e[BE_CISU_INF];
-  o.y1_u = e[BE_YU1], o.z1_u = e[BE_ZU1];
-  o.dual_inf = e[BE_DUAL_INF], o.sz_min = e[BE_SZ_MIN], o.sz_max = e[BE_SZ_MAX], o.ce_inf = e[BE_CE_INF], o.cis_inf = e[BE_CIS_INF];
-  o.y1 = e[BE_Y1], o.z1 = e[BE_Z1];
-  o.f = e[BE_F], o.viol = e[BE_CE_1] + e[BE_CIS_1], o.logsum = e[BE_LOGSUM];
-  o.aetce_sq = e[BE_AETCE2], o.ce_sq = e[BE_CE2], o.aitcp_sq = e[BE_AITCM2], o.cp_sq = e[BE_CM2];
-  o.x_inf = e[BE_X_INF], o.s_inf = e[BE_S_INF];
-  o.finite = e[BE_X_BAD] == 0.0 && e[BE_S_BAD] == 0.0 ? 1.0 : 0.0;
-  o.ci_all_pos = e[BE_CI_NONPOS] == 0.0 ? 1.0 : 0.0;
-  return o;
-}
-double error_one_norm(const double* e) { return e[BE_DUAL_1] + e[BE_COMP_1] + e[BE_CE_1] + e[BE_CIS_1]; }
-
 }  // namespace
 
 void interior_point_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales,
@@ -62,6 +46,8 @@ void interior_point_batch(NewtonSystem& sys, NewtonSystem& single, const std::ve
     throw std::runtime_error("interior_point_batch: wrong lengths");
   if (m_i == 0) throw std::runtime_error("interior_point_batch: a problem with inequality constraints only");
   SolveReport& rep = out.report;
+  out.driver = 1;
+  out.rounds = out.handoffs = 0;
 
   BatchIpmDevice bd(sys);
   bd.set_scales(scales);
@@ -149,6 +135,7 @@ void interior_point_batch(NewtonSystem& sys, NewtonSystem& single, const std::ve
     rep.t_kkt_build += since(t0);
     t0 = clk::now();
     const std::vector<FactorInfo> info = sys.compute(/*solve_speculatively=*/true, bd.active);
+    ++out.rounds;
     rep.factorizations += sys.last_factorizations();
     rep.solves += sys.last_factorizations();
     rep.t_kkt_decomp += since(t0);
@@ -209,6 +196,7 @@ void interior_point_batch(NewtonSystem& sys, NewtonSystem& single, const std::ve
       Instance& I = inst[b];
       if (!I.running || !I.ls.call_feasibility_restoration) continue;
       const auto t_fr = clk::now();
+      ++out.handoffs;
       Vec x, s, y, z, V;
       bd.get_instance(b, x, s, y, z, V);
       VView cur{st, V};

@@ -35,6 +35,22 @@ enum BatchErr {
 };
 constexpr int kBatchErrReduced = kBatchErrN - 1;  // all but BE_F
 
+// the reductions of batch_errors_kernel (one instance's BatchErr) as the fields the shared decisions read
+inline IpmErrOut err_of(const double* e) {
+  IpmErrOut o{};
+  o.dual_inf_u = e[BE_DUALU_INF], o.sz_max_u = e[BE_COMPU_INF], o.ce_inf_u = e[BE_CEU_INF], o.cis_inf_u = e[BE_CISU_INF];
+  o.y1_u = e[BE_YU1], o.z1_u = e[BE_ZU1];
+  o.dual_inf = e[BE_DUAL_INF], o.sz_min = e[BE_SZ_MIN], o.sz_max = e[BE_SZ_MAX], o.ce_inf = e[BE_CE_INF], o.cis_inf = e[BE_CIS_INF];
+  o.y1 = e[BE_Y1], o.z1 = e[BE_Z1];
+  o.f = e[BE_F], o.viol = e[BE_CE_1] + e[BE_CIS_1], o.logsum = e[BE_LOGSUM];
+  o.aetce_sq = e[BE_AETCE2], o.ce_sq = e[BE_CE2], o.aitcp_sq = e[BE_AITCM2], o.cp_sq = e[BE_CM2];
+  o.x_inf = e[BE_X_INF], o.s_inf = e[BE_S_INF];
+  o.finite = e[BE_X_BAD] == 0.0 && e[BE_S_BAD] == 0.0 ? 1.0 : 0.0;
+  o.ci_all_pos = e[BE_CI_NONPOS] == 0.0 ? 1.0 : 0.0;
+  return o;
+}
+inline double error_one_norm(const double* e) { return e[BE_DUAL_1] + e[BE_COMP_1] + e[BE_CE_1] + e[BE_CIS_1]; }
+
 // The device side of the batched driver (ipm_batch_launch.hip, kernels: ipm_batch_kernels.h): the iterate, the
 // trial point, the directions and the second-order correction's accumulators of every instance, batch-major, and the
 // per-instance parameters of a launch.  Launches take effect for the instances flagged in `active` only.
@@ -87,12 +103,16 @@ struct BatchSolveResult {
   std::vector<double> cost;                           // [B] unscaled f at the last iterate
   std::vector<int> iterations, restorations;          // [B]
   SolveReport report;                                 // batch totals; wall-clock phases of the batch
+  // how the batch ran: lockstep rounds (batched Newton-step computations of the outer loop), instances handed to the
+  // batch-1 system for restoration, and the driver: 0 none needed, 1 interior point, 2 SQP, 3 Newton
+  int64_t rounds = 0, handoffs = 0;
+  int driver = 0;
 };
 
 // x0 = [B][n]; scales = [B][1 + m_e + m_i] (compute_problem_scaling at each instance's x0); `run[b]` = 0:
 // instance b is not solved here (its status in `out` is left as the caller set it).  `sys` is the batch
 // system (batch() == B, tape at unit scales), `single` the batch-1 system of the same model (restoration).
-// Problems with inequality constraints only (the others go to newton() / sqp() one by one).
+// Problems with inequality constraints only (the others: sqp_batch / newton_batch, eq_batch.hpp).
 void interior_point_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales,
                           const Options& options, const std::vector<double>& x0, const std::vector<uint8_t>& run,
                           BatchSolveResult& out);

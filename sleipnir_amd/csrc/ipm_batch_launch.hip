@@ -1,8 +1,11 @@
-// Launch wrappers of the batched interior-point kernels (ipm_batch_kernels.h).
+// Launch wrappers of the batched interior-point kernels (ipm_batch_kernels.h), and of the batched SQP / Newton
+// kernels (eq_batch_kernels.h), which share the errors, scaling and input kernels of the former.
 #include <algorithm>
 
+#include "eq_batch.hpp"
 #include "ipm_batch.hpp"
 
+#include "eq_batch_kernels.h"
 #include "ipm_batch_kernels.h"
 
 namespace slpx {
@@ -257,6 +260,199 @@ void BatchIpmDevice::commit() {
   DeviceNlp& dev = sys.device();
   hipLaunchKernelGGL(batch_commit_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(),
                      BatchIter{m_tx.p, m_ts.p, m_ty.p, m_tz.p}, BatchIter{m_x.p, m_s.p, m_y.p, m_z.p}, m_mu.p, m_active.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+}
+
+// ---- BatchEqDevice (eq_batch.hpp) ----
+
+BatchEqDevice::BatchEqDevice(NewtonSystem& sys_) : sys(sys_) {
+  const NlpStructure& s = sys.structure();
+  if (s.m_i != 0) throw std::runtime_error("BatchEqDevice: a model without inequality constraints only");
+  B = sys.batch();
+  n = s.n;
+  m_e = s.m_e;
+  dim = n + m_e;
+  ns = s.n_scales();
+  nV = s.nV;
+  alpha.assign(B, 0.0);
+  alpha_soc.assign(B, 0.0);
+  mode.assign(B, 0);
+  first.assign(B, 0);
+  active.assign(B, 0);
+  m_scale_idx.upload(s.V_scale_idx);
+  m_is_static.upload(s.V_is_static);
+  m_static_raw.upload(s.V_static_raw);
+  m_scales.alloc(static_cast<size_t>(B) * ns);
+  m_active.alloc(B);
+  m_first.alloc(B);
+  m_mode.alloc(B);
+  m_alpha.alloc(B);
+  m_alpha_soc.alloc(B);
+  m_zero.upload(std::vector<double>(B, 0.0));  // (the barrier parameter batch_errors_kernel reads: none here)
+  m_none.alloc(1);                             // (s, z of an iterate without inequality rows: never read)
+  m_out.alloc(static_cast<size_t>(B) * kBatchErrN);
+  const size_t Bn = at_least_1(static_cast<size_t>(B) * n), Be = at_least_1(static_cast<size_t>(B) * m_e);
+  for (auto* b : {&m_x, &m_tx, &m_px, &m_sx}) b->alloc(Bn);
+  for (auto* b : {&m_y, &m_ty, &m_py, &m_sy, &m_tce, &m_sce}) b->alloc(Be);
+  m_Vcur.alloc(static_cast<size_t>(B) * nV);
+}
+
+void BatchEqDevice::upload() {
+  hipStream_t st = sys.device().stream();
+  auto put = [&](auto& buf, const auto& v) {
+    SLPX_HIP_CHECK(hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, st));
+  };
+  put(m_active, active);
+  put(m_alpha, alpha);
+  put(m_alpha_soc, alpha_soc);
+  put(m_mode, mode);
+  put(m_first, first);
+  // (pageable sources: the host may change its vectors once the copies are through)
+  SLPX_HIP_CHECK(hipStreamSynchronize(st));
+}
+
+void BatchEqDevice::set_scales(const std::vector<double>& scales) {
+  if (scales.size() != m_scales.n) throw std::runtime_error("BatchEqDevice::set_scales: wrong length");
+  SLPX_HIP_CHECK(hipMemcpy(m_scales.p, scales.data(), scales.size() * sizeof(double), hipMemcpyHostToDevice));
+}
+
+void BatchEqDevice::set_iterate(const std::vector<double>& x, const std::vector<double>& y) {
+  if (x.size() != static_cast<size_t>(B) * n || y.size() != static_cast<size_t>(B) * m_e)
+    throw std::runtime_error("BatchEqDevice::set_iterate: wrong lengths");
+  if (!x.empty()) SLPX_HIP_CHECK(hipMemcpy(m_x.p, x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (!y.empty()) SLPX_HIP_CHECK(hipMemcpy(m_y.p, y.data(), y.size() * sizeof(double), hipMemcpyHostToDevice));
+}
+
+void BatchEqDevice::get_iterate(std::vector<double>& x, std::vector<double>& y) {
+  DeviceNlp& dev = sys.device();
+  x.resize(static_cast<size_t>(B) * n);
+  y.resize(static_cast<size_t>(B) * m_e);
+  if (!x.empty()) dev.download(m_x.p, x.data(), x.size());
+  if (!y.empty()) dev.download(m_y.p, y.data(), y.size());
+}
+
+void BatchEqDevice::get_instance(int b, std::vector<double>& x, std::vector<double>& y, std::vector<double>& V) {
+  if (b < 0 || b >= B) throw std::runtime_error("BatchEqDevice::get_instance: no such instance");
+  DeviceNlp& dev = sys.device();
+  x.resize(n);
+  y.resize(m_e);
+  V.resize(nV);
+  if (n) dev.download(m_x.p + static_cast<size_t>(b) * n, x.data(), n);
+  if (m_e) dev.download(m_y.p + static_cast<size_t>(b) * m_e, y.data(), m_e);
+  dev.download(m_Vcur.p + static_cast<size_t>(b) * nV, V.data(), nV);
+}
+
+void BatchEqDevice::put_instance(int b, const std::vector<double>& x, const std::vector<double>& y) {
+  if (b < 0 || b >= B || x.size() != static_cast<size_t>(n) || y.size() != static_cast<size_t>(m_e))
+    throw std::runtime_error("BatchEqDevice::put_instance: wrong instance or lengths");
+  if (n) SLPX_HIP_CHECK(hipMemcpy(m_x.p + static_cast<size_t>(b) * n, x.data(), n * sizeof(double), hipMemcpyHostToDevice));
+  if (m_e) SLPX_HIP_CHECK(hipMemcpy(m_y.p + static_cast<size_t>(b) * m_e, y.data(), m_e * sizeof(double), hipMemcpyHostToDevice));
+}
+
+void BatchEqDevice::scale_V(int count) {
+  DeviceNlp& dev = sys.device();
+  hipLaunchKernelGGL(batch_scale_V_kernel, dim3(chunks(count), B), dim3(kBatchThreads), 0, dev.stream(), dev.d_V(), nV,
+                     count, m_scale_idx.p, m_is_static.p, m_static_raw.p, m_scales.p, ns, m_active.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+}
+
+void BatchEqDevice::download_out(size_t per_instance, std::vector<double>& out) {
+  out.resize(static_cast<size_t>(B) * per_instance);
+  sys.device().download(m_out.p, out.data(), out.size());
+}
+
+void BatchEqDevice::errors(const double* V, bool trial, std::vector<double>& err) {
+  DeviceNlp& dev = sys.device();
+  const BatchIter it = trial ? BatchIter{m_tx.p, m_none.p, m_ty.p, m_none.p} : BatchIter{m_x.p, m_none.p, m_y.p, m_none.p};
+  hipLaunchKernelGGL(batch_errors_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(), V, nV, nV, it, m_zero.p,
+                     m_scales.p, ns, m_active.p, m_out.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  download_out(kBatchErrN, err);
+}
+
+void BatchEqDevice::refresh(std::vector<double>& err) {
+  DeviceNlp& dev = sys.device();
+  hipStream_t st = dev.stream();
+  hipLaunchKernelGGL(batch_load_state_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), dev.d_x(),
+                     sys.structure().n_inputs(), BatchIter{m_x.p, m_none.p, m_y.p, m_none.p}, m_scales.p, ns, dev.d_s(),
+                     dev.d_y(), dev.d_z(), 1, m_active.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  dev.sweep_full();
+  scale_V(nV);
+  SLPX_HIP_CHECK(hipMemcpyAsync(m_Vcur.p, dev.d_V(), m_Vcur.n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  errors(m_Vcur.p, false, err);
+}
+
+void BatchEqDevice::direction(std::vector<double>& dphi) {
+  DeviceNlp& dev = sys.device();
+  hipLaunchKernelGGL(eq_direction_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(), m_Vcur.p, nV, dev.d_p(),
+                     EqIter{m_px.p, m_py.p}, m_active.p, m_out.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  download_out(1, dphi);
+}
+
+void BatchEqDevice::launch_trial(int with_duals) {
+  DeviceNlp& dev = sys.device();
+  EqTrialArgs A{};
+  A.cur = EqIter{m_x.p, m_y.p};
+  A.trial = EqIter{m_tx.p, m_ty.p};
+  A.newton = EqIter{m_px.p, m_py.p};
+  A.soc = EqIter{m_sx.p, m_sy.p};
+  A.mode = m_mode.p;
+  A.alpha = m_alpha.p;
+  A.in = dev.d_x();
+  A.in_stride = sys.structure().n_inputs();
+  A.S = m_scales.p;
+  A.ns = ns;
+  A.with_duals = with_duals;
+  hipLaunchKernelGGL(eq_trial_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(), A, m_active.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+}
+
+void BatchEqDevice::trial_values(std::vector<double>& met) {
+  DeviceNlp& dev = sys.device();
+  launch_trial(0);
+  dev.sweep_values();
+  scale_V(sys.structure().off_g);
+  hipLaunchKernelGGL(eq_trial_metrics_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(), dev.d_V(), nV,
+                     m_tce.p, m_active.p, m_out.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  download_out(3, met);
+}
+
+void BatchEqDevice::soc_step() {
+  DeviceNlp& dev = sys.device();
+  hipStream_t st = dev.stream();
+  EqSocArgs A{};
+  A.V = m_Vcur.p;
+  A.v_stride = nV;
+  A.y = m_y.p;
+  A.tce = m_tce.p;
+  A.alpha_soc = m_alpha_soc.p;
+  A.first = m_first.p;
+  A.sce = m_sce.p;
+  A.rhs = dev.d_rhs();
+  hipLaunchKernelGGL(eq_soc_rhs_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), A, m_active.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  dev.solve();  // (every instance's factor; the slices of the others are not read)
+  hipLaunchKernelGGL(eq_direction_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), m_Vcur.p, nV, dev.d_p(),
+                     EqIter{m_sx.p, m_sy.p}, m_active.p, static_cast<double*>(nullptr));
+  SLPX_HIP_CHECK(hipGetLastError());
+}
+
+void BatchEqDevice::kkt_fallback(std::vector<double>& err_cur, std::vector<double>& err_trial) {
+  DeviceNlp& dev = sys.device();
+  errors(m_Vcur.p, false, err_cur);
+  launch_trial(1);
+  dev.sweep_full();
+  scale_V(nV);
+  errors(dev.d_V(), true, err_trial);
+}
+
+void BatchEqDevice::commit() {
+  DeviceNlp& dev = sys.device();
+  hipLaunchKernelGGL(eq_commit_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(), EqIter{m_tx.p, m_ty.p},
+                     EqIter{m_x.p, m_y.p}, m_active.p);
   SLPX_HIP_CHECK(hipGetLastError());
 }
 

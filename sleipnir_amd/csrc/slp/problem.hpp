@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../ipm.hpp"
+#include "../eq_batch.hpp"
 #include "../ipm_batch.hpp"
 #include "../newton.hpp"
 #include "variable.hpp"
@@ -253,7 +254,8 @@ class ProblemF64 {
 
   // `batch` instances of this problem from x0 = [batch][n] (decision-variable order), each as solve() would
   // run from that start (ipm_batch.hpp), all with the same options.  The variables' values are left as they
-  // are.  Problems without inequality constraints run their instances one after another through solve().
+  // are.  The driver follows the kinds of constraints present, as solve() does (problem.hpp:335, 403, 512): Newton,
+  // SQP (eq_batch.hpp) or interior point, every one of them a lockstep batch on the device.
   slpx::BatchSolveResult solve_batch(int batch, const double* x0, const Options& options) {
     if (batch <= 0) throw std::runtime_error("solve_batch: batch must be positive");
     if (x0 == nullptr) throw std::runtime_error("solve_batch: x0 is null");
@@ -280,54 +282,6 @@ class ProblemF64 {
       for (size_t i = 0; i < n; ++i) g.val[m_decision_variables[i].expr] = saved[i];
     };
     compile();
-    if (m_i == 0) {  // newton() / sqp() (problem.hpp:335, 403): the single-problem path, instance by instance
-      // (what solve() leaves in the problem — report, duals, scaling — is put back afterwards; the timeout is the
-      // whole batch's: each solve gets what is left of it)
-      const SolveReport saved_report = m_report;
-      const std::vector<double> saved_scales = m_scales, saved_s = m_s, saved_y = m_y, saved_z = m_z;
-      auto restore_all = [&] {
-        restore();
-        m_report = saved_report;
-        m_scales = saved_scales;
-        m_s = saved_s;
-        m_y = saved_y;
-        m_z = saved_z;
-      };
-      const auto t_start = std::chrono::steady_clock::now();
-      try {
-        for (size_t b = 0; b < B; ++b) {
-          Options opt_b = options;
-          const double used = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-          if (used > options.timeout) {
-            out.status[b] = ExitStatus::TIMEOUT;
-            continue;
-          }
-          opt_b.timeout = options.timeout - used;
-          for (size_t i = 0; i < n; ++i) g.val[m_decision_variables[i].expr] = x0[b * n + i];
-          out.status[b] = solve(opt_b);
-          for (size_t i = 0; i < n; ++i) out.x[b * n + i] = g.val[m_decision_variables[i].expr];
-          std::copy(m_y.begin(), m_y.end(), out.y.begin() + b * m_e);
-          out.cost[b] = m_f ? m_f->value() : 0.0;
-          out.iterations[b] = m_report.iterations;
-          out.restorations[b] = m_report.restorations;
-          out.report.iterations += m_report.iterations;
-          out.report.factorizations += m_report.factorizations;
-          out.report.solves += m_report.solves;
-          out.report.value_sweeps += m_report.value_sweeps;
-          out.report.restorations += m_report.restorations;
-          out.report.restoration_iterations += m_report.restoration_iterations;
-          out.report.final_error = std::max(out.report.final_error, m_report.final_error);
-          out.report.delta = std::max(out.report.delta, m_report.delta);
-          out.report.gamma = std::max(out.report.gamma, m_report.gamma);
-        }
-      } catch (...) {
-        restore_all();
-        throw;
-      }
-      restore_all();
-      out.report.t_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-      return out;
-    }
     slpx::NewtonSystem& sys = batch_system(batch);
     // get_bounds conflict test and problem scaling at each instance's x0 (problem.hpp:597-616), from one batched
     // sweep at unit scales
@@ -356,7 +310,9 @@ class ProblemF64 {
     if (!conflict) {
       const std::vector<double> x0v(x0, x0 + B * n);
       try {
-        slpx::interior_point_batch(sys, *m_sys, scales, options, x0v, run, out);
+        if (m_i > 0) slpx::interior_point_batch(sys, *m_sys, scales, options, x0v, run, out);
+        else if (m_e > 0) slpx::sqp_batch(sys, *m_sys, scales, options, x0v, run, out);
+        else slpx::newton_batch(sys, *m_sys, scales, options, x0v, run, out);
       } catch (...) {
         reinstall_scaling();
         throw;

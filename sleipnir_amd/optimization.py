@@ -97,7 +97,9 @@ class IterationInfo:
 class BatchResult:
     """What Problem.solve_batch returns: per instance the ExitStatus, the end iterate (x: (B, n),
     s, z: (B, m_i), y: (B, m_e)), the unscaled cost, the iteration and restoration counts; `report` holds
-    the batch's totals and wall-clock phases."""
+    the batch's totals and wall-clock phases.  How the batch ran: `rounds` lockstep Newton-step computations,
+    `handoffs` instances handed to the batch-1 system for restoration, `driver` 0 none needed, 1 interior
+    point, 2 SQP, 3 Newton."""
     status: list
     x: np.ndarray
     s: np.ndarray
@@ -107,6 +109,9 @@ class BatchResult:
     iterations: np.ndarray
     restorations: np.ndarray
     report: dict
+    rounds: int = 0
+    handoffs: int = 0
+    driver: int = 0
 
 
 class Problem:
@@ -209,7 +214,7 @@ class Problem:
         r = self._p.solve_batch(guesses, timeout=timeout, **kwargs)
         return BatchResult(status=[ExitStatus(int(s)) for s in r["status"]], x=r["x"], s=r["s"], y=r["y"],
                            z=r["z"], cost=r["cost"], iterations=r["iterations"], restorations=r["restorations"],
-                           report=r["report"])
+                           report=r["report"], rounds=r["rounds"], handoffs=r["handoffs"], driver=r["driver"])
 
     def multistart(self, initial_guesses, **kwargs):
         """multistart.hpp:45-79 as one batched solve: every row of `initial_guesses` a start, then
