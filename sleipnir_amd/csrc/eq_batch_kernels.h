@@ -1,4 +1,4 @@
-// Kernels of the batched SQP and Newton drivers (eq_batch.cpp): the conventions of ipm_batch_kernels.h — B instances
+// Kernels of the batched SQP and Newton drivers (batch_lockstep.cpp): the conventions of ipm_batch_kernels.h — B instances
 // of one compiled model without inequality rows, each in its own slice of batch-major buffers, one 256-thread workgroup
 // per instance, grid (B).  An instance whose active flag is 0 is skipped: nothing of its slice is read or written.
 // Every reduction runs in an order fixed by the model's sizes alone (strided per-thread partials, then block_reduce),

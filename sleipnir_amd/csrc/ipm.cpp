@@ -1472,10 +1472,9 @@ ExitStatus newton_core(NewtonSystem& sys, const Vec& scales, const std::vector<I
   VView cur{st, V};
   Vec g = cur.g_dense();
   if (!all_finite(V.data(), st.nV)) return ExitStatus::NONFINITE_INITIAL_GUESS;  // :125-127
-  double f = cur.f();
   Filter filter{0.0};  // :131
-  // (a search of its own, newton.hpp:201-243: no corrections, no restoration to fall back on, a floor of 1e-20)
-  constexpr double alpha_min = 1e-20;  // :138-139
+  NewtonSearch search;   // (a search of its own, newton.hpp:201-243: no corrections, no restoration, a floor of 1e-20)
+  search.f = cur.f();
   const bool identity = scaling_is_identity(st, scales);
   auto E0_of = [&](const Vec& gg) {
     return kkt_error_impl<ErrType::INF_NORM_SCALED>(st, gg, nullptr, nullptr, nullptr, nullptr, none, none, none, 0.0,
@@ -1483,7 +1482,6 @@ ExitStatus newton_core(NewtonSystem& sys, const Vec& scales, const std::vector<I
   };
   double E_0 = E0_of(g);
   Vec p_x(n), trial_x;
-  double trial_f = 0.0;
   while (E_0 > options.tolerance) {
     if (norm_inf(x.data(), n) > 1e10 || !all_finite(x.data(), n)) return ExitStatus::DIVERGING_ITERATES;  // :164
     for (const auto& cb : callbacks)
@@ -1503,44 +1501,35 @@ ExitStatus newton_core(NewtonSystem& sys, const Vec& scales, const std::vector<I
     dev.download(dev.d_p(), p_x.data(), n);
 
     t0 = clk::now();
-    constexpr double alpha_max = 1.0;
-    double alpha = alpha_max;
     double D_phi = 0.0;
     for (int i = 0; i < n; ++i) D_phi += g[i] * p_x[i];
-    while (true) {  // :201-243
-      trial_x = axpy(x, alpha, p_x);
-      trial_f = eval_f(trial_x);
-      if (!std::isfinite(trial_f)) {
-        alpha *= kAlphaReduction;
-        if (alpha < alpha_min) return ExitStatus::LINE_SEARCH_FAILED;
+    search.start(filter, D_phi);
+    while (search.want != NewtonSearch::Want::Done) {
+      if (search.want == NewtonSearch::Want::Eval) {
+        trial_x = axpy(x, search.t_alpha, p_x);
+        const double trial_f = eval_f(trial_x);
+        search.on_trial(trial_f, std::isfinite(trial_f));
         continue;
       }
-      if (filter.try_add(FilterEntry{f, 0.0}, FilterEntry{trial_f, 0.0}, D_phi, alpha)) break;
-      alpha *= kAlphaReduction;
-      if (alpha < alpha_min) {
-        const double current_kkt = norm_1(g.data(), n);
-        trial_x = axpy(x, alpha_max, p_x);
-        Vec Vt(st.nV);
-        dev.upload_x(trial_x.data());
-        dev.sweep_full();
-        dev.download_V(Vt.data());
-        VView tv{st, Vt};
-        const Vec tg = tv.g_dense();
-        if (norm_1(tg.data(), n) <= kFallbackDecrease * current_kkt) {
-          trial_f = tv.f();
-          break;
-        }
-        return ExitStatus::LINE_SEARCH_FAILED;
-      }
+      const double current_kkt = norm_1(g.data(), n);  // KktEval
+      trial_x = axpy(x, NewtonSearch::alpha_max, p_x);
+      Vec Vt(st.nV);
+      dev.upload_x(trial_x.data());
+      dev.sweep_full();
+      dev.download_V(Vt.data());
+      VView tv{st, Vt};
+      const Vec tg = tv.g_dense();
+      search.on_kkt_errors(current_kkt, norm_1(tg.data(), n), tv.f());
     }
+    if (search.failed) return ExitStatus::LINE_SEARCH_FAILED;
     rep.t_line_search += since(t0);
     x = trial_x;
-    f = trial_f;
     refresh_full(x);  // :254-255
     g = cur.g_dense();
     E_0 = E0_of(g);
     rep.final_error = E_0;
-    if (options.diagnostics) print_iteration(iterations, E_0, f, 0.0, 0.0, rep, alpha, alpha, sys.last_factorizations(), "  (newton)");
+    if (options.diagnostics)
+      print_iteration(iterations, E_0, search.f, 0.0, 0.0, rep, search.alpha, search.alpha, sys.last_factorizations(), "  (newton)");
     ++iterations;
     if (iterations >= options.max_iterations) return ExitStatus::MAX_ITERATIONS_EXCEEDED;
     if (since(solve_start) > options.timeout) return ExitStatus::TIMEOUT;

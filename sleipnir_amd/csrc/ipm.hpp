@@ -114,7 +114,7 @@ ExitStatus feasibility_restoration_steps(NewtonSystem& sys, const std::vector<do
                                          SolveReport* report = nullptr);
 
 // feasibility_restoration as interior_point() enters it (interior_point.hpp:721-771), for a caller that runs the
-// outer iteration itself (the batched driver, ipm_batch.cpp): the iterate (x, s, y, z) and barrier parameter mu of
+// outer iteration itself (the batched loop, batch_lockstep.cpp): the iterate (x, s, y, z) and barrier parameter mu of
 // the outer problem, c_e, c_i, g at x, its constraint violation, and `outer_accepts(entry, D_phi)` — the outer
 // filter's verdict on a restoration iterate.  `scales` must be installed on the device; x, s, y, z in/out.
 ExitStatus feasibility_restoration_handoff(NewtonSystem& sys, const std::vector<double>& scales,

@@ -1,4 +1,4 @@
-// Kernels of the batched interior-point driver (ipm_batch.cpp): B instances of one compiled model, each in its own
+// Kernels of the batched interior-point driver (batch_lockstep.cpp): B instances of one compiled model, each in its own
 // slice of batch-major buffers ([b * stride + i]), one 256-thread workgroup per instance.  An instance whose active
 // flag is 0 is skipped: nothing of its slice is read or written.  Every reduction runs in an order fixed by the
 // model's sizes alone (strided per-thread partials, then block_reduce: wave64 butterflies and a fixed combination of
@@ -20,11 +20,6 @@
 namespace slpx {
 
 constexpr int kBatchThreads = 256;
-
-// pointers of one batch's iterate-shaped buffers
-struct BatchIter {
-  double *x, *s, *y, *z;
-};
 
 // V[b][k], k < count: the tape's scaling of entry k with instance b's scales.  Entries the tape writes are multiplied
 // in place; static entries (never written by the tape) are set from their unscaled value, so the kernel may follow any

@@ -1,5 +1,5 @@
-// Launch wrappers of the batched interior-point kernels (ipm_batch_kernels.h), and of the batched SQP / Newton
-// kernels (eq_batch_kernels.h), which share the errors, scaling and input kernels of the former.
+// Launch wrappers of the batched drivers' kernels: BatchDevice, the state and the errors, scaling and input kernels
+// every driver shares; BatchIpmDevice (ipm_batch_kernels.h); BatchEqDevice (eq_batch_kernels.h).
 #include <algorithm>
 
 #include "eq_batch.hpp"
@@ -15,7 +15,9 @@ int chunks(int work) { return (work + kBatchThreads - 1) / kBatchThreads; }
 size_t at_least_1(size_t k) { return k ? k : 1; }
 }  // namespace
 
-BatchIpmDevice::BatchIpmDevice(NewtonSystem& sys_) : sys(sys_) {
+// ---- BatchDevice (batch_lockstep.hpp) ----
+
+BatchDevice::BatchDevice(NewtonSystem& sys_) : sys(sys_) {
   const NlpStructure& s = sys.structure();
   B = sys.batch();
   n = s.n;
@@ -24,137 +26,151 @@ BatchIpmDevice::BatchIpmDevice(NewtonSystem& sys_) : sys(sys_) {
   dim = n + m_e;
   ns = s.n_scales();
   nV = s.nV;
-  mu.assign(B, 0.0);
-  tau.assign(B, 0.0);
   alpha.assign(B, 0.0);
-  alpha_z.assign(B, 0.0);
   alpha_soc.assign(B, 0.0);
   mode.assign(B, 0);
-  s_from_ci.assign(B, 0);
   first.assign(B, 0);
   active.assign(B, 0);
   m_scale_idx.upload(s.V_scale_idx);
   m_is_static.upload(s.V_is_static);
   m_static_raw.upload(s.V_static_raw);
   m_scales.alloc(static_cast<size_t>(B) * ns);
-  for (auto* b : {&m_active, &m_s_from_ci, &m_first}) b->alloc(B);
+  for (auto* b : {&m_active, &m_first}) b->alloc(B);
   m_mode.alloc(B);
-  for (auto* b : {&m_mu, &m_tau, &m_alpha, &m_alpha_z, &m_alpha_soc}) b->alloc(B);
+  for (auto* b : {&m_alpha, &m_alpha_soc}) b->alloc(B);
   m_out.alloc(static_cast<size_t>(B) * kBatchErrN);
-  const size_t Bn = at_least_1(static_cast<size_t>(B) * n), Be = at_least_1(static_cast<size_t>(B) * m_e),
-               Bi = at_least_1(static_cast<size_t>(B) * m_i);
+  const size_t Bn = at_least_1(static_cast<size_t>(B) * n), Be = at_least_1(static_cast<size_t>(B) * m_e);
   for (auto* b : {&m_x, &m_tx, &m_sx}) b->alloc(Bn);
   for (auto* b : {&m_y, &m_ty, &m_sy, &m_tce, &m_sce}) b->alloc(Be);
-  for (auto* b : {&m_s, &m_z, &m_ts, &m_tz, &m_ss, &m_sz, &m_ps, &m_pz, &m_tci, &m_scims, &m_t}) b->alloc(Bi);
-  m_p.alloc(static_cast<size_t>(B) * dim);
   m_Vcur.alloc(static_cast<size_t>(B) * nV);
 }
 
-void BatchIpmDevice::upload() {
-  hipStream_t st = sys.device().stream();
-  auto put = [&](auto& buf, const auto& v) {
-    SLPX_HIP_CHECK(hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, st));
-  };
-  put(m_active, active);
-  put(m_mu, mu);
-  put(m_tau, tau);
-  put(m_alpha, alpha);
-  put(m_alpha_z, alpha_z);
-  put(m_alpha_soc, alpha_soc);
-  put(m_mode, mode);
-  put(m_s_from_ci, s_from_ci);
-  put(m_first, first);
+void BatchDevice::upload() {
+  put_async(m_active, active);
+  put_async(m_alpha, alpha);
+  put_async(m_alpha_soc, alpha_soc);
+  put_async(m_mode, mode);
+  put_async(m_first, first);
   // (pageable sources: the host may change its vectors once the copies are through)
-  SLPX_HIP_CHECK(hipStreamSynchronize(st));
+  SLPX_HIP_CHECK(hipStreamSynchronize(sys.device().stream()));
 }
 
-void BatchIpmDevice::set_scales(const std::vector<double>& scales) {
-  if (scales.size() != m_scales.n) throw std::runtime_error("BatchIpmDevice::set_scales: wrong length");
+void BatchDevice::set_scales(const std::vector<double>& scales) {
+  if (scales.size() != m_scales.n) throw std::runtime_error("BatchDevice::set_scales: wrong length");
   SLPX_HIP_CHECK(hipMemcpy(m_scales.p, scales.data(), scales.size() * sizeof(double), hipMemcpyHostToDevice));
 }
 
-void BatchIpmDevice::set_iterate(const std::vector<double>& x, const std::vector<double>& s, const std::vector<double>& y,
-                                 const std::vector<double>& z) {
-  auto put = [](DevBuf<double>& d, const std::vector<double>& h) {
-    if (!h.empty()) SLPX_HIP_CHECK(hipMemcpy(d.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+void BatchDevice::set_iterate(const std::vector<double>& x, const std::vector<double>& s, const std::vector<double>& y,
+                              const std::vector<double>& z) {
+  const size_t Bs = B;
+  if (x.size() != Bs * n || s.size() != Bs * m_i || y.size() != Bs * m_e || z.size() != Bs * m_i)
+    throw std::runtime_error("BatchDevice::set_iterate: wrong lengths");
+  auto put = [](double* d, const std::vector<double>& h) {
+    if (!h.empty()) SLPX_HIP_CHECK(hipMemcpy(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
   };
-  put(m_x, x);
-  put(m_s, s);
-  put(m_y, y);
-  put(m_z, z);
+  put(m_cur.x, x);
+  put(m_cur.s, s);
+  put(m_cur.y, y);
+  put(m_cur.z, z);
 }
 
-void BatchIpmDevice::get_iterate(std::vector<double>& x, std::vector<double>& s, std::vector<double>& y,
-                                 std::vector<double>& z) {
+void BatchDevice::get_iterate(std::vector<double>& x, std::vector<double>& s, std::vector<double>& y, std::vector<double>& z) {
   DeviceNlp& dev = sys.device();
   x.resize(static_cast<size_t>(B) * n);
   s.resize(static_cast<size_t>(B) * m_i);
   y.resize(static_cast<size_t>(B) * m_e);
   z.resize(static_cast<size_t>(B) * m_i);
-  if (!x.empty()) dev.download(m_x.p, x.data(), x.size());
-  if (!s.empty()) dev.download(m_s.p, s.data(), s.size());
-  if (!y.empty()) dev.download(m_y.p, y.data(), y.size());
-  if (!z.empty()) dev.download(m_z.p, z.data(), z.size());
+  if (!x.empty()) dev.download(m_cur.x, x.data(), x.size());
+  if (!s.empty()) dev.download(m_cur.s, s.data(), s.size());
+  if (!y.empty()) dev.download(m_cur.y, y.data(), y.size());
+  if (!z.empty()) dev.download(m_cur.z, z.data(), z.size());
 }
 
-void BatchIpmDevice::get_instance(int b, std::vector<double>& x, std::vector<double>& s, std::vector<double>& y,
-                                  std::vector<double>& z, std::vector<double>& V) {
+void BatchDevice::get_instance(int b, std::vector<double>& x, std::vector<double>& s, std::vector<double>& y,
+                               std::vector<double>& z, std::vector<double>& V) {
+  if (b < 0 || b >= B) throw std::runtime_error("BatchDevice::get_instance: no such instance");
   DeviceNlp& dev = sys.device();
   x.resize(n);
   s.resize(m_i);
   y.resize(m_e);
   z.resize(m_i);
   V.resize(nV);
-  if (n) dev.download(m_x.p + static_cast<size_t>(b) * n, x.data(), n);
-  if (m_i) dev.download(m_s.p + static_cast<size_t>(b) * m_i, s.data(), m_i);
-  if (m_e) dev.download(m_y.p + static_cast<size_t>(b) * m_e, y.data(), m_e);
-  if (m_i) dev.download(m_z.p + static_cast<size_t>(b) * m_i, z.data(), m_i);
+  if (n) dev.download(m_cur.x + static_cast<size_t>(b) * n, x.data(), n);
+  if (m_i) dev.download(m_cur.s + static_cast<size_t>(b) * m_i, s.data(), m_i);
+  if (m_e) dev.download(m_cur.y + static_cast<size_t>(b) * m_e, y.data(), m_e);
+  if (m_i) dev.download(m_cur.z + static_cast<size_t>(b) * m_i, z.data(), m_i);
   dev.download(m_Vcur.p + static_cast<size_t>(b) * nV, V.data(), nV);
 }
 
-void BatchIpmDevice::put_instance(int b, const std::vector<double>& x, const std::vector<double>& s,
-                                  const std::vector<double>& y, const std::vector<double>& z) {
+void BatchDevice::put_instance(int b, const std::vector<double>& x, const std::vector<double>& s, const std::vector<double>& y,
+                               const std::vector<double>& z) {
+  if (b < 0 || b >= B || x.size() != static_cast<size_t>(n) || s.size() != static_cast<size_t>(m_i) ||
+      y.size() != static_cast<size_t>(m_e) || z.size() != static_cast<size_t>(m_i))
+    throw std::runtime_error("BatchDevice::put_instance: wrong instance or lengths");
   auto put = [](double* d, const std::vector<double>& h) {
     if (!h.empty()) SLPX_HIP_CHECK(hipMemcpy(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
   };
-  put(m_x.p + static_cast<size_t>(b) * n, x);
-  put(m_s.p + static_cast<size_t>(b) * m_i, s);
-  put(m_y.p + static_cast<size_t>(b) * m_e, y);
-  put(m_z.p + static_cast<size_t>(b) * m_i, z);
+  put(m_cur.x + static_cast<size_t>(b) * n, x);
+  put(m_cur.s + static_cast<size_t>(b) * m_i, s);
+  put(m_cur.y + static_cast<size_t>(b) * m_e, y);
+  put(m_cur.z + static_cast<size_t>(b) * m_i, z);
 }
 
-void BatchIpmDevice::scale_V(int count) {
+void BatchDevice::scale_V(int count) {
   DeviceNlp& dev = sys.device();
   hipLaunchKernelGGL(batch_scale_V_kernel, dim3(chunks(count), B), dim3(kBatchThreads), 0, dev.stream(), dev.d_V(), nV,
                      count, m_scale_idx.p, m_is_static.p, m_static_raw.p, m_scales.p, ns, m_active.p);
   SLPX_HIP_CHECK(hipGetLastError());
 }
 
-void BatchIpmDevice::download_out(size_t per_instance, std::vector<double>& out) {
+void BatchDevice::download_out(size_t per_instance, std::vector<double>& out) {
   out.resize(static_cast<size_t>(B) * per_instance);
   sys.device().download(m_out.p, out.data(), out.size());
 }
 
-void BatchIpmDevice::errors(const double* V, bool trial, std::vector<double>& err) {
+void BatchDevice::errors(const double* V, bool trial, std::vector<double>& err) {
   DeviceNlp& dev = sys.device();
-  const BatchIter it = trial ? BatchIter{m_tx.p, m_ts.p, m_ty.p, m_tz.p} : BatchIter{m_x.p, m_s.p, m_y.p, m_z.p};
-  hipLaunchKernelGGL(batch_errors_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(), V, nV, nV, it, m_mu.p,
-                     m_scales.p, ns, m_active.p, m_out.p);
+  hipLaunchKernelGGL(batch_errors_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(), V, nV, nV,
+                     trial ? m_trial : m_cur, m_mu_of_errors, m_scales.p, ns, m_active.p, m_out.p);
   SLPX_HIP_CHECK(hipGetLastError());
   download_out(kBatchErrN, err);
 }
 
-void BatchIpmDevice::refresh(std::vector<double>& err) {
+void BatchDevice::refresh(std::vector<double>& err) {
   DeviceNlp& dev = sys.device();
   hipStream_t st = dev.stream();
   hipLaunchKernelGGL(batch_load_state_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), dev.d_x(),
-                     sys.structure().n_inputs(), BatchIter{m_x.p, m_s.p, m_y.p, m_z.p}, m_scales.p, ns, dev.d_s(), dev.d_y(),
-                     dev.d_z(), 1, m_active.p);
+                     sys.structure().n_inputs(), m_cur, m_scales.p, ns, dev.d_s(), dev.d_y(), dev.d_z(), 1, m_active.p);
   SLPX_HIP_CHECK(hipGetLastError());
   dev.sweep_full();
   scale_V(nV);
   SLPX_HIP_CHECK(hipMemcpyAsync(m_Vcur.p, dev.d_V(), m_Vcur.n * sizeof(double), hipMemcpyDeviceToDevice, st));
   errors(m_Vcur.p, false, err);
+}
+
+// ---- BatchIpmDevice (ipm_batch.hpp) ----
+
+BatchIpmDevice::BatchIpmDevice(NewtonSystem& sys_) : BatchDevice(sys_) {
+  mu.assign(B, 0.0);
+  tau.assign(B, 0.0);
+  alpha_z.assign(B, 0.0);
+  s_from_ci.assign(B, 0);
+  m_s_from_ci.alloc(B);
+  for (auto* b : {&m_mu, &m_tau, &m_alpha_z}) b->alloc(B);
+  const size_t Bi = at_least_1(static_cast<size_t>(B) * m_i);
+  for (auto* b : {&m_s, &m_z, &m_ts, &m_tz, &m_ss, &m_sz, &m_ps, &m_pz, &m_tci, &m_scims, &m_t}) b->alloc(Bi);
+  m_p.alloc(static_cast<size_t>(B) * dim);
+  m_cur = BatchIter{m_x.p, m_s.p, m_y.p, m_z.p};
+  m_trial = BatchIter{m_tx.p, m_ts.p, m_ty.p, m_tz.p};
+  m_mu_of_errors = m_mu.p;
+}
+
+void BatchIpmDevice::upload() {
+  put_async(m_mu, mu);
+  put_async(m_tau, tau);
+  put_async(m_alpha_z, alpha_z);
+  put_async(m_s_from_ci, s_from_ci);
+  BatchDevice::upload();
 }
 
 void BatchIpmDevice::newton_direction(std::vector<double>& dir) {
@@ -171,12 +187,11 @@ void BatchIpmDevice::newton_direction(std::vector<double>& dir) {
   download_out(3, dir);
 }
 
-void BatchIpmDevice::trial_values(std::vector<double>& met) {
+void BatchIpmDevice::launch_trial(int with_duals) {
   DeviceNlp& dev = sys.device();
-  hipStream_t st = dev.stream();
   BatchTrialArgs A{};
-  A.cur = BatchIter{m_x.p, m_s.p, m_y.p, m_z.p};
-  A.trial = BatchIter{m_tx.p, m_ts.p, m_ty.p, m_tz.p};
+  A.cur = m_cur;
+  A.trial = m_trial;
   A.soc = BatchIter{m_sx.p, m_ss.p, m_sy.p, m_sz.p};
   A.p = m_p.p;
   A.ps = m_ps.p;
@@ -189,13 +204,18 @@ void BatchIpmDevice::trial_values(std::vector<double>& met) {
   A.in_stride = sys.structure().n_inputs();
   A.S = m_scales.p;
   A.ns = ns;
-  A.with_duals = 0;
-  hipLaunchKernelGGL(batch_trial_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), A, m_active.p);
+  A.with_duals = with_duals;
+  hipLaunchKernelGGL(batch_trial_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(), A, m_active.p);
   SLPX_HIP_CHECK(hipGetLastError());
+}
+
+void BatchIpmDevice::trial_values(std::vector<double>& met) {
+  DeviceNlp& dev = sys.device();
+  launch_trial(0);
   dev.sweep_values();
   scale_V(sys.structure().off_g);
-  hipLaunchKernelGGL(batch_trial_metrics_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), dev.d_V(), nV, m_s_from_ci.p,
-                     m_mode.p, m_ts.p, m_tce.p, m_tci.p, m_active.p, m_out.p);
+  hipLaunchKernelGGL(batch_trial_metrics_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(), dev.d_V(), nV,
+                     m_s_from_ci.p, m_mode.p, m_ts.p, m_tce.p, m_tci.p, m_active.p, m_out.p);
   SLPX_HIP_CHECK(hipGetLastError());
   download_out(4, met);
 }
@@ -206,7 +226,7 @@ void BatchIpmDevice::soc_step(std::vector<double>& sd) {
   BatchSocArgs A{};
   A.V = m_Vcur.p;
   A.v_stride = nV;
-  A.cur = BatchIter{m_x.p, m_s.p, m_y.p, m_z.p};
+  A.cur = m_cur;
   A.ts = m_ts.p;
   A.tce = m_tce.p;
   A.tci = m_tci.p;
@@ -221,7 +241,7 @@ void BatchIpmDevice::soc_step(std::vector<double>& sd) {
   SLPX_HIP_CHECK(hipGetLastError());
   dev.solve();  // (every instance's factor; the slices of the others are not read)
   hipLaunchKernelGGL(batch_soc_direction_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), m_Vcur.p, nV, dev.d_p(),
-                     BatchIter{m_x.p, m_s.p, m_y.p, m_z.p}, m_scims.p, m_mu.p, m_tau.p, BatchIter{m_sx.p, m_ss.p, m_sy.p, m_sz.p},
+                     m_cur, m_scims.p, m_mu.p, m_tau.p, BatchIter{m_sx.p, m_ss.p, m_sy.p, m_sz.p},
                      m_active.p, m_out.p);
   SLPX_HIP_CHECK(hipGetLastError());
   download_out(2, sd);
@@ -233,24 +253,7 @@ void BatchIpmDevice::kkt_fallback(std::vector<double>& err_cur, std::vector<doub
   std::fill(s_from_ci.begin(), s_from_ci.end(), uint8_t{0});
   upload();
   errors(m_Vcur.p, false, err_cur);
-  BatchTrialArgs A{};
-  A.cur = BatchIter{m_x.p, m_s.p, m_y.p, m_z.p};
-  A.trial = BatchIter{m_tx.p, m_ts.p, m_ty.p, m_tz.p};
-  A.soc = BatchIter{m_sx.p, m_ss.p, m_sy.p, m_sz.p};
-  A.p = m_p.p;
-  A.ps = m_ps.p;
-  A.pz = m_pz.p;
-  A.mode = m_mode.p;
-  A.s_from_ci = m_s_from_ci.p;
-  A.alpha = m_alpha.p;
-  A.alpha_z = m_alpha_z.p;
-  A.in = dev.d_x();
-  A.in_stride = sys.structure().n_inputs();
-  A.S = m_scales.p;
-  A.ns = ns;
-  A.with_duals = 1;
-  hipLaunchKernelGGL(batch_trial_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(), A, m_active.p);
-  SLPX_HIP_CHECK(hipGetLastError());
+  launch_trial(1);
   dev.sweep_full();
   scale_V(nV);
   errors(dev.d_V(), true, err_trial);
@@ -259,128 +262,21 @@ void BatchIpmDevice::kkt_fallback(std::vector<double>& err_cur, std::vector<doub
 void BatchIpmDevice::commit() {
   DeviceNlp& dev = sys.device();
   hipLaunchKernelGGL(batch_commit_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(),
-                     BatchIter{m_tx.p, m_ts.p, m_ty.p, m_tz.p}, BatchIter{m_x.p, m_s.p, m_y.p, m_z.p}, m_mu.p, m_active.p);
+                     m_trial, m_cur, m_mu.p, m_active.p);
   SLPX_HIP_CHECK(hipGetLastError());
 }
 
 // ---- BatchEqDevice (eq_batch.hpp) ----
 
-BatchEqDevice::BatchEqDevice(NewtonSystem& sys_) : sys(sys_) {
-  const NlpStructure& s = sys.structure();
-  if (s.m_i != 0) throw std::runtime_error("BatchEqDevice: a model without inequality constraints only");
-  B = sys.batch();
-  n = s.n;
-  m_e = s.m_e;
-  dim = n + m_e;
-  ns = s.n_scales();
-  nV = s.nV;
-  alpha.assign(B, 0.0);
-  alpha_soc.assign(B, 0.0);
-  mode.assign(B, 0);
-  first.assign(B, 0);
-  active.assign(B, 0);
-  m_scale_idx.upload(s.V_scale_idx);
-  m_is_static.upload(s.V_is_static);
-  m_static_raw.upload(s.V_static_raw);
-  m_scales.alloc(static_cast<size_t>(B) * ns);
-  m_active.alloc(B);
-  m_first.alloc(B);
-  m_mode.alloc(B);
-  m_alpha.alloc(B);
-  m_alpha_soc.alloc(B);
+BatchEqDevice::BatchEqDevice(NewtonSystem& sys_) : BatchDevice(sys_) {
+  if (m_i != 0) throw std::runtime_error("BatchEqDevice: a model without inequality constraints only");
+  m_px.alloc(at_least_1(static_cast<size_t>(B) * n));
+  m_py.alloc(at_least_1(static_cast<size_t>(B) * m_e));
   m_zero.upload(std::vector<double>(B, 0.0));  // (the barrier parameter batch_errors_kernel reads: none here)
   m_none.alloc(1);                             // (s, z of an iterate without inequality rows: never read)
-  m_out.alloc(static_cast<size_t>(B) * kBatchErrN);
-  const size_t Bn = at_least_1(static_cast<size_t>(B) * n), Be = at_least_1(static_cast<size_t>(B) * m_e);
-  for (auto* b : {&m_x, &m_tx, &m_px, &m_sx}) b->alloc(Bn);
-  for (auto* b : {&m_y, &m_ty, &m_py, &m_sy, &m_tce, &m_sce}) b->alloc(Be);
-  m_Vcur.alloc(static_cast<size_t>(B) * nV);
-}
-
-void BatchEqDevice::upload() {
-  hipStream_t st = sys.device().stream();
-  auto put = [&](auto& buf, const auto& v) {
-    SLPX_HIP_CHECK(hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, st));
-  };
-  put(m_active, active);
-  put(m_alpha, alpha);
-  put(m_alpha_soc, alpha_soc);
-  put(m_mode, mode);
-  put(m_first, first);
-  // (pageable sources: the host may change its vectors once the copies are through)
-  SLPX_HIP_CHECK(hipStreamSynchronize(st));
-}
-
-void BatchEqDevice::set_scales(const std::vector<double>& scales) {
-  if (scales.size() != m_scales.n) throw std::runtime_error("BatchEqDevice::set_scales: wrong length");
-  SLPX_HIP_CHECK(hipMemcpy(m_scales.p, scales.data(), scales.size() * sizeof(double), hipMemcpyHostToDevice));
-}
-
-void BatchEqDevice::set_iterate(const std::vector<double>& x, const std::vector<double>& y) {
-  if (x.size() != static_cast<size_t>(B) * n || y.size() != static_cast<size_t>(B) * m_e)
-    throw std::runtime_error("BatchEqDevice::set_iterate: wrong lengths");
-  if (!x.empty()) SLPX_HIP_CHECK(hipMemcpy(m_x.p, x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice));
-  if (!y.empty()) SLPX_HIP_CHECK(hipMemcpy(m_y.p, y.data(), y.size() * sizeof(double), hipMemcpyHostToDevice));
-}
-
-void BatchEqDevice::get_iterate(std::vector<double>& x, std::vector<double>& y) {
-  DeviceNlp& dev = sys.device();
-  x.resize(static_cast<size_t>(B) * n);
-  y.resize(static_cast<size_t>(B) * m_e);
-  if (!x.empty()) dev.download(m_x.p, x.data(), x.size());
-  if (!y.empty()) dev.download(m_y.p, y.data(), y.size());
-}
-
-void BatchEqDevice::get_instance(int b, std::vector<double>& x, std::vector<double>& y, std::vector<double>& V) {
-  if (b < 0 || b >= B) throw std::runtime_error("BatchEqDevice::get_instance: no such instance");
-  DeviceNlp& dev = sys.device();
-  x.resize(n);
-  y.resize(m_e);
-  V.resize(nV);
-  if (n) dev.download(m_x.p + static_cast<size_t>(b) * n, x.data(), n);
-  if (m_e) dev.download(m_y.p + static_cast<size_t>(b) * m_e, y.data(), m_e);
-  dev.download(m_Vcur.p + static_cast<size_t>(b) * nV, V.data(), nV);
-}
-
-void BatchEqDevice::put_instance(int b, const std::vector<double>& x, const std::vector<double>& y) {
-  if (b < 0 || b >= B || x.size() != static_cast<size_t>(n) || y.size() != static_cast<size_t>(m_e))
-    throw std::runtime_error("BatchEqDevice::put_instance: wrong instance or lengths");
-  if (n) SLPX_HIP_CHECK(hipMemcpy(m_x.p + static_cast<size_t>(b) * n, x.data(), n * sizeof(double), hipMemcpyHostToDevice));
-  if (m_e) SLPX_HIP_CHECK(hipMemcpy(m_y.p + static_cast<size_t>(b) * m_e, y.data(), m_e * sizeof(double), hipMemcpyHostToDevice));
-}
-
-void BatchEqDevice::scale_V(int count) {
-  DeviceNlp& dev = sys.device();
-  hipLaunchKernelGGL(batch_scale_V_kernel, dim3(chunks(count), B), dim3(kBatchThreads), 0, dev.stream(), dev.d_V(), nV,
-                     count, m_scale_idx.p, m_is_static.p, m_static_raw.p, m_scales.p, ns, m_active.p);
-  SLPX_HIP_CHECK(hipGetLastError());
-}
-
-void BatchEqDevice::download_out(size_t per_instance, std::vector<double>& out) {
-  out.resize(static_cast<size_t>(B) * per_instance);
-  sys.device().download(m_out.p, out.data(), out.size());
-}
-
-void BatchEqDevice::errors(const double* V, bool trial, std::vector<double>& err) {
-  DeviceNlp& dev = sys.device();
-  const BatchIter it = trial ? BatchIter{m_tx.p, m_none.p, m_ty.p, m_none.p} : BatchIter{m_x.p, m_none.p, m_y.p, m_none.p};
-  hipLaunchKernelGGL(batch_errors_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(), V, nV, nV, it, m_zero.p,
-                     m_scales.p, ns, m_active.p, m_out.p);
-  SLPX_HIP_CHECK(hipGetLastError());
-  download_out(kBatchErrN, err);
-}
-
-void BatchEqDevice::refresh(std::vector<double>& err) {
-  DeviceNlp& dev = sys.device();
-  hipStream_t st = dev.stream();
-  hipLaunchKernelGGL(batch_load_state_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), dev.d_x(),
-                     sys.structure().n_inputs(), BatchIter{m_x.p, m_none.p, m_y.p, m_none.p}, m_scales.p, ns, dev.d_s(),
-                     dev.d_y(), dev.d_z(), 1, m_active.p);
-  SLPX_HIP_CHECK(hipGetLastError());
-  dev.sweep_full();
-  scale_V(nV);
-  SLPX_HIP_CHECK(hipMemcpyAsync(m_Vcur.p, dev.d_V(), m_Vcur.n * sizeof(double), hipMemcpyDeviceToDevice, st));
-  errors(m_Vcur.p, false, err);
+  m_cur = BatchIter{m_x.p, m_none.p, m_y.p, m_none.p};
+  m_trial = BatchIter{m_tx.p, m_none.p, m_ty.p, m_none.p};
+  m_mu_of_errors = m_zero.p;
 }
 
 void BatchEqDevice::direction(std::vector<double>& dphi) {

@@ -1,5 +1,5 @@
 // Host-side pieces of the interior-point iteration shared by the single-problem driver (ipm.cpp) and
-// the batched lockstep driver (ipm_batch.cpp): norms over downloaded vectors, the KKT error measures, the
+// the batched lockstep loop (batch_lockstep.cpp): norms over downloaded vectors, the KKT error measures, the
 // filter (its rules: ipm_decide.h), the fraction-to-the-boundary rule.  (The line search and the scalar decisions
 // around it: ipm_line_search.hpp.)
 #pragma once

@@ -5,7 +5,7 @@
 //
 // The machine says which device work it waits for (`want`, at `t_alpha`, `t_alpha_z`, along the Newton direction or
 // the correction's) and is resumed with a handful of scalars.  A sequential driver (ipm.cpp: host, device-resident,
-// restoration, SQP) runs it with `while (ls.want != Done) switch (ls.want)`; the batched driver (ipm_batch.cpp)
+// restoration, SQP) runs it with `while (ls.want != Done) switch (ls.want)`; the batched loop (batch_lockstep.cpp)
 // keeps one per instance and answers all instances that want the same work with one masked launch.  What a driver
 // keeps for itself is plumbing: where the four numbers of a trial point come from, and what to commit.
 #pragma once
@@ -19,6 +19,7 @@ namespace slpx::ipm_host {
 
 constexpr double kAlphaReduction = 0.5;  // alpha_reduction_factor
 constexpr double kAlphaMin = 1e-7;       // the step floor of the filter line search
+constexpr double kNewtonAlphaMin = 1e-20;  // the step floor of Newton's search (newton.hpp:138-139)
 constexpr double kTauMin = 0.99;         // fraction to the boundary
 constexpr double kKappaSoc = 0.99;       // a correction round must take 1 % off the violation to be followed by another
 constexpr int kMaxCorrections = 5;
@@ -37,6 +38,7 @@ class LineSearch {
   // restoration wanted.  Set from the start where alpha_max is below the floor (:489-491): the search still runs,
   // as the reference's does, and whatever it accepts is not committed.
   bool call_feasibility_restoration = false;
+  static constexpr bool failed = false;  // (a search that accepts nothing asks for restoration; NewtonSearch can fail)
   double alpha_max = 1.0, alpha = 1.0, alpha_z = 1.0;
 
   // the request: Eval / SocEval = f, violation, sum ln s at (t_alpha, t_alpha_z) along the Newton direction or
@@ -150,6 +152,61 @@ class LineSearch {
       return;
     }
     request_eval();
+  }
+};
+
+// Newton's own search (newton.hpp:201-243) as the same kind of machine: no corrections, no restoration to fall back
+// on, a floor of 1e-20, entries without a constraint violation.  Eval asks for the cost at `t_alpha` along the
+// Newton direction and whether it is finite; past the floor KktEval asks for ||g||_1 here and at the full step
+// `alpha_max`, and for the cost there.  It ends (Done) accepted — `t_alpha` is the step to commit, `f` the cost the
+// filter compares the next search's trial points with — or `failed`: LINE_SEARCH_FAILED.
+class NewtonSearch {
+ public:
+  using Want = LineSearch::Want;
+  static constexpr double alpha_max = 1.0;
+  static constexpr bool call_feasibility_restoration = false;
+
+  Want want = Want::Done;
+  bool failed = false;
+  double f = 0.0;
+  double alpha = alpha_max;  // halved with every rejection; stays the halved one where the fallback accepts
+  double t_alpha = alpha_max;
+
+  void start(Filter& filter, double D_phi) {  // (`f` is the caller's to set before the first search)
+    m_filter = &filter;
+    m_D_phi = D_phi;
+    alpha = t_alpha = alpha_max;
+    failed = false;
+    want = Want::Eval;
+  }
+
+  void on_trial(double trial_f, bool finite) {
+    if (finite && m_filter->try_add(FilterEntry{f, 0.0}, FilterEntry{trial_f, 0.0}, m_D_phi, alpha)) {
+      f = trial_f;
+      want = Want::Done;
+      return;
+    }
+    alpha *= kAlphaReduction;
+    t_alpha = alpha;
+    if (alpha < kNewtonAlphaMin) {
+      if (finite) want = Want::KktEval;  // :225-236: the full step's ||g||_1 against the current one
+      else fail();                       // (a non-finite cost has no fallback, :208-214)
+    }
+  }
+
+  void on_kkt_errors(double current_kkt_error, double next_kkt_error, double f_at_full_step) {
+    if (!(next_kkt_error <= kFallbackDecrease * current_kkt_error)) return fail();
+    t_alpha = alpha_max;  // (the full step is what is committed)
+    f = f_at_full_step;
+    want = Want::Done;
+  }
+
+ private:
+  Filter* m_filter = nullptr;
+  double m_D_phi = 0.0;
+  void fail() {
+    failed = true;
+    want = Want::Done;
   }
 };
 

@@ -5,18 +5,13 @@
 // slpx_system_create(problem, B, 0) makes, tape at unit scales, as Problem::batch_system does — and read back every
 // per-instance buffer.  Nothing of the kernels is compiled here.  tests/test_solve_batch_kernels_gpu.py compares what
 // comes back with numpy.
-#include <cstdint>
-#include <cstring>
-#include <stdexcept>
-#include <string>
-#include <vector>
-
-#include "../../sleipnir_amd/csrc/capi_internal.hpp"
 #include "../../sleipnir_amd/csrc/ipm_batch.hpp"
+#include "probe_common.hpp"
 
 namespace slpx {
 
 struct BatchIpmProbe {
+  static constexpr const char* kName = "batchcheck";
   explicit BatchIpmProbe(NewtonSystem& s) : sys(s), bd(s) {}
   NewtonSystem& sys;
   BatchIpmDevice bd;
@@ -65,42 +60,13 @@ struct BatchIpmProbe {
 
 using slpx::BatchIpmProbe;
 
-namespace {
-std::string g_error;
-template <class F>
-int guard(F&& f) {
-  try {
-    f();
-    return 0;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-    return -1;
-  } catch (...) {
-    g_error = "unknown error";
-    return -1;
-  }
-}
-template <class T>
-std::vector<T> vec(const T* p, size_t n) {
-  return p ? std::vector<T>(p, p + n) : std::vector<T>();
-}
-void check(BatchIpmProbe* h) {
-  if (!h) throw std::runtime_error("batchcheck: no probe");
-}
-}  // namespace
+using namespace probe;
 
 extern "C" {
 
 const char* bc_last_error() { return g_error.c_str(); }
 
-BatchIpmProbe* bc_create(slpx_system* s) {
-  BatchIpmProbe* h = nullptr;
-  guard([&] {
-    if (!s) throw std::runtime_error("batchcheck: no system");
-    h = new BatchIpmProbe(s->get());
-  });
-  return h;
-}
+BatchIpmProbe* bc_create(slpx_system* s) { return create<BatchIpmProbe>(s); }
 
 void bc_destroy(BatchIpmProbe* h) { delete h; }
 
@@ -166,7 +132,7 @@ int bc_assemble(BatchIpmProbe* h) {
     dev.upload_mu(h->bd.mu.data());
     dev.assemble();
     dev.build_rhs();
-    SLPX_HIP_CHECK(hipStreamSynchronize(dev.stream()));
+    sync(h);
   });
 }
 
@@ -201,63 +167,25 @@ int bc_compute(BatchIpmProbe* h, int spec, const uint8_t* mask, int32_t* info, i
     const auto r = mask ? h->sys.compute(spec != 0, vec(mask, h->bd.B)) : h->sys.compute(spec != 0);
     for (size_t b = 0; b < r.size(); ++b) info[b] = static_cast<int32_t>(r[b]);
     *factorizations = h->sys.last_factorizations();
-    SLPX_HIP_CHECK(hipStreamSynchronize(h->sys.device().stream()));
+    sync(h);
   });
 }
 
-#define BC_OUT(name, call)                                     \
-  int bc_##name(BatchIpmProbe* h, double* out) {               \
-    return guard([&] {                                         \
-      check(h);                                                \
-      std::vector<double> v;                                   \
-      h->bd.call(v);                                           \
-      std::memcpy(out, v.data(), v.size() * sizeof(double));   \
-    });                                                        \
-  }
-BC_OUT(refresh, refresh)
-BC_OUT(newton_direction, newton_direction)
-BC_OUT(trial_values, trial_values)
-BC_OUT(soc_step, soc_step)
-#undef BC_OUT
-
-int bc_kkt_fallback(BatchIpmProbe* h, double* err_cur, double* err_trial) {
-  return guard([&] {
-    check(h);
-    std::vector<double> c, t;
-    h->bd.kkt_fallback(c, t);
-    std::memcpy(err_cur, c.data(), c.size() * sizeof(double));
-    std::memcpy(err_trial, t.data(), t.size() * sizeof(double));
-  });
+int bc_refresh(BatchIpmProbe* h, double* out) {
+  return scalars_out(h, out, [](auto& bd, auto& v) { bd.refresh(v); });
 }
-
-int bc_commit(BatchIpmProbe* h) {
-  return guard([&] {
-    check(h);
-    h->bd.commit();
-    SLPX_HIP_CHECK(hipStreamSynchronize(h->sys.device().stream()));
-  });
+int bc_newton_direction(BatchIpmProbe* h, double* out) {
+  return scalars_out(h, out, [](auto& bd, auto& v) { bd.newton_direction(v); });
 }
-
-// length of buffer `which` (BatchIpmProbe::buffer); out != nullptr: its contents
-int64_t bc_get(BatchIpmProbe* h, int which, double* out) {
-  int64_t count = -1;
-  const int rc = guard([&] {
-    check(h);
-    const auto [p, n] = h->buffer(which);
-    SLPX_HIP_CHECK(hipStreamSynchronize(h->sys.device().stream()));
-    if (out && n) SLPX_HIP_CHECK(hipMemcpy(out, p, n * sizeof(double), hipMemcpyDeviceToHost));
-    count = static_cast<int64_t>(n);
-  });
-  return rc == 0 ? count : -1;
+int bc_trial_values(BatchIpmProbe* h, double* out) {
+  return scalars_out(h, out, [](auto& bd, auto& v) { bd.trial_values(v); });
 }
-
-int bc_put(BatchIpmProbe* h, int which, const double* in) {
-  return guard([&] {
-    check(h);
-    const auto [p, n] = h->buffer(which);
-    SLPX_HIP_CHECK(hipStreamSynchronize(h->sys.device().stream()));
-    if (n) SLPX_HIP_CHECK(hipMemcpy(p, in, n * sizeof(double), hipMemcpyHostToDevice));
-  });
+int bc_soc_step(BatchIpmProbe* h, double* out) {
+  return scalars_out(h, out, [](auto& bd, auto& v) { bd.soc_step(v); });
 }
+int bc_kkt_fallback(BatchIpmProbe* h, double* err_cur, double* err_trial) { return kkt_fallback(h, err_cur, err_trial); }
+int bc_commit(BatchIpmProbe* h) { return commit(h); }
+int64_t bc_get(BatchIpmProbe* h, int which, double* out) { return get(h, which, out); }
+int bc_put(BatchIpmProbe* h, int which, const double* in) { return put(h, which, in); }
 
 }  // extern "C"

@@ -16,9 +16,10 @@ import sleipnir_amd
 
 HERE = Path(__file__).resolve().parent
 LIB_PATH = HERE / "libslpx_batchcheck.so"
-SOURCES = [HERE / "batchcheck.cpp", HERE.parents[1] / "sleipnir_amd" / "csrc" / "ipm_batch.hpp"]
+_CSRC = HERE.parents[1] / "sleipnir_amd" / "csrc"
+SOURCES = [HERE / "batchcheck.cpp", HERE / "probe_common.hpp", _CSRC / "ipm_batch.hpp", _CSRC / "batch_lockstep.hpp"]
 
-# the per-instance errors of batch_errors_kernel (ipm_batch.hpp: BatchErr), in order
+# the per-instance errors of batch_errors_kernel (batch_lockstep.hpp: BatchErr), in order
 ERR_KEYS = ["F", "DUAL_INF", "DUAL_1", "Y1", "Z1", "SZ_MAX", "SZ_MIN", "COMP_1", "CE_INF", "CE_1", "CIS_INF", "CIS_1",
             "DUALU_INF", "YU1", "ZU1", "COMPU_INF", "CEU_INF", "CISU_INF",
             "LOGSUM", "V_BAD", "CI_NONPOS", "AETCE2", "CE2", "AITCM2", "CM2", "X_INF", "X_BAD", "S_INF", "S_BAD"]

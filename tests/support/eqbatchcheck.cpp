@@ -4,18 +4,13 @@
 // drive the REAL launch wrappers of libslpx.so on the NewtonSystem behind an slpx_system handle (the batch system
 // slpx_system_create(problem, B, 0) makes, tape at unit scales) and read back every per-instance buffer.  Nothing of
 // the kernels is compiled here.  tests/test_eq_batch_kernels_gpu.py compares what comes back with numpy.
-#include <cstdint>
-#include <cstring>
-#include <stdexcept>
-#include <string>
-#include <vector>
-
-#include "../../sleipnir_amd/csrc/capi_internal.hpp"
 #include "../../sleipnir_amd/csrc/eq_batch.hpp"
+#include "probe_common.hpp"
 
 namespace slpx {
 
 struct BatchEqProbe {
+  static constexpr const char* kName = "eqbatchcheck";
   explicit BatchEqProbe(NewtonSystem& s) : sys(s), bd(s) {}
   NewtonSystem& sys;
   BatchEqDevice bd;
@@ -51,43 +46,13 @@ struct BatchEqProbe {
 
 using slpx::BatchEqProbe;
 
-namespace {
-std::string g_error;
-template <class F>
-int guard(F&& f) {
-  try {
-    f();
-    return 0;
-  } catch (const std::exception& e) {
-    g_error = e.what();
-    return -1;
-  } catch (...) {
-    g_error = "unknown error";
-    return -1;
-  }
-}
-template <class T>
-std::vector<T> vec(const T* p, size_t n) {
-  return p ? std::vector<T>(p, p + n) : std::vector<T>();
-}
-void check(BatchEqProbe* h) {
-  if (!h) throw std::runtime_error("eqbatchcheck: no probe");
-}
-void sync(BatchEqProbe* h) { SLPX_HIP_CHECK(hipStreamSynchronize(h->sys.device().stream())); }
-}  // namespace
+using namespace probe;
 
 extern "C" {
 
 const char* ebc_last_error() { return g_error.c_str(); }
 
-BatchEqProbe* ebc_create(slpx_system* s) {
-  BatchEqProbe* h = nullptr;
-  guard([&] {
-    if (!s) throw std::runtime_error("eqbatchcheck: no system");
-    h = new BatchEqProbe(s->get());
-  });
-  return h;
-}
+BatchEqProbe* ebc_create(slpx_system* s) { return create<BatchEqProbe>(s); }
 
 void ebc_destroy(BatchEqProbe* h) { delete h; }
 
@@ -149,19 +114,15 @@ int ebc_newton_step(BatchEqProbe* h, int32_t* info) {
   });
 }
 
-#define EBC_OUT(name)                                          \
-  int ebc_##name(BatchEqProbe* h, double* out) {               \
-    return guard([&] {                                         \
-      check(h);                                                \
-      std::vector<double> v;                                   \
-      h->bd.name(v);                                           \
-      std::memcpy(out, v.data(), v.size() * sizeof(double));   \
-    });                                                        \
-  }
-EBC_OUT(refresh)
-EBC_OUT(direction)
-EBC_OUT(trial_values)
-#undef EBC_OUT
+int ebc_refresh(BatchEqProbe* h, double* out) {
+  return scalars_out(h, out, [](auto& bd, auto& v) { bd.refresh(v); });
+}
+int ebc_direction(BatchEqProbe* h, double* out) {
+  return scalars_out(h, out, [](auto& bd, auto& v) { bd.direction(v); });
+}
+int ebc_trial_values(BatchEqProbe* h, double* out) {
+  return scalars_out(h, out, [](auto& bd, auto& v) { bd.trial_values(v); });
+}
 
 int ebc_soc_step(BatchEqProbe* h) {
   return guard([&] {
@@ -171,44 +132,9 @@ int ebc_soc_step(BatchEqProbe* h) {
   });
 }
 
-int ebc_kkt_fallback(BatchEqProbe* h, double* err_cur, double* err_trial) {
-  return guard([&] {
-    check(h);
-    std::vector<double> c, t;
-    h->bd.kkt_fallback(c, t);
-    std::memcpy(err_cur, c.data(), c.size() * sizeof(double));
-    std::memcpy(err_trial, t.data(), t.size() * sizeof(double));
-  });
-}
-
-int ebc_commit(BatchEqProbe* h) {
-  return guard([&] {
-    check(h);
-    h->bd.commit();
-    sync(h);
-  });
-}
-
-// length of buffer `which` (BatchEqProbe::buffer); out != nullptr: its contents
-int64_t ebc_get(BatchEqProbe* h, int which, double* out) {
-  int64_t count = -1;
-  const int rc = guard([&] {
-    check(h);
-    const auto [p, n] = h->buffer(which);
-    sync(h);
-    if (out && n) SLPX_HIP_CHECK(hipMemcpy(out, p, n * sizeof(double), hipMemcpyDeviceToHost));
-    count = static_cast<int64_t>(n);
-  });
-  return rc == 0 ? count : -1;
-}
-
-int ebc_put(BatchEqProbe* h, int which, const double* in) {
-  return guard([&] {
-    check(h);
-    const auto [p, n] = h->buffer(which);
-    sync(h);
-    if (n) SLPX_HIP_CHECK(hipMemcpy(p, in, n * sizeof(double), hipMemcpyHostToDevice));
-  });
-}
+int ebc_kkt_fallback(BatchEqProbe* h, double* err_cur, double* err_trial) { return kkt_fallback(h, err_cur, err_trial); }
+int ebc_commit(BatchEqProbe* h) { return commit(h); }
+int64_t ebc_get(BatchEqProbe* h, int which, double* out) { return get(h, which, out); }
+int ebc_put(BatchEqProbe* h, int which, const double* in) { return put(h, which, in); }
 
 }  // extern "C"

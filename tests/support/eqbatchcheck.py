@@ -17,8 +17,8 @@ from tests.support.batchcheck import ERR, ERR_KEYS  # noqa: F401  (the layout of
 
 HERE = Path(__file__).resolve().parent
 LIB_PATH = HERE / "libslpx_eqbatchcheck.so"
-SOURCES = [HERE / "eqbatchcheck.cpp", HERE.parents[1] / "sleipnir_amd" / "csrc" / "eq_batch.hpp",
-           HERE.parents[1] / "sleipnir_amd" / "csrc" / "ipm_batch.hpp"]
+_CSRC = HERE.parents[1] / "sleipnir_amd" / "csrc"
+SOURCES = [HERE / "eqbatchcheck.cpp", HERE / "probe_common.hpp", _CSRC / "eq_batch.hpp", _CSRC / "batch_lockstep.hpp"]
 
 # ebc_get / ebc_put selectors (eqbatchcheck.cpp: BatchEqProbe::buffer)
 BUFFERS = ["x", "y", "tx", "ty", "px", "py", "sx", "sy", "Vcur", "tce", "sce", "out", "sys_V", "sys_rhs", "sys_p",

@@ -1304,6 +1304,41 @@ extern "C" int32_t hc_line_search(double initial_violation, int32_t counter, con
 }
 
 // ---------------------------------------------------------------------------
+// Newton's own search (ipm_line_search.hpp: NewtonSearch), driven by a script as hc_line_search drives the other:
+// the searches of one solve, sharing ONE filter (made for no violation) and the machine's cost, which starts as
+// `f0`.  starts[k] = D_phi of the k-th search; the answers are taken in order, three doubles each: a trial point's
+// {f, finite, -}, the fallback's {||g||_1 here, ||g||_1 at the full step, f at the full step}.  out rows (5 doubles):
+//   a request       {0 Eval | 3 KktEval, the step asked about (t_alpha; the full step for KktEval), 0, 0, 0}
+//   a search's end  {4, failed, the step to commit, the cost kept, alpha}
+// A failed search is the last.  Returns the rows (written up to `cap`), or -1 where the answers ran out.
+// ---------------------------------------------------------------------------
+extern "C" int32_t hc_newton_search(double f0, const double* starts, int32_t n_starts, const double* answers,
+                                    int32_t n_answers, double* out, int32_t cap) {
+  using slpx::ipm_host::NewtonSearch;
+  using Want = NewtonSearch::Want;
+  slpx::ipm_host::Filter filter{0.0};
+  NewtonSearch ns;
+  ns.f = f0;
+  int32_t rows = 0, used = 0;
+  auto put = [&](std::initializer_list<double> row) {
+    if (rows < cap) std::copy(row.begin(), row.end(), out + 5 * static_cast<size_t>(rows));
+    ++rows;
+  };
+  for (int32_t k = 0; k < n_starts && !ns.failed; ++k) {
+    ns.start(filter, starts[k]);
+    while (ns.want != Want::Done) {
+      put({static_cast<double>(ns.want), ns.want == Want::KktEval ? NewtonSearch::alpha_max : ns.t_alpha, 0.0, 0.0, 0.0});
+      if (used >= n_answers) return -1;
+      const double* a = answers + 3 * static_cast<size_t>(used++);
+      if (ns.want == Want::KktEval) ns.on_kkt_errors(a[0], a[1], a[2]);
+      else ns.on_trial(a[0], a[1] != 0.0);
+    }
+    put({4.0, ns.failed ? 1.0 : 0.0, ns.t_alpha, ns.f, ns.alpha});
+  }
+  return rows;
+}
+
+// ---------------------------------------------------------------------------
 // The regularization policy every factorization driver runs (csrc/ldlt_policy.hpp), driven without a device: the
 // loops NewtonSystem::compute / compute_twin / compute_hooked run (ldlt_run_batch, ldlt_run_twin), with launchers that
 // answer every attempt from a scripted inertia RESPONSE instead of a factorization.

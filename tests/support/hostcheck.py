@@ -75,6 +75,7 @@ def lib():
     sig("hc_solve_after_factor", None, vp, vp)
     sig("hc_backsub", None, vp, vp, vp, d, vp, vp)
     sig("hc_line_search", i32, d, i32, vp, i32, vp, i32, vp, i32)
+    sig("hc_newton_search", i32, d, vp, i32, vp, i32, vp, i32)
     sig("hc_reg_policy", i32, i32, i32, i32, i32, d, i32, ctypes.c_uint32, d, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp)
     _lib = L
     return L
@@ -114,6 +115,29 @@ def line_search(searches, initial_violation=1.0, counter=0):
             res.append(("done", how[int(r[1])], bool(r[2]), r[3], r[4], int(r[5]), r[6], bool(r[7])))
         else:
             res.append((kinds[int(r[0])], r[1], r[2], bool(r[3]), bool(r[4]), r[5]))
+    return res
+
+
+def newton_search(f0, searches):
+    """Newton's own search (csrc/ipm_line_search.hpp: NewtonSearch) driven by scripted answers (hostcheck.cpp:
+    hc_newton_search).  searches = [(D_phi, answers), ...] sharing one filter and the cost the machine keeps, f0 at
+    first; an answer is (f, finite) for a trial point, (||g||_1 here, ||g||_1 at the full step, f at the full step)
+    for the fallback.  Returns the rows: requests ("eval" | "kkt", step) and, per search,
+    ("done", failed, the step to commit, the cost kept, alpha); a failed search is the last."""
+    starts = _fa([d for d, _ in searches])
+    flat = [tuple(a) + (0.0,) * (3 - len(a)) for _, ans in searches for a in ans]
+    answers = _fa(flat if flat else np.zeros((0, 3))).reshape(-1, 3)
+    out = np.zeros((4096, 5))
+    rows = lib().hc_newton_search(float(f0), starts.ctypes.data, len(starts), answers.ctypes.data, len(answers),
+                                  out.ctypes.data, len(out))
+    if rows < 0:
+        raise RuntimeError("newton_search: the script's answers ran out")
+    res = []
+    for r in out[:rows]:
+        if r[0] == 4.0:
+            res.append(("done", bool(r[1]), r[2], r[3], r[4]))
+        else:
+            res.append(("eval" if r[0] == 0.0 else "kkt", r[1]))
     return res
 
 

@@ -1,4 +1,5 @@
-"""The filter line search every solver driver runs (csrc/ipm_line_search.hpp), without a GPU: a scripted list of
+"""The line searches of the solver drivers (csrc/ipm_line_search.hpp: the filter line search every driver but Newton
+runs, and Newton's own — below), without a GPU: a scripted list of
 answers goes in, the sequence of requests and the end state come out (tests/support/hostcheck.cpp: hc_line_search).
 
 The expected sequences are written from the reference's lines (interior_point.hpp:512-716, filter.hpp:109-172), not
@@ -7,7 +8,12 @@ a trial point passes the filter's rules iff  f <= f_cur - alpha^1.5 1e-8 viol_cu
 viol <= (1 - alpha^1.5 1e-5) viol_cur), the current iterate is (f, violation) = (10, 1) unless said otherwise, and
 the filter was made for an initial violation of 1: max_constraint_violation = 1e4.
 """
-from tests.support.hostcheck import line_search
+import itertools
+import math
+
+import pytest
+
+from tests.support.hostcheck import line_search, newton_search
 
 AZ = 0.9                                         # alpha_z of the Newton direction
 START = (1.0, AZ, 0.0, 0.0, 10.0, 0.0, 1.0)      # alpha_max, alpha_z, D_phi, mu, f, sum ln s, violation
@@ -133,3 +139,123 @@ def test_sqp_corrections_keep_the_full_step():
         expected += [solve(k == 0, 1.0), req("soc_eval", 1.0, 1.0, True)]
     rows = line_search([(start, [WORSE] + answers + [GOOD])])
     check(rows, [req("eval", 1.0, 1.0)] + expected + [req("eval", 0.5, 1.0), ("done", "newton", False, 0.5, 1.0, 1, MAXV, False)])
+
+
+# ---- Newton's own search (csrc/ipm_line_search.hpp: NewtonSearch; hostcheck.cpp: hc_newton_search) ----
+#
+# The machine against a restatement of the reference's lines (newton.hpp: the loop "until a step is accepted" of
+# newton(), and filter.hpp:109-172 for entries without a constraint violation), fed the same scripted answers.
+
+REDUCTION, FLOOR, DECREASE = 0.5, 1e-20, 0.999   # α_reduction_factor, α_min, the fallback's factor, as the reference has them
+# trial points it takes to pass the floor: the first k with REDUCTION^k < FLOOR
+TO_THE_FLOOR = next(k for k in itertools.count(1) if REDUCTION ** k < FLOOR)
+DESCENT = -1.0                                   # D_phi of a descent direction
+NONFINITE = (float("nan"), False)
+
+
+class ReferenceFilter:
+    """filter.hpp:109-172 where every entry's constraint violation is 0 (an unconstrained problem): the violation
+    tests pass (0 <= max, 0 <= min_constraint_violation, 0 <= (1 - phi gamma) 0), the table holds costs."""
+
+    def __init__(self):
+        self.table = []
+
+    def try_add(self, f_cur, f_trial, D_phi, alpha):
+        if not math.isfinite(f_trial):
+            return False
+        switching = D_phi < 0 and alpha * (-D_phi) ** 2.3 > 0.0 ** 1.1
+        armijo = f_trial <= f_cur + 1e-8 * alpha * D_phi
+        if switching and not armijo:
+            return False                          # (otherwise: sufficient decrease holds by the violation's test)
+        if any(cost <= f_trial for cost in self.table):
+            return False                          # dominated by an entry of the table
+        if not switching or not armijo:
+            self.table = [cost for cost in self.table if not f_cur <= cost] + [f_cur]
+        return True
+
+
+def reference_newton_search(filt, f, D_phi, answers):
+    """The reference's loop; `answers` as hc_newton_search takes them.  Returns the rows expected of the machine."""
+    alpha_max = 1.0
+    alpha = alpha_max
+    rows = []
+    while True:
+        rows.append(("eval", alpha))
+        trial_f, finite = next(answers)
+        if not finite:
+            alpha *= REDUCTION
+            if alpha < FLOOR:
+                return rows + [("done", True)], f
+            continue
+        if filt.try_add(f, trial_f, D_phi, alpha):
+            return rows + [("done", False, alpha, trial_f, alpha)], trial_f
+        alpha *= REDUCTION
+        if alpha < FLOOR:
+            rows.append(("kkt", alpha_max))
+            current, at_full_step, f_at_full_step = next(answers)
+            if at_full_step <= DECREASE * current:
+                return rows + [("done", False, alpha_max, f_at_full_step, alpha)], f_at_full_step
+            return rows + [("done", True)], f
+
+
+def newton_rows(f0, searches):
+    """the machine's rows, checked against the reference's restatement; a failed search's end is ("done", True)"""
+    got = [r[:2] if r[0] == "done" and r[1] else r for r in newton_search(f0, searches)]
+    filt, f, expected = ReferenceFilter(), f0, []
+    for D_phi, answers in searches:
+        rows, f = reference_newton_search(filt, f, D_phi, iter(answers))
+        expected += rows
+    assert got == expected, (got, expected)
+    return got
+
+
+def test_floor_of_the_newton_search_follows_from_its_constants():
+    assert REDUCTION ** (TO_THE_FLOOR - 1) >= FLOOR > REDUCTION ** TO_THE_FLOOR
+
+
+def test_newton_first_trial_accepted():
+    rows = newton_rows(10.0, [(DESCENT, [(9.0, True)])])
+    assert rows == [("eval", 1.0), ("done", False, 1.0, 9.0, 1.0)]
+
+
+@pytest.mark.parametrize("k", [1, 3, TO_THE_FLOOR - 1])
+def test_newton_rejections_then_acceptance(k):
+    """k trial points with the cost up, then one with the cost down: accepted at REDUCTION^k.  The accepted cost is what
+    the next search compares with: 9.5 is no decrease from 9 (it would have been one from 10)."""
+    rows = newton_rows(10.0, [(DESCENT, [(11.0, True)] * k + [(9.0, True)]), (DESCENT, [(9.5, True), (8.0, True)])])
+    assert rows[: k + 2] == [("eval", REDUCTION ** j) for j in range(k + 1)] + [("done", False, REDUCTION ** k, 9.0, REDUCTION ** k)]
+    assert rows[k + 2:] == [("eval", 1.0), ("eval", REDUCTION), ("done", False, REDUCTION, 8.0, REDUCTION)]
+
+
+def test_newton_nonfinite_costs_past_the_floor_fail_without_a_fallback():
+    rows = newton_rows(10.0, [(DESCENT, [NONFINITE] * TO_THE_FLOOR)])
+    assert rows == [("eval", REDUCTION ** j) for j in range(TO_THE_FLOOR)] + [("done", True)]
+    # the last trial point decides: non-finite after finite rejections fails, finite after non-finite ones falls back
+    rows = newton_rows(10.0, [(DESCENT, [(11.0, True)] * (TO_THE_FLOOR - 1) + [NONFINITE])])
+    assert rows[-2:] == [("eval", REDUCTION ** (TO_THE_FLOOR - 1)), ("done", True)]
+    rows = newton_rows(10.0, [(DESCENT, [NONFINITE] * (TO_THE_FLOOR - 1) + [(11.0, True), (1.0, 0.5, 7.0)])])
+    assert rows[-2:] == [("kkt", 1.0), ("done", False, 1.0, 7.0, REDUCTION ** TO_THE_FLOOR)]
+
+
+def test_newton_fallback_at_the_full_step_succeeds():
+    """Every trial point rejected down to the floor; ||g||_1 at the full step is DECREASE times the current one: the
+    full step is committed and the cost kept is the full sweep's.  alpha stays the halved one."""
+    stall = [(11.0, True)] * TO_THE_FLOOR
+    rows = newton_rows(10.0, [(DESCENT, stall + [(1.0, DECREASE, 7.0)]), (DESCENT, [(7.5, True), (6.0, True)])])
+    evals = [("eval", REDUCTION ** j) for j in range(TO_THE_FLOOR)]
+    assert rows[: TO_THE_FLOOR + 2] == evals + [("kkt", 1.0), ("done", False, 1.0, 7.0, REDUCTION ** TO_THE_FLOOR)]
+    assert rows[TO_THE_FLOOR + 2:] == [("eval", 1.0), ("eval", REDUCTION), ("done", False, REDUCTION, 6.0, REDUCTION)]
+
+
+def test_newton_fallback_at_the_full_step_fails():
+    stall = [(11.0, True)] * TO_THE_FLOOR
+    rows = newton_rows(10.0, [(DESCENT, stall + [(1.0, 0.9991, 7.0)])])
+    assert rows == [("eval", REDUCTION ** j) for j in range(TO_THE_FLOOR)] + [("kkt", 1.0), ("done", True)]
+    rows = newton_rows(10.0, [(DESCENT, stall + [(1.0, float("nan"), 7.0)])])
+    assert rows[-1] == ("done", True)
+
+
+def test_newton_ascent_direction_goes_through_the_table():
+    """D_phi >= 0: no switching condition, so an accepted step adds the current cost to the table (filter.hpp:165-169)
+    and a later trial point at or above it is rejected as dominated."""
+    newton_rows(10.0, [(0.5, [(9.0, True)]), (0.5, [(10.0, True), (8.0, True)])])

@@ -1,7 +1,7 @@
 """The batched interior-point kernels (ipm_batch_kernels.h) through their launch wrappers (BatchIpmDevice,
 ipm_batch_launch.hip), instance by instance: a probe (tests/support/batchcheck.cpp) drives each method on the batch
 system of a model (`sa.System(problem, B)`: tape at unit scales, as Problem::batch_system builds it), and every output
-is compared with plain float64 numpy of the same formulas (interior_point.hpp, kkt_error.hpp, as ipm_batch.cpp
+is compared with plain float64 numpy of the same formulas (interior_point.hpp, kkt_error.hpp, as batch_lockstep.cpp
 consumes them).  Each instance of a batch has its own scales, iterate, mu, tau, step sizes and flags, and the mask of
 active instances has holes.  The V of instance b is taken from a batch-1 system of the same model under that instance's
 scales (its V is pinned to the oracle by test_gpu_parity.py).
