@@ -260,6 +260,29 @@ int slpx_ldlt_compute(slpx_system* s, int32_t* info, double* reg, int32_t* facto
 int slpx_ldlt_reset(slpx_system* s, double gamma_min);
 int slpx_ldlt_solve(slpx_system* s); /* rhs -> p, reusable after one compute */
 int slpx_step_backsub(slpx_system* s);
+/* r = rhs - (lhs + diag(delta, -gamma)) p of the factorization in memory, accumulated in
+ * double-double; r[batch][dim] and norm_inf[batch] may be NULL.
+ * lhs, rhs, p: what slpx_system_get(1 / 2 / 3) hands out (a matrix or right-hand side the caller set is used as
+ * given; a Newton step that never stored its system has it assembled now, at the RESIDENT state); delta on the
+ * first n rows, -gamma on the other m_e, per problem those of the last factorization of that problem — the pair
+ * slpx_ldlt_compute / slpx_newton_step settled on, or the one given to slpx_ldlt_factor.  Every row is summed in one
+ * fixed order, so r and norm_inf of a problem have the same bits at any batch size.  norm_inf = max |r_i|, non-finite
+ * if any r_i is.  Returns 0, or -100 + slpx_last_error() (no factorization and solution in memory yet).  An
+ * addition within ABI version 6, detected by the symbol's presence like slpx_problem_solve_batch. */
+int slpx_ldlt_residual(slpx_system* s, double* r, double* norm_inf);
+/* up to max_steps steps of iterative refinement of p on the factors in memory;
+ * norms[batch][max_steps+1] (unused tail = NaN), accepted[batch]; either may be NULL.
+ * A step solves (lhs + diag(delta, -gamma)) d = r with the factors in memory and takes p + d only if its residual
+ * norm is finite and smaller than the one before — otherwise that problem keeps its p and stops; a problem whose
+ * first norm is 0 takes no step (p keeps its bits).  norms = the norm before, then the one after every step taken or
+ * tried; accepted = steps taken.  The right-hand side in memory is the same on return; p_s / p_z are not updated:
+ * slpx_step_backsub does that.  Between slpx_newton_step and slpx_step_backsub, and BEFORE the iterate moves: a
+ * system the step never stored is evaluated at the resident state.  An addition within ABI version 6. */
+int slpx_ldlt_refine(slpx_system* s, int32_t max_steps, double* norms, int32_t* accepted);
+/* The two above for the problems with mask[b] != 0 only (mask NULL: all): nothing of the others is touched — their
+ * p, and their rows of r, norm_inf, norms and accepted keep what they held.  Additions within ABI version 6. */
+int slpx_ldlt_residual_masked(slpx_system* s, const uint8_t* mask, double* r, double* norm_inf);
+int slpx_ldlt_refine_masked(slpx_system* s, int32_t max_steps, const uint8_t* mask, double* norms, int32_t* accepted);
 /* AD refresh (optional) + assemble + rhs + compute + solve + backsub */
 int slpx_newton_step(slpx_system* s, int refresh_ad, int32_t* info);
 /* `count` such steps one after the other on the resident state, each waited for like a single

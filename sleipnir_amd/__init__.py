@@ -168,6 +168,11 @@ def lib() -> ctypes.CDLL:
             vp, vp, vp, vp, vp, ctypes.POINTER(Report))
     if hasattr(L, "slpx_problem_batch_stats"):
         sig("slpx_problem_batch_stats", ctypes.c_int, vp, vp)
+    if hasattr(L, "slpx_ldlt_residual"):
+        sig("slpx_ldlt_residual", ctypes.c_int, vp, vp, vp)
+        sig("slpx_ldlt_refine", ctypes.c_int, vp, i32, vp, vp)
+        sig("slpx_ldlt_residual_masked", ctypes.c_int, vp, vp, vp, vp)
+        sig("slpx_ldlt_refine_masked", ctypes.c_int, vp, i32, vp, vp, vp)
     _lib = L
     return L
 
@@ -448,6 +453,37 @@ class System:
 
     def backsub(self):
         _check(lib().slpx_step_backsub(self._h))
+
+    @staticmethod
+    def _mask(mask, batch):
+        if mask is None:
+            return None
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        if m.shape != (batch,):
+            raise ValueError("mask: one entry per problem of the batch")
+        return m
+
+    def residual(self, mask=None, out=None):
+        """(r, norm): r = rhs - (lhs + diag(delta, -gamma)) p of the factorization in memory, accumulated in
+        double-double (slpx_ldlt_residual); r is [batch, dim], norm [batch] = max |r_i| (non-finite if an r_i is).
+        mask: only the problems with mask[b] != 0 — the others' rows keep what `out` = (r, norm) held (zeros
+        without `out`).  Also on a linear_solver() handle."""
+        dim = self.info["n"] + self.info["m_e"]
+        r, norm = (np.zeros((self.batch, dim)), np.zeros(self.batch)) if out is None else out
+        m = self._mask(mask, self.batch)
+        _check(lib().slpx_ldlt_residual_masked(self._h, _ptr(m), r.ctypes.data, norm.ctypes.data))
+        return r, norm
+
+    def refine(self, max_steps=1, mask=None):
+        """(norms, accepted): up to max_steps steps of iterative refinement of p on the factors in memory
+        (slpx_ldlt_refine).  norms is [batch, max_steps + 1]: the residual norm before, then after every step taken or
+        tried (NaN beyond); accepted [batch] = steps taken.  Run it before the iterate moves: a Newton step that never
+        stored its system has it evaluated at the resident state.  mask as in residual() (rows of the others: NaN, 0)."""
+        norms = np.full((self.batch, int(max_steps) + 1), np.nan)
+        accepted = np.zeros(self.batch, dtype=np.int32)
+        m = self._mask(mask, self.batch)
+        _check(lib().slpx_ldlt_refine_masked(self._h, int(max_steps), _ptr(m), norms.ctypes.data, accepted.ctypes.data))
+        return norms, accepted
 
     def newton_step(self, refresh_ad=True):
         info = np.zeros(self.batch, dtype=np.int32)

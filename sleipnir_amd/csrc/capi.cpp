@@ -490,6 +490,44 @@ int slpx_ldlt_reset(slpx_system* s, double gamma_min) {
   });
 }
 int slpx_ldlt_solve(slpx_system* s) { return guard([&] { s->get().device().solve(); }); }
+int slpx_ldlt_residual_masked(slpx_system* s, const uint8_t* mask, double* r, double* norm_inf) {
+  return guard([&] {
+    if (slpx_device_count() < 1) throw std::runtime_error("slpx_ldlt_residual: no HIP device");
+    if (s == nullptr) throw std::runtime_error("slpx_ldlt_residual: null system");
+    auto& dev = s->get().device();
+    const size_t B = dev.batch(), dim = s->get().kkt().dim;
+    const std::vector<uint8_t> active = mask ? std::vector<uint8_t>(mask, mask + B) : std::vector<uint8_t>(B, 1);
+    std::vector<double> norm;
+    dev.residual(active, norm);
+    for (size_t b = 0; b < B; ++b) {
+      if (!active[b]) continue;
+      if (norm_inf) norm_inf[b] = norm[b];
+      if (r) dev.download(dev.d_residual() + b * dim, r + b * dim, dim);
+    }
+  });
+}
+int slpx_ldlt_residual(slpx_system* s, double* r, double* norm_inf) { return slpx_ldlt_residual_masked(s, nullptr, r, norm_inf); }
+
+int slpx_ldlt_refine_masked(slpx_system* s, int32_t max_steps, const uint8_t* mask, double* norms, int32_t* accepted) {
+  return guard([&] {
+    if (slpx_device_count() < 1) throw std::runtime_error("slpx_ldlt_refine: no HIP device");
+    if (s == nullptr) throw std::runtime_error("slpx_ldlt_refine: null system");
+    auto& sys = s->get();
+    const size_t B = sys.batch();
+    std::vector<uint8_t> active;
+    if (mask) active.assign(mask, mask + B);
+    const slpx::NewtonSystem::Refinement res = sys.refine(max_steps, mask ? &active : nullptr);
+    const size_t stride = static_cast<size_t>(max_steps) + 1;
+    for (size_t b = 0; b < B; ++b) {
+      if (mask && !active[b]) continue;
+      if (norms) std::copy(res.norms.begin() + b * stride, res.norms.begin() + (b + 1) * stride, norms + b * stride);
+      if (accepted) accepted[b] = res.accepted[b];
+    }
+  });
+}
+int slpx_ldlt_refine(slpx_system* s, int32_t max_steps, double* norms, int32_t* accepted) {
+  return slpx_ldlt_refine_masked(s, max_steps, nullptr, norms, accepted);
+}
 int slpx_step_backsub(slpx_system* s) { return guard([&] { s->get().device().backsub(); }); }
 int slpx_newton_step(slpx_system* s, int refresh_ad, int32_t* info) {
   return guard([&] {

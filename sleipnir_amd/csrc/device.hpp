@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -485,6 +486,24 @@ class DeviceNlp {
   void factor_solve_publish(const std::vector<double>& delta, const std::vector<double>& gamma,
                             const std::vector<uint8_t>& active);
   void refine_solution(int iters);                  // iterative refinement of the last solve() against the lhs
+  // ---- residual of the solution in memory, and the pieces of its iterative refinement (kkt_refine.hip; the loop is
+  // NewtonSystem::refine) ----
+  // r = rhs - (lhs + diag(delta, -gamma)) p for the problems with mask[b] != 0, accumulated in double-double
+  // (kkt_residual.h), into d_residual(); norm[b] = max |r_i| of those problems (a NaN or Inf in r shows as a non-finite
+  // norm), the others' entries of r and norm are not touched.  (delta, gamma) are those of the factorization whose
+  // factors are in memory.  Needs a factorization and a solution in memory (throws otherwise); lhs / rhs are assembled
+  // at the RESIDENT state if the step that made p never stored them.  Synchronizes.
+  void residual(const std::vector<uint8_t>& mask, std::vector<double>& norm);
+  double* d_residual() { return m_res.p; }
+  void refine_begin();             // keeps p and rhs
+  void refine_solve_correction();  // residual -> rhs, solve(), the correction d kept aside, rhs = the kept one again
+  void refine_apply(const std::vector<uint8_t>& accept);  // p = kept p + d where accept[b], the kept p elsewhere
+  void refine_keep_solution();     // the kept p = p
+  // (delta, gamma) of the factorization whose factors of problem b are in memory (NaN: none yet)
+  std::pair<double, double> factored_regularization(int b) const {
+    if (static_cast<size_t>(b) >= m_fact_delta.size()) return {std::numeric_limits<double>::quiet_NaN(), 0.0};
+    return {m_fact_delta[b], m_fact_gamma[b]};
+  }
   void backsub();                                   // p -> p_x, p_y, p_s, p_z
   void backsub_and_publish(const LdltStats* stats_src);
   void backsub_publish();
@@ -561,10 +580,12 @@ class DeviceNlp {
     int stats_cur, stats_tw_cur, xg_parity, xg_tw_parity, twin_mode, kkt_pending;
     bool last_step_chained, stats_in_host, lhs_stale, rhs_stale, tape_pending, touched;
     unsigned long long stats_seq;
+    std::pair<double, double> factored;  // factored_regularization(0)
   };
   LaunchBook save_book() const {
     return LaunchBook{m_stats_cur, m_stats_tw_cur, m_xg_parity, m_xg_tw_parity, m_twin_mode, m_kkt_pending, m_last_step_chained,
-                      m_stats_in_host, m_lhs_stale, m_rhs_stale, m_stream.tape_pending, m_stream.touched, m_stats_seq};
+                      m_stats_in_host, m_lhs_stale, m_rhs_stale, m_stream.tape_pending, m_stream.touched, m_stats_seq,
+                      factored_regularization(0)};
   }
   // launch_ran: the launch was not let pass at its gate — it ran with its results held back (a step that carried the
   // error launch deciding about it: MfDev::ride_verdict) and so moved the launch's OWN hand-overs on: the buffers the
@@ -585,6 +606,7 @@ class DeviceNlp {
     m_stream.tape_pending = b.tape_pending;
     m_stream.touched = b.touched;
     m_stats_seq = b.stats_seq;
+    if (!launch_ran) note_factored(0, b.factored.first, b.factored.second);
   }
   double* d_V_trial() { return m_V_trial.p; }
   // the tape's separable sums (for a caller's launch that lets them ride: restoration.hip's error launch)
@@ -679,6 +701,23 @@ class DeviceNlp {
   DevBuf<int32_t> m_dense_colptr, m_dense_rowidx;
   uint32_t m_dense_lds = 0;
   DevBuf<double> m_rhs0, m_p_acc;
+  // residual / refinement (kkt_refine.hip): the row map of the lhs (KktRowMap) and the buffers, all made on first use
+  DevBuf<int32_t> m_rm_rowptr, m_rm_ent, m_rm_col;
+  DevBuf<double> m_res, m_ref_keep_p, m_ref_keep_b, m_ref_d, m_res_reg;
+  DevBuf<unsigned long long> m_res_partial, m_res_norm;
+  DevBuf<uint8_t> m_res_mask;
+  // what the factors in memory are factors OF, per problem: written wherever a factorization is enqueued
+  std::vector<double> m_fact_delta, m_fact_gamma;
+  double m_fact_tw[2] = {0.0, 0.0};  // ... of the second attempt of a twin launch (adopt_twin)
+  bool m_solution_valid = false;     // some solve has written p
+  void note_factored(int b, double delta, double gamma) {
+    if (m_fact_delta.empty()) {
+      m_fact_delta.assign(m_batch, std::numeric_limits<double>::quiet_NaN());
+      m_fact_gamma.assign(m_batch, 0.0);
+    }
+    m_fact_delta[b] = delta;
+    m_fact_gamma[b] = gamma;
+  }
   DevBuf<uint32_t> m_sn_lvl_ptr, m_col_sn, m_lvl_pack, m_col_lvl_pack;
   DevBuf<uint2> m_bwd_range;
   DevBuf<LdltSolveItem> m_fwd_items, m_sext_items, m_bwd_items;

@@ -1595,6 +1595,7 @@ void DeviceNlp::write_reg(const std::vector<double>& delta, const std::vector<do
   for (int b = 0; b < m_batch; ++b) {
     m_h_reg[2 * b] = active[b] ? delta[b] : std::numeric_limits<double>::quiet_NaN();
     m_h_reg[2 * b + 1] = gamma[b];
+    if (active[b]) note_factored(b, delta[b], gamma[b]);
   }
 }
 
@@ -1792,6 +1793,7 @@ bool DeviceNlp::twin_available() {
 // roles, parities and chain numbers of this moment; book_mf_step() is what the launch changes on the host.
 void DeviceNlp::launch_mf_step(int twin_mode, const double* reg, const KktFuse& f, bool chained, const double* lhs2, const double* rhs2) {
   const LdltPlan& l = m_l_ref;
+  m_solution_valid = true;
   const int parity = m_stats_cur ^ 1;
   LdltStats* cur = m_stats.p + static_cast<size_t>(parity);
   LdltStats* next = m_stats.p + static_cast<size_t>(parity ^ 1);
@@ -1927,6 +1929,9 @@ bool DeviceNlp::factor_solve_publish_twin(double delta0, double gamma0, double d
   m_h_reg[1] = gamma0;
   m_h_reg[2] = delta1;
   m_h_reg[3] = gamma1;
+  note_factored(0, delta0, gamma0);
+  m_fact_tw[0] = delta1;
+  m_fact_tw[1] = gamma1;
   if (!m_kkt_pending) materialize_kkt();
   const KktFuse f = take_kkt_fuse();
   launch_mf_step(mode, m_h_reg, f, false);
@@ -1943,6 +1948,9 @@ bool DeviceNlp::factor_solve_publish_twin_written(double delta0, double gamma0, 
   m_h_reg[1] = gamma0;
   m_h_reg[2] = delta1;
   m_h_reg[3] = gamma1;
+  note_factored(0, delta0, gamma0);
+  m_fact_tw[0] = delta1;
+  m_fact_tw[1] = gamma1;
   launch_mf_step(mode, m_h_reg, KktFuse{}, false, lhs2, rhs2);
   book_mf_step(mode, false);
   m_stats_seq = ++m_seq_expected;
@@ -1963,6 +1971,7 @@ void DeviceNlp::adopt_twin() {
   std::swap(m_stats_cur, m_stats_tw_cur);
   m_h_stats[0] = m_h_stats[1];
   m_twin_mode = 0;
+  note_factored(0, m_fact_tw[0], m_fact_tw[1]);
 }
 
 void DeviceNlp::enqueue_factor_solve(int parity) {
@@ -2010,6 +2019,7 @@ void DeviceNlp::read_stats(std::vector<LdltStats>& out) {
 // corrections, multiplier estimate, slpx_ldlt_solve): forward, then backward.
 void DeviceNlp::solve() {
   if (m_rhs_stale) build_rhs();
+  m_solution_valid = true;
   const LdltPlan& l = m_l_ref;
   if (m_dense) {
     solve_after_factor();
@@ -2085,6 +2095,7 @@ void DeviceNlp::solve_backsub_publish() {
 
 void DeviceNlp::solve_after_factor_impl(const LdltStats* publish) {
   const LdltPlan& l = m_l_ref;
+  m_solution_valid = true;
   const long long lxs = static_cast<long long>(std::max<int64_t>(1, l.nnzL));
   if (m_dense) {  // (nothing rides in a dense factorization: forward and backward substitution from the rhs in memory)
     if (m_rhs_stale) build_rhs();

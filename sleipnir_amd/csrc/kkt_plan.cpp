@@ -3,6 +3,8 @@
 #include "setup_timing.hpp"
 
 #include <algorithm>
+#include <stdexcept>
+#include <utility>
 
 namespace slpx {
 
@@ -145,6 +147,66 @@ KktPlan build_kkt_plan(const NlpStructure& s) {
   k.rhs_bytes = 16LL * n + 24LL * s.m_e + 24LL * s.m_i + 12 * (a + i);
   lap("  kkt plan");
   return k;
+}
+
+CscPattern complete_diagonal(const CscPattern& lower, std::vector<int32_t>& user_map, std::vector<uint8_t>& diag_given) {
+  const int dim = lower.cols;
+  CscPattern full;
+  full.rows = full.cols = dim;
+  full.colptr.assign(1, 0);
+  user_map.assign(lower.rowidx.size(), -1);
+  diag_given.assign(dim, 0);
+  for (int c = 0; c < dim; ++c) {
+    std::vector<std::pair<int32_t, int32_t>> rows;  // (row, index in the caller's arrays or -1)
+    bool has_diag = false;
+    for (int32_t p = lower.colptr[c]; p < lower.colptr[c + 1]; ++p) {
+      const int32_t r = lower.rowidx[p];
+      if (r < c || r >= dim) throw std::runtime_error("slpx: the pattern must be the lower triangle in CSC form");
+      has_diag = has_diag || r == c;
+      rows.emplace_back(r, p);
+    }
+    diag_given[c] = has_diag;
+    if (!has_diag) rows.emplace_back(c, -1);
+    std::sort(rows.begin(), rows.end());
+    for (auto& [r, p] : rows) {
+      if (p >= 0) user_map[p] = static_cast<int32_t>(full.rowidx.size());
+      full.rowidx.push_back(r);
+    }
+    full.colptr.push_back(static_cast<int32_t>(full.rowidx.size()));
+  }
+  return full;
+}
+
+KktRowMap build_kkt_row_map(const CscPattern& lower) {
+  const int dim = lower.cols;
+  KktRowMap m;
+  m.rowptr.assign(dim + 1, 0);
+  for (int c = 0; c < dim; ++c)
+    for (int32_t q = lower.colptr[c]; q < lower.colptr[c + 1]; ++q) {
+      const int32_t r = lower.rowidx[q];
+      ++m.rowptr[r + 1];             // K(r, c) in row r
+      if (r != c) ++m.rowptr[c + 1];  // ... and, mirrored, in row c
+    }
+  for (int i = 0; i < dim; ++i) m.rowptr[i + 1] += m.rowptr[i];
+  m.ent.assign(m.rowptr[dim], 0);
+  m.col.assign(m.rowptr[dim], 0);
+  std::vector<int32_t> fill(m.rowptr.begin(), m.rowptr.end() - 1);
+  // the row's own part: columns ascending, so every K(i, j), j <= i, lands in column order
+  for (int c = 0; c < dim; ++c)
+    for (int32_t q = lower.colptr[c]; q < lower.colptr[c + 1]; ++q) {
+      const int32_t at = fill[lower.rowidx[q]]++;
+      m.ent[at] = q;
+      m.col[at] = c;
+    }
+  // the mirrored part behind it: column i below the diagonal, in the order of the column
+  for (int c = 0; c < dim; ++c)
+    for (int32_t q = lower.colptr[c]; q < lower.colptr[c + 1]; ++q)
+      if (lower.rowidx[q] != c) {
+        const int32_t at = fill[c]++;
+        m.ent[at] = q;
+        m.col[at] = lower.rowidx[q];
+      }
+  return m;
 }
 
 }  // namespace slpx

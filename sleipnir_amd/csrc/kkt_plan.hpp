@@ -56,4 +56,20 @@ struct KktPlan {
 
 KktPlan build_kkt_plan(const NlpStructure& s);
 
+// Row-gather form of a symmetric matrix given by its lower triangle in CSC (pattern 5 of a problem's system, or the
+// pattern of a bare linear-solver system: the same thing): for row i the list of (index into the value array,
+// column j) of every entry of the FULL matrix in that row — first row i of the lower triangle, K(i, j) for j <= i in
+// column order (the diagonal last), then column i below the diagonal, K(j, i) for j > i in row order.  2 nnz - dim
+// entries where every diagonal entry is present.  The residual of a solve (kkt_residual.h) sums a row in this order.
+// The pattern a bare linear-solver system factors: the caller's lower triangle plus every diagonal entry it lacks
+// (sparse_regularized_ldlt.hpp:67), rows of a column sorted.  user_map[k] = position in the result of the caller's
+// entry k; diag_given[c] = the caller's pattern held the diagonal entry of column c.  Throws on an entry above the
+// diagonal or outside the matrix.
+CscPattern complete_diagonal(const CscPattern& lower, std::vector<int32_t>& user_map, std::vector<uint8_t>& diag_given);
+
+struct KktRowMap {
+  std::vector<int32_t> rowptr, ent, col;
+};
+KktRowMap build_kkt_row_map(const CscPattern& lower);
+
 }  // namespace slpx

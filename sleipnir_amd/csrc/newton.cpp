@@ -191,28 +191,8 @@ NewtonSystem::NewtonSystem(const CscPattern& lower, int n_dec, int m_e, const Ne
   m_k.m_e = m_e;
   m_k.m_i = 0;
   m_k.dim = dim;
-  m_k.lhs.rows = m_k.lhs.cols = dim;
-  m_k.lhs.colptr.assign(1, 0);
-  m_user_lhs_map.assign(lower.rowidx.size(), -1);
-  std::vector<uint8_t> diag_has_source(dim, 0);
-  for (int c = 0; c < dim; ++c) {
-    std::vector<std::pair<int32_t, int32_t>> rows;  // (row, index in the caller's arrays or -1)
-    bool has_diag = false;
-    for (int32_t p = lower.colptr[c]; p < lower.colptr[c + 1]; ++p) {
-      const int32_t r = lower.rowidx[p];
-      if (r < c || r >= dim) throw std::runtime_error("slpx: the pattern must be the lower triangle in CSC form");
-      has_diag = has_diag || r == c;
-      rows.emplace_back(r, p);
-    }
-    diag_has_source[c] = has_diag;
-    if (!has_diag) rows.emplace_back(c, -1);
-    std::sort(rows.begin(), rows.end());
-    for (auto& [r, p] : rows) {
-      if (p >= 0) m_user_lhs_map[p] = static_cast<int32_t>(m_k.lhs.rowidx.size());
-      m_k.lhs.rowidx.push_back(r);
-    }
-    m_k.lhs.colptr.push_back(static_cast<int32_t>(m_k.lhs.rowidx.size()));
-  }
+  std::vector<uint8_t> diag_has_source;
+  m_k.lhs = complete_diagonal(lower, m_user_lhs_map, diag_has_source);
   const int nnz = m_k.lhs.nnz();
   m_k.dptr.assign(nnz + 1, 0);
   m_k.pptr.assign(nnz + 1, 0);
@@ -456,6 +436,54 @@ bool NewtonSystem::factor_unregularized() {
   m_dev->read_stats(stats);
   ++m_last_factorizations;
   return std::all_of(stats.begin(), stats.begin() + B, [&](const LdltStats& st) { return ldlt_ideal(st, m_s.n, m_s.m_e); });
+}
+
+NewtonSystem::Refinement NewtonSystem::refine(int max_steps, const std::vector<uint8_t>* mask) {
+  const int B = m_opt.batch;
+  if (max_steps < 0) throw std::runtime_error("slpx: refine: max_steps must not be negative");
+  if (mask && static_cast<int>(mask->size()) != B) throw std::runtime_error("slpx: refine: mask length");
+  Refinement out;
+  out.max_steps = max_steps;
+  out.norms.assign(static_cast<size_t>(B) * (max_steps + 1), std::numeric_limits<double>::quiet_NaN());
+  out.accepted.assign(B, 0);
+  std::vector<uint8_t> active = mask ? *mask : std::vector<uint8_t>(B, 1);
+  std::vector<double> norm(B), trial(B);
+  m_dev->residual(active, norm);
+  for (int b = 0; b < B; ++b)
+    if (active[b]) {
+      out.norms[static_cast<size_t>(b) * (max_steps + 1)] = norm[b];
+      // nothing to gain (an exact solution keeps its bits) or nothing to measure a gain against
+      if (norm[b] == 0.0 || !std::isfinite(norm[b])) active[b] = 0;
+    }
+  if (max_steps == 0 || std::none_of(active.begin(), active.end(), [](uint8_t a) { return a != 0; })) return out;
+  m_dev->refine_begin();
+  for (int k = 0; k < max_steps; ++k) {
+    if (std::none_of(active.begin(), active.end(), [](uint8_t a) { return a != 0; })) break;
+    m_dev->refine_solve_correction();
+    m_dev->refine_apply(active);  // the candidates
+    m_dev->residual(active, trial);
+    bool rejected = false;
+    for (int b = 0; b < B; ++b) {
+      if (!active[b]) continue;
+      out.norms[static_cast<size_t>(b) * (max_steps + 1) + k + 1] = trial[b];
+      if (std::isfinite(trial[b]) && trial[b] < norm[b]) {
+        norm[b] = trial[b];
+        ++out.accepted[b];
+        if (trial[b] == 0.0) active[b] = 0;  // (taken; nothing left to refine)
+      } else {
+        active[b] = 0;
+        rejected = true;
+      }
+    }
+    if (rejected) {
+      // p = kept p + d once more for the problems that took the step (the same bits), the kept p for the others
+      std::vector<uint8_t> took(B, 0);
+      for (int b = 0; b < B; ++b) took[b] = out.accepted[b] == k + 1 ? 1 : 0;
+      m_dev->refine_apply(took);
+    }
+    m_dev->refine_keep_solution();
+  }
+  return out;
 }
 
 std::vector<FactorInfo> NewtonSystem::newton_step(bool refresh_ad) {

@@ -146,6 +146,20 @@ class NewtonSystem {
   int last_twin_launches() const { return m_last_twin_launches; }   // step launches of the last compute() that held two attempts
   int last_twin_taken() const { return m_last_twin_taken; }         // ... whose second attempt the policy took
 
+  // Iterative refinement of the solution p in memory on the factors in memory: up to max_steps times, per problem
+  // with mask[b] != 0 (null: all), r = rhs - Kreg p in double-double (DeviceNlp::residual), Kreg d = r through
+  // DeviceNlp::solve() — so every factorization family serves — and p + d is taken only if its residual norm is
+  // finite and smaller; the first step that is not ends that problem's refinement with its p put back.  A problem
+  // whose first norm is 0 takes no step.  p of the other problems and the right-hand side in memory are unchanged on
+  // return.  The system is the one p was solved from: a step that evaluated it in place has it assembled now, AT THE
+  // RESIDENT STATE — refine before the iterate moves.  Throws without a factorization and a solution in memory.
+  struct Refinement {
+    int max_steps = 0;
+    std::vector<double> norms;      // [batch][max_steps + 1]: the norm before, then after every step taken or tried; NaN beyond
+    std::vector<int32_t> accepted;  // [batch]: steps taken
+  };
+  Refinement refine(int max_steps, const std::vector<uint8_t>* mask = nullptr);
+
   // One full Newton step on device-resident state: AD refresh, KKT lhs/rhs,
   // regularized factorization, solve, back-substitution
   // (interior_point.hpp:809-812 + :426-482).
