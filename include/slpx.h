@@ -283,6 +283,24 @@ int slpx_ldlt_refine(slpx_system* s, int32_t max_steps, double* norms, int32_t* 
  * p, and their rows of r, norm_inf, norms and accepted keep what they held.  Additions within ABI version 6. */
 int slpx_ldlt_residual_masked(slpx_system* s, const uint8_t* mask, double* r, double* norm_inf);
 int slpx_ldlt_refine_masked(slpx_system* s, int32_t max_steps, const uint8_t* mask, double* norms, int32_t* accepted);
+/* Error bounds of p on the factors in memory, per problem with mask[b] != 0 (mask NULL: all) — the outputs of
+ * LAPACK's expert drivers (xSYRFS).  berr[batch]: the componentwise backward error max_i |r_i| / (|b| + |K'| |p|)_i
+ * (0 where the denominator is 0), K' = lhs + diag(delta, -gamma) and r as in slpx_ldlt_residual.  ferr[batch]: an
+ * estimate of || |K'^-1| (|r| + rho) ||_inf / ||p||_inf, rho_i a proven bound on the rounding error of the
+ * double-double r_i — it bounds the relative forward error max |p - p*| / max |p| as far as Hager's / Higham's 1-norm
+ * estimator (LAPACK's dlacn2) goes, which is a lower estimate, nearly always within a small factor.  ||p||_inf == 0:
+ * ferr = 0 if |r| + rho is all zero, +inf otherwise.  solves[batch]: the solves each problem's estimate took, at most
+ * 11; all problems share them.  Any output may be NULL; ferr == NULL: no estimator and no solve run.  A non-finite
+ * entry in a problem's system, right-hand side or solution makes that problem's numbers NaN and leaves the others'
+ * bits alone.  p and the right-hand side in memory have the bits on return that they had on entry, for every problem;
+ * rows of the problems left out keep what they held.  When and errors as slpx_ldlt_refine.  Every number of a
+ * problem has the same bits at any batch size, in any slot and under any mask.  An addition within ABI version 6,
+ * detected by the symbol's presence. */
+int slpx_ldlt_error_bounds(slpx_system* s, const uint8_t* mask, double* berr, double* ferr, int32_t* solves);
+/* norm1[batch] = ||K'||_1 and inv_norm1[batch] ~ ||K'^-1||_1 (the same estimator: never above the true norm but for
+ * the rounding of the solves); their product estimates the 1-norm condition number of what was factored.
+ * solves[batch] as above.  Same contract as slpx_ldlt_error_bounds.  An addition within ABI version 6. */
+int slpx_ldlt_condest(slpx_system* s, const uint8_t* mask, double* norm1, double* inv_norm1, int32_t* solves);
 /* AD refresh (optional) + assemble + rhs + compute + solve + backsub */
 int slpx_newton_step(slpx_system* s, int refresh_ad, int32_t* info);
 /* `count` such steps one after the other on the resident state, each waited for like a single

@@ -173,6 +173,9 @@ def lib() -> ctypes.CDLL:
         sig("slpx_ldlt_refine", ctypes.c_int, vp, i32, vp, vp)
         sig("slpx_ldlt_residual_masked", ctypes.c_int, vp, vp, vp, vp)
         sig("slpx_ldlt_refine_masked", ctypes.c_int, vp, i32, vp, vp, vp)
+    if hasattr(L, "slpx_ldlt_error_bounds"):
+        sig("slpx_ldlt_error_bounds", ctypes.c_int, vp, vp, vp, vp, vp)
+        sig("slpx_ldlt_condest", ctypes.c_int, vp, vp, vp, vp, vp)
     _lib = L
     return L
 
@@ -484,6 +487,28 @@ class System:
         m = self._mask(mask, self.batch)
         _check(lib().slpx_ldlt_refine_masked(self._h, int(max_steps), _ptr(m), norms.ctypes.data, accepted.ctypes.data))
         return norms, accepted
+
+    def error_bounds(self, mask=None, forward=True, out=None):
+        """{berr, ferr, solves} of p on the factors in memory (slpx_ldlt_error_bounds), each [batch]: the componentwise
+        backward error, the estimated bound on max |p - p*| / max |p|, and the solves the estimate took (shared by the
+        batch; at most 11).  forward=False: berr alone, no solve (ferr stays NaN).  p and rhs keep their bits.  mask as
+        in residual(): the others' rows keep what `out` = (berr, ferr, solves) held (NaN, NaN, 0 without `out`)."""
+        berr, ferr, solves = ((np.full(self.batch, np.nan), np.full(self.batch, np.nan), np.zeros(self.batch, dtype=np.int32))
+                              if out is None else out)
+        m = self._mask(mask, self.batch)
+        _check(lib().slpx_ldlt_error_bounds(self._h, _ptr(m), berr.ctypes.data, ferr.ctypes.data if forward else None,
+                                            solves.ctypes.data))
+        return {"berr": berr, "ferr": ferr, "solves": solves}
+
+    def condest(self, mask=None, out=None):
+        """{norm1, inv_norm1, cond1, solves} of the matrix the factors in memory are factors of (slpx_ldlt_condest):
+        its 1-norm, the estimated 1-norm of its inverse (a lower estimate), their product, the solves taken.  mask and
+        `out` = (norm1, inv_norm1, solves) as in error_bounds()."""
+        norm1, inv_norm1, solves = ((np.full(self.batch, np.nan), np.full(self.batch, np.nan), np.zeros(self.batch, dtype=np.int32))
+                                    if out is None else out)
+        m = self._mask(mask, self.batch)
+        _check(lib().slpx_ldlt_condest(self._h, _ptr(m), norm1.ctypes.data, inv_norm1.ctypes.data, solves.ctypes.data))
+        return {"norm1": norm1, "inv_norm1": inv_norm1, "cond1": norm1 * inv_norm1, "solves": solves}
 
     def newton_step(self, refresh_ad=True):
         info = np.zeros(self.batch, dtype=np.int32)

@@ -528,6 +528,40 @@ int slpx_ldlt_refine_masked(slpx_system* s, int32_t max_steps, const uint8_t* ma
 int slpx_ldlt_refine(slpx_system* s, int32_t max_steps, double* norms, int32_t* accepted) {
   return slpx_ldlt_refine_masked(s, max_steps, nullptr, norms, accepted);
 }
+int slpx_ldlt_error_bounds(slpx_system* s, const uint8_t* mask, double* berr, double* ferr, int32_t* solves) {
+  return guard([&] {
+    if (slpx_device_count() < 1) throw std::runtime_error("slpx_ldlt_error_bounds: no HIP device");
+    if (s == nullptr) throw std::runtime_error("slpx_ldlt_error_bounds: null system");
+    auto& sys = s->get();
+    const size_t B = sys.batch();
+    std::vector<uint8_t> active;
+    if (mask) active.assign(mask, mask + B);
+    const slpx::NewtonSystem::ErrorBounds res = sys.error_bounds(mask ? &active : nullptr, ferr != nullptr);
+    for (size_t b = 0; b < B; ++b) {
+      if (mask && !active[b]) continue;
+      if (berr) berr[b] = res.berr[b];
+      if (ferr) ferr[b] = res.ferr[b];
+      if (solves) solves[b] = res.solves[b];
+    }
+  });
+}
+int slpx_ldlt_condest(slpx_system* s, const uint8_t* mask, double* norm1, double* inv_norm1, int32_t* solves) {
+  return guard([&] {
+    if (slpx_device_count() < 1) throw std::runtime_error("slpx_ldlt_condest: no HIP device");
+    if (s == nullptr) throw std::runtime_error("slpx_ldlt_condest: null system");
+    auto& sys = s->get();
+    const size_t B = sys.batch();
+    std::vector<uint8_t> active;
+    if (mask) active.assign(mask, mask + B);
+    const slpx::NewtonSystem::Condest res = sys.condest(mask ? &active : nullptr);
+    for (size_t b = 0; b < B; ++b) {
+      if (mask && !active[b]) continue;
+      if (norm1) norm1[b] = res.norm1[b];
+      if (inv_norm1) inv_norm1[b] = res.inv_norm1[b];
+      if (solves) solves[b] = res.solves[b];
+    }
+  });
+}
 int slpx_step_backsub(slpx_system* s) { return guard([&] { s->get().device().backsub(); }); }
 int slpx_newton_step(slpx_system* s, int refresh_ad, int32_t* info) {
   return guard([&] {

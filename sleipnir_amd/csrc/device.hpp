@@ -499,6 +499,28 @@ class DeviceNlp {
   void refine_solve_correction();  // residual -> rhs, solve(), the correction d kept aside, rhs = the kept one again
   void refine_apply(const std::vector<uint8_t>& accept);  // p = kept p + d where accept[b], the kept p elsewhere
   void refine_keep_solution();     // the kept p = p
+  // ---- error bounds of the solution in memory (kkt_errbound.hip; the loops are NewtonSystem::error_bounds / condest) ----
+  // Per problem with mask[b] != 0: norm1 = max row sum of |Kreg|; with want_bounds also berr = max |r_i| / w_i,
+  // p_inf = max |p_i|, f_inf = max f_i, from the r a residual() call left in d_residual(), and w, f = |r| + rho kept
+  // in memory for errbound_round().  The preconditions and the assembly of residual().  Synchronizes.
+  struct ErrRowScalars {
+    double berr = 0.0, norm1 = 0.0, p_inf = 0.0, f_inf = 0.0;
+  };
+  void errbound_rows(const std::vector<uint8_t>& mask, bool want_bounds, std::vector<ErrRowScalars>& out);
+  // One round of the 1-norm estimator for every problem at once: each problem's probe vector (kind: NormEstProbe of
+  // kkt_errbound.h; zeros for kProbeNone) into the right-hand side, solve(), the solution to four scalars.  scale:
+  // 0 plain, 1 the probe times f before the solve, 2 the solution times f after it.  kept: which sign buffer holds the
+  // kept sign vector; sign(v) goes to the other.  OVERWRITES rhs and p: between refine_begin() and errbound_restore().
+  struct EstRound {
+    int32_t kind = 0, j = 0, scale = 0, kept = 0;
+  };
+  struct EstScalars {
+    double norm1 = 0.0;
+    int argmax = 0;
+    bool signs_repeated = false, finite = true;
+  };
+  void errbound_round(const std::vector<EstRound>& rounds, std::vector<EstScalars>& out);
+  void errbound_restore();  // p and rhs = what refine_begin() kept, to the bit
   // (delta, gamma) of the factorization whose factors of problem b are in memory (NaN: none yet)
   std::pair<double, double> factored_regularization(int b) const {
     if (static_cast<size_t>(b) >= m_fact_delta.size()) return {std::numeric_limits<double>::quiet_NaN(), 0.0};
@@ -706,6 +728,14 @@ class DeviceNlp {
   DevBuf<double> m_res, m_ref_keep_p, m_ref_keep_b, m_ref_d, m_res_reg;
   DevBuf<unsigned long long> m_res_partial, m_res_norm;
   DevBuf<uint8_t> m_res_mask;
+  void residual_buffers();
+  // error bounds (kkt_errbound.hip), made on first use: w, f; the workgroups' slots and a problem's scalars ([.][4]);
+  // the two sign buffers ([2][batch][dim]); the commands of a round
+  DevBuf<double> m_eb_w, m_eb_f;
+  DevBuf<unsigned long long> m_eb_partial, m_eb_scal;
+  DevBuf<int8_t> m_eb_sign;
+  DevBuf<int32_t> m_eb_cmd;
+  void errbound_require(const std::vector<uint8_t>& mask, const char* what);
   // what the factors in memory are factors OF, per problem: written wherever a factorization is enqueued
   std::vector<double> m_fact_delta, m_fact_gamma;
   double m_fact_tw[2] = {0.0, 0.0};  // ... of the second attempt of a twin launch (adopt_twin)

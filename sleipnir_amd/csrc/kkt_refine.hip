@@ -80,6 +80,23 @@ __global__ __launch_bounds__(256) void refine_accept_kernel(int dim, const doubl
   p[at] = accept[b] ? keep[at] + d[at] : keep[at];
 }
 
+void DeviceNlp::residual_buffers() {
+  if (m_rm_rowptr.n != 0) return;
+  const int dim = m_kdev.dim, B = m_batch;
+  const int n_part = (dim + kResidualThreads - 1) / kResidualThreads;
+  const KktRowMap map = build_kkt_row_map(m_k_ref.lhs);
+  m_rm_rowptr.upload(map.rowptr);
+  m_rm_ent.upload(map.ent);
+  m_rm_col.upload(map.col);
+  m_res.alloc(static_cast<size_t>(B) * dim);
+  m_res.zero(m_stream);
+  m_res_reg.alloc(2 * static_cast<size_t>(B));
+  m_res_mask.alloc(B);
+  m_res_partial.alloc(static_cast<size_t>(B) * n_part);
+  m_res_norm.alloc(B);
+  m_res_norm.zero(m_stream);
+}
+
 void DeviceNlp::residual(const std::vector<uint8_t>& mask, std::vector<double>& norm) {
   const int dim = m_kdev.dim, nnz = m_kdev.nnz_lhs, B = m_batch;
   if (static_cast<int>(mask.size()) != B) throw std::runtime_error("slpx: residual: mask length");
@@ -88,19 +105,7 @@ void DeviceNlp::residual(const std::vector<uint8_t>& mask, std::vector<double>& 
     if (mask[b] && std::isnan(factored_regularization(b).first))
       throw std::runtime_error("slpx: residual / refine: no factorization in memory (factor and solve first)");
   const int n_part = (dim + kResidualThreads - 1) / kResidualThreads;
-  if (m_rm_rowptr.n == 0) {
-    const KktRowMap map = build_kkt_row_map(m_k_ref.lhs);
-    m_rm_rowptr.upload(map.rowptr);
-    m_rm_ent.upload(map.ent);
-    m_rm_col.upload(map.col);
-    m_res.alloc(static_cast<size_t>(B) * dim);
-    m_res.zero(m_stream);
-    m_res_reg.alloc(2 * static_cast<size_t>(B));
-    m_res_mask.alloc(B);
-    m_res_partial.alloc(static_cast<size_t>(B) * n_part);
-    m_res_norm.alloc(B);
-    m_res_norm.zero(m_stream);
-  }
+  residual_buffers();
   // the system p solves, in batch-major memory: assembled now (at the resident state) if the step evaluated it in
   // place; a system the caller wrote is not stale and stays as given
   materialize_kkt();

@@ -486,6 +486,87 @@ NewtonSystem::Refinement NewtonSystem::refine(int max_steps, const std::vector<u
   return out;
 }
 
+void NewtonSystem::run_norm_estimator(std::vector<NormEstState>& est, bool scale_by_f) {
+  const int B = m_opt.batch;
+  const auto all_done = [&] { return std::all_of(est.begin(), est.end(), [](const NormEstState& e) { return e.done(); }); };
+  if (all_done()) return;
+  std::vector<DeviceNlp::EstRound> rounds(B);
+  std::vector<DeviceNlp::EstScalars> scal;
+  std::vector<int32_t> kept(B, 0);
+  m_dev->refine_begin();  // keeps p and rhs
+  // (every state machine ends within 11 rounds; the bound only guards the loop)
+  for (int k = 0; k < 2 * kNormEstIterations + 2 && !all_done(); ++k) {
+    for (int b = 0; b < B; ++b) {
+      rounds[b].kind = est[b].probe();
+      rounds[b].j = est[b].probe() == kProbeUnit ? est[b].unit_index() : 0;
+      // ||diag(f) Kreg^-1||_1: the product with it scales the solution, the product with its transpose the probe
+      rounds[b].scale = !scale_by_f ? 0 : est[b].transposed() ? 1 : 2;
+      rounds[b].kept = kept[b];
+    }
+    m_dev->errbound_round(rounds, scal);
+    for (int b = 0; b < B; ++b) {
+      if (est[b].done()) continue;
+      if (est[b].advance(scal[b].norm1, scal[b].argmax, scal[b].signs_repeated, scal[b].finite)) kept[b] ^= 1;
+    }
+  }
+  m_dev->errbound_restore();
+}
+
+NewtonSystem::ErrorBounds NewtonSystem::error_bounds(const std::vector<uint8_t>* mask, bool want_ferr) {
+  const int B = m_opt.batch;
+  if (mask && static_cast<int>(mask->size()) != B) throw std::runtime_error("slpx: error_bounds: mask length");
+  const std::vector<uint8_t> active = mask ? *mask : std::vector<uint8_t>(B, 1);
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  ErrorBounds out;
+  out.berr.assign(B, nan);
+  out.ferr.assign(B, nan);
+  out.solves.assign(B, 0);
+  std::vector<double> norm;
+  m_dev->residual(active, norm);
+  std::vector<DeviceNlp::ErrRowScalars> rows;
+  m_dev->errbound_rows(active, /*want_bounds=*/true, rows);
+  for (int b = 0; b < B; ++b)
+    if (active[b]) out.berr[b] = rows[b].berr;
+  if (!want_ferr) return out;
+  std::vector<NormEstState> est(B, NormEstState(m_k.dim));
+  for (int b = 0; b < B; ++b) {
+    if (!active[b]) est[b].finish(nan);
+    // no scale to measure against: 0 if nothing is to be measured, +inf otherwise (a NaN in f stays one)
+    else if (rows[b].p_inf == 0.0) est[b].finish(rows[b].f_inf == 0.0 ? 0.0 : rows[b].f_inf != rows[b].f_inf ? nan : std::numeric_limits<double>::infinity());
+  }
+  run_norm_estimator(est, /*scale_by_f=*/true);
+  for (int b = 0; b < B; ++b) {
+    if (!active[b]) continue;
+    out.ferr[b] = rows[b].p_inf == 0.0 ? est[b].estimate() : est[b].estimate() / rows[b].p_inf;
+    out.solves[b] = est[b].solves();
+  }
+  return out;
+}
+
+NewtonSystem::Condest NewtonSystem::condest(const std::vector<uint8_t>* mask) {
+  const int B = m_opt.batch;
+  if (mask && static_cast<int>(mask->size()) != B) throw std::runtime_error("slpx: condest: mask length");
+  const std::vector<uint8_t> active = mask ? *mask : std::vector<uint8_t>(B, 1);
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  Condest out;
+  out.norm1.assign(B, nan);
+  out.inv_norm1.assign(B, nan);
+  out.solves.assign(B, 0);
+  std::vector<DeviceNlp::ErrRowScalars> rows;
+  m_dev->errbound_rows(active, /*want_bounds=*/false, rows);
+  std::vector<NormEstState> est(B, NormEstState(m_k.dim));
+  for (int b = 0; b < B; ++b)
+    if (!active[b]) est[b].finish(nan);
+  run_norm_estimator(est, /*scale_by_f=*/false);
+  for (int b = 0; b < B; ++b) {
+    if (!active[b]) continue;
+    out.norm1[b] = rows[b].norm1;
+    out.inv_norm1[b] = est[b].estimate();
+    out.solves[b] = est[b].solves();
+  }
+  return out;
+}
+
 std::vector<FactorInfo> NewtonSystem::newton_step(bool refresh_ad) {
   // SLPX_HOST_TIMING=1: where the host's time per step goes (printed every 1000 steps)
   static const bool timing = std::getenv("SLPX_HOST_TIMING") != nullptr;

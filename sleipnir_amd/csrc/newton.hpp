@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "device.hpp"
+#include "kkt_errbound.h"
 #include "kkt_plan.hpp"
 #include "ldlt_policy.hpp"
 #include "ldlt_symbolic.hpp"
@@ -160,6 +161,27 @@ class NewtonSystem {
   };
   Refinement refine(int max_steps, const std::vector<uint8_t>* mask = nullptr);
 
+  // Error bounds of the solution p in memory on the factors in memory (kkt_errbound.h has the definitions), per problem
+  // with mask[b] != 0 (null: all): berr, the componentwise backward error max |r_i| / (|b| + |Kreg| |p|)_i with r in
+  // double-double; with want_ferr also ferr, an estimate of || |Kreg^-1| (|r| + rho) ||_inf / ||p||_inf — a bound on
+  // the relative forward error ||p - p*||_inf / ||p||_inf as far as the estimator goes — by Hager's / Higham's 1-norm
+  // estimator around DeviceNlp::solve(): at most 11 solves, shared by all problems (one that has finished rides along
+  // with a zero right-hand side).  berr alone performs no solve.  p and the right-hand side in memory have the bits on
+  // return that they had on entry, for every problem; the residual in memory (d_residual) is that of p.  The system,
+  // the preconditions and the errors are those of refine().
+  struct ErrorBounds {
+    std::vector<double> berr, ferr;  // [batch]; NaN for the problems left out (ferr also without want_ferr)
+    std::vector<int32_t> solves;     // [batch]: solves this problem took part in before its estimate stood
+  };
+  ErrorBounds error_bounds(const std::vector<uint8_t>* mask = nullptr, bool want_ferr = true);
+  // norm1 = ||Kreg||_1 (exact but for the rounding of a row sum) and inv_norm1 ~ ||Kreg^-1||_1, a LOWER estimate by the
+  // same estimator; their product estimates the 1-norm condition number.  Same contract as error_bounds().
+  struct Condest {
+    std::vector<double> norm1, inv_norm1;
+    std::vector<int32_t> solves;
+  };
+  Condest condest(const std::vector<uint8_t>* mask = nullptr);
+
   // One full Newton step on device-resident state: AD refresh, KKT lhs/rhs,
   // regularized factorization, solve, back-substitution
   // (interior_point.hpp:809-812 + :426-482).
@@ -183,6 +205,9 @@ class NewtonSystem {
   bool m_hooked_chain_valid = false;  // compute_hooked: `after` ran behind the attempt that was accepted
   long m_twin_hist[6] = {0, 0, 0, 0, 0, 0};
   int m_twin_expect = kLdltTooManyNegative;  // what the loop's first launch drew last time (compute_twin): negative pivots or positive
+  // the estimator's rounds for the problems whose state machine is not done; scale_by_f: the operator is
+  // diag(f) Kreg^-1 (ferr), else Kreg^-1 (condest)
+  void run_norm_estimator(std::vector<NormEstState>& est, bool scale_by_f);
   // the policy state of problem b from its memory, and the memory from a state that is done
   LdltPolicy start_policy(int b, bool skip_first) const;
   FactorInfo remember(int b, const LdltPolicy& p);
