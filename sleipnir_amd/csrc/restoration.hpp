@@ -108,6 +108,21 @@ class FrDevice {
   // [p_e | n_e | p_i | n_i], their slacks, their duals -> host
   void download_state(double* pn, double* sx, double* zx);
   void download_direction(double* dpn, double* psx, double* pzx);
+  // read-only views of the device buffers (tests/support/frcheck.cpp compares them kernel by kernel): the restoration
+  // iterate [p_e | n_e | p_i | n_i] with its slacks and duals, its direction, its look-ahead twin, the second-order-
+  // correction accumulators (c_e', block 0 of c_i' - s', the bound rows), the kept direction, the step sizes
+  struct View {
+    const double *pn, *sx, *zx, *dpn, *psx, *pzx, *pn_ahead, *sx_ahead, *zx_ahead;
+    const double *soc_ce, *soc_c0, *soc_x;
+    const double *keep_p, *keep_ps0, *keep_pz0, *keep_dpn, *keep_psx, *keep_pzx;
+    const double* alpha;  // alpha_max, alpha_z, D_phi, eliminated_min_pivot of the last expand()
+    size_t second_lhs_count, second_rhs_count;
+  };
+  View view() const {
+    return View{m_pn.p,     m_sx.p,     m_zx.p,     m_dpn.p,      m_psx.p,      m_pzx.p,      m_pn_t.p,     m_sx_t.p,     m_zx_t.p,  m_soc_ce.p,
+                m_soc_c0.p, m_soc_x.p,  m_keep_p.p, m_keep_ps0.p, m_keep_pz0.p, m_keep_dpn.p, m_keep_psx.p, m_keep_pzx.p, m_alpha.p, m_lhs2.n,
+                m_rhs2.n};
+  }
 
   struct Args;  // the kernels' view (restoration.hip)
 

@@ -39,6 +39,41 @@ def test_restoration_steps_match_oracle(fresh, slpx, orc, N, steps):
     pp.close()
 
 
+@pytest.mark.parametrize("name", ["tiny", "ineq_only", "chain300"])
+@pytest.mark.parametrize("steps", [1, 2])
+def test_restoration_steps_match_oracle_on_general_models(fresh, slpx, orc, name, steps):
+    """The same comparison on models whose inequality rows have two or three entries and whose equality and inequality
+    Jacobians share a hub column of more than twenty entries (tests/support/fr_models.py), from the mild outer state.
+    The agreement asked is the oracle's own sensitivity — its result from x perturbed by 1e-15 relative against its
+    unperturbed one, computed here — times 10, floored at the 1e-10 (x, s) and 1e-8 (y, z) of the test above.
+    Measured when this was written (steps 1 / 2): tiny x 4.4e-16 / 1.1e-15, s 0 / 1.9e-15, y 8.9e-16 / 8.3e-17,
+    z 1.1e-16 / 1.3e-16; ineq_only x 3.0e-14 / 1.6e-14, s 2.3e-14 / 4.4e-14, z 1.8e-13 / 1.0e-13; chain300 x 1.0e-15 /
+    3.1e-15, s 2.5e-16 / 4.6e-16, y 1.5e-14 / 8.9e-15, z 1.1e-14 / 8.6e-15 — the floors are what holds."""
+    from tests.support import fr_models, model
+
+    pp_, start = fr_models.make(model.Model(model.ProductBackend("gpu")), name)
+    op_, _ = fr_models.make(model.Model(model.OracleBackend()), name)
+    pp, op = pp_.p, op_.p
+    n, me, mi = pp.dims
+    assert (n, me, mi) == op.dims
+    scales = op.scaling()
+    x, s, y, z, mu = cases.newton_state("interior", start, n, me, mi, scales[0])
+    so, xo, s_o, yo, zo = op.restoration_steps(x, s, y, z, mu, steps)
+    x_pert = x * (1.0 + 1e-15 * np.random.default_rng(cases.SEED).uniform(-1, 1, n))
+    sq, xq, s_q, yq, zq = op.restoration_steps(x_pert, s, y, z, mu, steps)
+    sens = {k: cases.max_rel(a, b) for k, a, b in (("x", xq, xo), ("s", s_q, s_o), ("y", yq, yo), ("z", zq, zo))}
+    sp, xp, s_p, yp, zp = pp.restoration_steps(x, s, y, z, mu, steps)
+    assert sp == so == sq == 0
+    assert not np.allclose(xo, x, rtol=0, atol=1e-6)  # the restoration moved the iterate
+    errs = {k: cases.max_rel(a, b) for k, a, b in (("x", xp, xo), ("s", s_p, s_o), ("y", yp, yo), ("z", zp, zo))}
+    tol = {k: max(10.0 * sens[k], 1e-10 if k in "xs" else 1e-8) for k in sens}
+    print(f"{name} steps={steps}: product vs oracle", {k: f"{v:.2e}" for k, v in errs.items()},
+          "oracle's own sensitivity", {k: f"{v:.2e}" for k, v in sens.items()})
+    for k in errs:
+        assert errs[k] <= tol[k], (k, errs, tol)
+    pp.close()
+
+
 @pytest.mark.parametrize("N", [50, 100])
 def test_trajectory_tracks_oracle_at_the_start(fresh, slpx, orc, N):
     pp, op = cases.build_pair("cart_pole", N, slpx, orc)
