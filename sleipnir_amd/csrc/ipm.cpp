@@ -1,5 +1,6 @@
 #include "ipm.hpp"
 
+#include "ipm_formulas.h"
 #include "ipm_line_search.hpp"
 #include "restoration.hpp"
 
@@ -207,16 +208,13 @@ ExitStatus ipm_core_host(NewtonSystem& sys, const Vec& scales,
           c_e_soc = c_e;
           for (int j = 0; j < m_i; ++j) cims_soc[j] = c_i[j] - s[j];
         }
-        for (int j = 0; j < m_e; ++j) c_e_soc[j] = ls.alpha_soc * c_e_soc[j] + trial_c_e[j];
-        for (int j = 0; j < m_i; ++j) cims_soc[j] = ls.alpha_soc * cims_soc[j] + trial_c_i[j] - trial_s[j];
+        for (int j = 0; j < m_e; ++j) c_e_soc[j] = soc_accumulate(ls.alpha_soc, c_e_soc[j], trial_c_e[j]);
+        for (int j = 0; j < m_i; ++j) cims_soc[j] = soc_accumulate(ls.alpha_soc, cims_soc[j], trial_c_i[j]) - trial_s[j];
         // rhs (:613-616) is O(nnz(A)) host work on the downloaded Jacobians
         Vec rhs(dim, 0.0);
         {
           Vec t(m_i);
-          for (int j = 0; j < m_i; ++j) {
-            const double sinv = 1.0 / s[j];
-            t[j] = mu * sinv - (sinv * z[j]) * cims_soc[j];
-          }
+          for (int j = 0; j < m_i; ++j) t[j] = soc_rhs_multiplier(mu, s[j], z[j], cims_soc[j]);
           for (int i = 0; i < n; ++i) rhs[i] = -g[i];
           add_At_v(st.Ae, cur.Ae(), nullptr, y.data(), 1.0, rhs);
           add_At_v(st.Ai, cur.Ai(), nullptr, t.data(), 1.0, rhs);
@@ -237,7 +235,7 @@ ExitStatus ipm_core_host(NewtonSystem& sys, const Vec& scales,
           for (int j = 0; j < m_i; ++j) {
             const double sinv = 1.0 / s[j];
             soc_ps[j] = cims_soc[j] + aipx[j];
-            soc_pz[j] = mu * sinv - z[j] - (sinv * z[j]) * soc_ps[j];
+            soc_pz[j] = backsub_pz_sinv(mu, sinv, z[j], soc_ps[j]);
           }
         }
         ls.on_soc_solve(ftb(s, soc_ps, tau), ftb(z, soc_pz, tau));
@@ -295,8 +293,7 @@ ExitStatus ipm_core_host(NewtonSystem& sys, const Vec& scales,
       s = trial_s;
       y = trial_y;
       z = trial_z;
-      for (int j = 0; j < m_i; ++j)  // :797-801
-        z[j] = std::clamp(z[j], 1.0 / kKappa * mu / s[j], kKappa * mu / s[j]);
+      for (int j = 0; j < m_i; ++j) z[j] = z_reset(z[j], mu, s[j]);  // :797-801
     }
     f = trial_f;
     c_e = trial_c_e;
@@ -804,8 +801,7 @@ bool lagrange_multiplier_estimate(NewtonSystem& sys, const Vec& V, const Vec& s,
     for (int q = st.Ai.colptr[c]; q < st.Ai.colptr[c + 1]; ++q) aid[st.Ai.rowidx[q]] += cur.Ai()[q] * p[c];
   z.assign(m_i, 0.0);
   for (int j = 0; j < m_i; ++j) {
-    const double zj = mu / s[j] - aid[j] / (s[j] * s[j]);
-    z[j] = std::clamp(zj, 1.0 / kKappa * mu / s[j], kKappa * mu / s[j]);  // :125-130
+    z[j] = z_reset(mu / s[j] - aid[j] / (s[j] * s[j]), mu, s[j]);  // :125-130
   }
   return true;
 }

@@ -4,6 +4,7 @@
 // model's sizes alone (strided per-thread partials, then block_reduce: wave64 butterflies and a fixed combination of
 // the waves), so an instance's scalars do not depend on B or on which other instances are active.  The iterate, the
 // direction and the trial point stay on the device; the host reads a few scalars per instance and decides.
+// The per-row formulas are the bodies of ipm_formulas.h — the ones the single solve's kernels and the host run.
 //
 // Per-instance problem scaling: the batch system's tape runs with unit scales; the dual inputs are multiplied by the
 // instance's d_ce, d_ci before a sweep (batch_load_state_kernel), and what the sweep wrote is multiplied by the scale
@@ -15,6 +16,7 @@
 #include "device.hpp"
 #include "ipm_batch.hpp"
 #include "ipm_decide.h"
+#include "ipm_formulas.h"
 #include "ipm_reduce.h"
 
 namespace slpx {
@@ -97,8 +99,8 @@ __global__ __launch_bounds__(kBatchThreads) void batch_direction_kernel(
   double logbar = 0.0;
   for (int r = tid; r < m_i; r += kBatchThreads) {
     const double sr = s[r], psr = ps[r], zr = z[r], pzr = pz[r];
-    if (psr < 0.0) acc[0] = fmin(acc[0], -tau_b / psr * sr);
-    if (pzr < 0.0) acc[1] = fmin(acc[1], -tau_b / pzr * zr);
+    acc[0] = ftb_candidate(acc[0], tau_b, psr, sr);
+    acc[1] = ftb_candidate(acc[1], tau_b, pzr, zr);
     logbar += (1.0 / sr) * psr;
   }
   for (int j = tid; j < n; j += kBatchThreads) {
@@ -333,16 +335,15 @@ __global__ __launch_bounds__(kBatchThreads) void batch_soc_rhs_kernel(KktDev K, 
   double* rhs = A.rhs + static_cast<size_t>(b) * K.dim;
   for (int j = tid; j < m_e; j += kBatchThreads) {
     const double prev = first ? V[K.off_ce + j] : A.sce[be + j];
-    const double c = as * prev + A.tce[be + j];
+    const double c = soc_accumulate(as, prev, A.tce[be + j]);
     A.sce[be + j] = c;
     rhs[n + j] = -c;
   }
   for (int j = tid; j < m_i; j += kBatchThreads) {
     const double prev = first ? V[K.off_ci + j] - A.cur.s[bi + j] : A.scims[bi + j];
-    const double c = as * prev + A.tci[bi + j] - A.ts[bi + j];
+    const double c = soc_accumulate(as, prev, A.tci[bi + j]) - A.ts[bi + j];
     A.scims[bi + j] = c;
-    const double sinv = 1.0 / A.cur.s[bi + j];
-    A.t[bi + j] = mu_b * sinv - (sinv * A.cur.z[bi + j]) * c;
+    A.t[bi + j] = soc_rhs_multiplier(mu_b, A.cur.s[bi + j], A.cur.z[bi + j], c);
   }
   __syncthreads();  // (t, written above by this workgroup, is read below)
   const double* Ae = V + K.off_Ae;
@@ -384,11 +385,11 @@ __global__ __launch_bounds__(kBatchThreads) void batch_soc_direction_kernel(
     for (int q = K.ai_rowptr[r]; q < K.ai_rowptr[r + 1]; ++q) aipx += V[K.ai_src[q]] * p[K.ai_col[q]];
     const double sr = cur.s[bi + r], zr = cur.z[bi + r], sinv = 1.0 / sr;
     const double ps = scims[bi + r] + aipx;
-    const double pz = mu_b * sinv - zr - (sinv * zr) * ps;
+    const double pz = backsub_pz_sinv(mu_b, sinv, zr, ps);
     soc.s[bi + r] = ps;
     soc.z[bi + r] = pz;
-    if (ps < 0.0) acc[0] = fmin(acc[0], -tau_b / ps * sr);
-    if (pz < 0.0) acc[1] = fmin(acc[1], -tau_b / pz * zr);
+    acc[0] = ftb_candidate(acc[0], tau_b, ps, sr);
+    acc[1] = ftb_candidate(acc[1], tau_b, pz, zr);
   }
   const int ops[2] = {IPM_MIN, IPM_MIN};
   block_reduce<2, kBatchThreads>(acc, ops, scratch);
@@ -398,7 +399,7 @@ __global__ __launch_bounds__(kBatchThreads) void batch_soc_direction_kernel(
   }
 }
 
-// Commit (interior_point.hpp:773-801): the trial point becomes the iterate, z clamped to [mu / (kappa s), kappa mu / s].
+// Commit (interior_point.hpp:773-801): the trial point becomes the iterate, with the z reset (z_reset: a NaN stays).
 // grid (B).
 __global__ __launch_bounds__(kBatchThreads) void batch_commit_kernel(KktDev K, BatchIter trial, BatchIter cur,
                                                                      const double* __restrict__ mu,
@@ -408,13 +409,12 @@ __global__ __launch_bounds__(kBatchThreads) void batch_commit_kernel(KktDev K, B
   const int n = K.n, m_e = K.m_e, m_i = K.m_i;
   const size_t bx = static_cast<size_t>(b) * n, be = static_cast<size_t>(b) * m_e, bi = static_cast<size_t>(b) * m_i;
   const double mu_b = mu[b];
-  constexpr double kappa = 1e10;
   for (int i = threadIdx.x; i < n; i += kBatchThreads) cur.x[bx + i] = trial.x[bx + i];
   for (int j = threadIdx.x; j < m_e; j += kBatchThreads) cur.y[be + j] = trial.y[be + j];
   for (int j = threadIdx.x; j < m_i; j += kBatchThreads) {
     const double s = trial.s[bi + j];
     cur.s[bi + j] = s;
-    cur.z[bi + j] = fmin(fmax(trial.z[bi + j], 1.0 / kappa * mu_b / s), kappa * mu_b / s);
+    cur.z[bi + j] = z_reset(trial.z[bi + j], mu_b, s);
   }
 }
 

@@ -10,6 +10,7 @@
 // z reset), util/fraction_to_the_boundary_rule.hpp:19-43, util/filter.hpp:30-60 (entry =
 // f − μ Σ ln s, ‖c_e‖₁ + ‖c_i − s‖₁), util/kkt_error.hpp:92-146 and :216-251 (un-scaling),
 // util/is_locally_infeasible.hpp:17-60, interior_point.hpp:399-407 (divergence).
+// The per-row formulas among them are the bodies of ipm_formulas.h; the sums' tree is ipm_reduce.h's.
 //
 // The reductions are latency-, not bandwidth-bound (n is a few thousand to a few ten
 // thousand): wave totals by DPP butterflies + scalar lane reads (no LDS traffic), a fixed
@@ -22,6 +23,7 @@
 #include "coherent.h"
 #include "device.hpp"
 #include "ipm_decide.h"
+#include "ipm_formulas.h"
 #include "ipm_reduce.h"
 
 namespace slpx {
@@ -40,8 +42,8 @@ __global__ __launch_bounds__(kIpmThreads) void ipm_direction_kernel(
   double acc[3] = {1.0, 1.0, 0.0};  // alpha_max, alpha_z, D_phi
   for (int r = tid; r < K.m_i; r += kIpmThreads) {
     const double sr = s[r], psr = ps[r], zr = z[r], pzr = pz[r];
-    if (psr < 0.0) acc[0] = fmin(acc[0], -tau / psr * sr);
-    if (pzr < 0.0) acc[1] = fmin(acc[1], -tau / pzr * zr);
+    acc[0] = ftb_candidate(acc[0], tau, psr, sr);
+    acc[1] = ftb_candidate(acc[1], tau, pzr, zr);
     acc[2] -= mu * ((1.0 / sr) * psr);
   }
   for (int j = tid; j < K.n; j += kIpmThreads) {
@@ -131,8 +133,8 @@ __device__ __forceinline__ void ipm_lookahead_body(IpmLookaheadArgs A, double* s
 #pragma unroll
     for (int k = 0; k < kPre; ++k)
       if (tid + k * THREADS < m_i) {
-        if (pss[k] < 0.0) acc[0] = fmin(acc[0], -tau / pss[k] * ss[k]);
-        if (pzs[k] < 0.0) acc[1] = fmin(acc[1], -tau / pzs[k] * zs[k]);
+        acc[0] = ftb_candidate(acc[0], tau, pss[k], ss[k]);
+        acc[1] = ftb_candidate(acc[1], tau, pzs[k], zs[k]);
         acc[2] -= mu * ((1.0 / ss[k]) * pss[k]);
       }
 #pragma unroll
@@ -152,10 +154,7 @@ __device__ __forceinline__ void ipm_lookahead_body(IpmLookaheadArgs A, double* s
       }
       if (j < m_i) {
         const double sn = ss[k] + alpha * pss[k];
-        double zn = zs[k] + alpha_z * pzs[k];
-        constexpr double kappa = 1e10;
-        const double lo = 1.0 / kappa * mu / sn, hi = kappa * mu / sn;
-        zn = zn < lo ? lo : (zn > hi ? hi : zn);
+        const double zn = z_reset(zs[k] + alpha_z * pzs[k], mu, sn);
         s_t[j] = sn;
         z_t[j] = zn;
         in_t[n + m_e + j] = zn;
@@ -164,8 +163,8 @@ __device__ __forceinline__ void ipm_lookahead_body(IpmLookaheadArgs A, double* s
   } else {
     for (int r = tid; r < m_i; r += THREADS) {
       const double sr = s[r], psr = ld(ps + r), zr = z[r], pzr = ld(pz + r);
-      if (psr < 0.0) acc[0] = fmin(acc[0], -tau / psr * sr);
-      if (pzr < 0.0) acc[1] = fmin(acc[1], -tau / pzr * zr);
+      acc[0] = ftb_candidate(acc[0], tau, psr, sr);
+      acc[1] = ftb_candidate(acc[1], tau, pzr, zr);
       acc[2] -= mu * ((1.0 / sr) * psr);
     }
     for (int j = tid; j < n; j += THREADS) {
@@ -183,10 +182,7 @@ __device__ __forceinline__ void ipm_lookahead_body(IpmLookaheadArgs A, double* s
     }
     for (int r = tid; r < m_i; r += THREADS) {
       const double sn = s[r] + alpha * ld(ps + r);
-      double zn = z[r] + alpha_z * ld(pz + r);
-      constexpr double kappa = 1e10;
-      const double lo = 1.0 / kappa * mu / sn, hi = kappa * mu / sn;
-      zn = zn < lo ? lo : (zn > hi ? hi : zn);
+      const double zn = z_reset(z[r] + alpha_z * ld(pz + r), mu, sn);
       s_t[r] = sn;
       z_t[r] = zn;
       in_t[n + m_e + r] = zn;
@@ -219,8 +215,8 @@ __global__ __launch_bounds__(256) void ipm_trial_point_kernel(int n, const doubl
 // alpha < 0: take the step size from alpha_dev[0].  s_from_ci: trial_s = trial c_i
 // (feasible-IPM option, interior_point.hpp:520-526).
 // The separable sums the forward sweep left as partial terms (the cost: one term per stage
-// group) are finished here, in the order tape_reduce_body uses (same bits), instead of by a
-// launch of their own between the sweep and this kernel.
+// group) are finished here (separable_sum_tree) instead of by a launch of their own between
+// the sweep and this kernel.
 __global__ __launch_bounds__(kIpmThreads) void ipm_trial_metrics_kernel(
     KktDev K, double* __restrict__ Vt, const double* __restrict__ s, const double* __restrict__ ps,
     double alpha, const double* __restrict__ alpha_dev, int s_from_ci, IpmTrialOut* __restrict__ out,
@@ -231,17 +227,8 @@ __global__ __launch_bounds__(kIpmThreads) void ipm_trial_metrics_kernel(
   const int tid = threadIdx.x;
   for (int q = 0; q < n_red; ++q) {
     const NlpStructure::SumReduce r = red[q];
-    if (tid < 64) {
-      double acc = 0.0;
-      for (int k = tid; k < r.count; k += 64) acc += Vt[r.src_off + k];
-      part[tid] = acc;
-    }
-    __syncthreads();
-    for (int w = 32; w > 0; w >>= 1) {
-      if (tid < w) part[tid] += part[tid + w];
-      __syncthreads();
-    }
-    if (tid == 0) Vt[r.dst] = (r.scale_idx >= 0 ? scales[r.scale_idx] : 1.0) * part[0];
+    separable_sum_tree(Vt, r, part, tid);
+    if (tid == 0) Vt[r.dst] = separable_sum_scale(r, scales) * part[0];
     __syncthreads();
   }
   if (alpha < 0.0) alpha = alpha_dev[0];
@@ -292,10 +279,7 @@ __global__ __launch_bounds__(256) void ipm_commit_kernel(KktDev K, const double*
   }
   for (int r = t0; r < K.m_i; r += stride) {
     const double sn = s_from_ci ? Vt[K.off_ci + r] : s[r] + alpha * ps[r];
-    double zn = z[r] + alpha_z * pz[r];
-    constexpr double kappa = 1e10;
-    const double lo = 1.0 / kappa * mu / sn, hi = kappa * mu / sn;
-    zn = zn < lo ? lo : (zn > hi ? hi : zn);
+    const double zn = z_reset(z[r] + alpha_z * pz[r], mu, sn);
     s[r] = sn;
     z[r] = zn;
     in[K.n + K.m_e + r] = zn;
@@ -331,13 +315,13 @@ __global__ __launch_bounds__(256) void ipm_soc_accumulate_kernel(KktDev K, const
   const int t0 = blockIdx.x * blockDim.x + threadIdx.x;
   for (int r = t0; r < K.m_e; r += stride) {
     const double prev = first ? V[K.off_ce + r] : soc_ce[r];
-    soc_ce[r] = alpha * prev + Vt[K.off_ce + r];
+    soc_ce[r] = soc_accumulate(alpha, prev, Vt[K.off_ce + r]);
   }
   for (int r = t0; r < K.m_i; r += stride) {
     const double prev = first ? V[K.off_ci + r] - s[r] : soc_cims[r];
     const double ct = Vt[K.off_ci + r];
     const double st = s_from_ci ? ct : s[r] + alpha * ps[r];
-    soc_cims[r] = alpha * prev + ct - st;
+    soc_cims[r] = soc_accumulate(alpha, prev, ct) - st;
   }
 }
 
@@ -367,8 +351,7 @@ __global__ __launch_bounds__(256) void ipm_soc_rhs_kernel(KktDev K, const double
     double ait = 0.0;
     for (int q = K.ai_colptr[j]; q < K.ai_colptr[j + 1]; ++q) {
       const int r = K.ai_rowidx[q];
-      const double sinv = 1.0 / s[r];
-      ait += Ai[q] * (m * sinv - (sinv * z[r]) * soc_cims[r]);
+      ait += Ai[q] * soc_rhs_multiplier(m, s[r], z[r], soc_cims[r]);
     }
     rhs[j] = acc + ait;
   }
@@ -390,7 +373,7 @@ __global__ __launch_bounds__(256) void ipm_soc_backsub_kernel(KktDev K, const do
     const double sinv = 1.0 / s[r];
     const double p_s = soc_cims[r] + aipx;
     ps[r] = p_s;
-    pz[r] = m * sinv - z[r] - (sinv * z[r]) * p_s;
+    pz[r] = backsub_pz_sinv(m, sinv, z[r], p_s);
   }
 }
 
@@ -754,6 +737,7 @@ __device__ __forceinline__ void ipm_error_block(const KktDev& K, const double* _
   if (fin.n_err_blocks != 0 && block >= fin.n_err_blocks) {
     const NlpStructure::SumReduce r = fin.red[block - fin.n_err_blocks];
     const int tid = threadIdx.x;
+    // restates separable_sum_tree (ipm_reduce.h): through the shared body the riding twin kernel's instructions change
     double* scratch = tr;
     double acc = 0.0;
     if (tid < 64)

@@ -24,7 +24,6 @@ constexpr double kTauMin = 0.99;         // fraction to the boundary
 constexpr double kKappaSoc = 0.99;       // a correction round must take 1 % off the violation to be followed by another
 constexpr int kMaxCorrections = 5;
 constexpr double kFallbackDecrease = 0.999;  // the KKT-error fallback's test on the full step
-constexpr double kKappa = 1e10;          // z stays within [mu / (kappa s), kappa mu / s] (:797-801)
 
 class LineSearch {
  public:

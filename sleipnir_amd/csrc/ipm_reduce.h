@@ -1,6 +1,7 @@
 // Reduction helpers of the interior-point iteration kernels (ipm_kernels.h, restoration.hip): wave totals by DPP
 // butterflies + scalar lane reads (no LDS traffic), workgroup totals through a few LDS words, a fixed combination
-// order (reproducible run to run), and the sequence number a chain of launches hands the host at its end.
+// order (reproducible run to run), the one tree that finishes the tape's separable sums, and the sequence number a
+// chain of launches hands the host at its end.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -74,6 +75,25 @@ __device__ __forceinline__ void block_reduce(double (&vals)[NQ], const int (&ops
 #pragma unroll
   for (int q = 0; q < NQ; ++q) vals[q] = scratch[kWaves * NQ + q];
   __syncthreads();
+}
+
+// The tape's separable sums (nlp.cpp), which make f.  The ORDER IS A CONTRACT: a strided partial per lane of one wave,
+// then a pairwise tree over `part` (64 doubles of LDS).  EVERY lane of the workgroup calls; lanes >= 64 only keep the
+// barriers company.  Afterwards lane 0 may read part[0] and stores separable_sum_scale(r, scales) * part[0] its own way.
+__device__ __forceinline__ void separable_sum_tree(const double* V, const NlpStructure::SumReduce& r, double* part, int tid) {
+  if (tid < 64) {
+    double acc = 0.0;
+    for (int k = tid; k < r.count; k += 64) acc += V[r.src_off + k];
+    part[tid] = acc;
+  }
+  __syncthreads();
+  for (int w = 32; w > 0; w >>= 1) {
+    if (tid < w) part[tid] += part[tid + w];
+    __syncthreads();
+  }
+}
+__device__ __forceinline__ double separable_sum_scale(const NlpStructure::SumReduce& r, const double* scales) {
+  return r.scale_idx >= 0 ? scales[r.scale_idx] : 1.0;
 }
 
 // Last act of a chain of launches whose results sit in pinned host memory: bump the

@@ -289,20 +289,10 @@ __global__ __launch_bounds__(256) void kkt_build_kernel(KktDev K, double* __rest
     kkt_rhs_body(K, V, s, y + static_cast<size_t>(b) * K.m_e, z, mu[b], rhs + static_cast<size_t>(b) * K.dim,
                  blk - na, nr);
   } else {
-    // tape_reduce_body wants a 64-lane workgroup: the first wave does it, the others idle
-    // at its barriers
     const NlpStructure::SumReduce r = red[blk - na - nr];
     const int tid = threadIdx.x;
-    double acc = 0.0;
-    if (tid < 64)
-      for (int k = tid; k < r.count; k += 64) acc += V[r.src_off + k];
-    if (tid < 64) part[tid] = acc;
-    __syncthreads();
-    for (int w = 32; w > 0; w >>= 1) {
-      if (tid < w) part[tid] += part[tid + w];
-      __syncthreads();
-    }
-    if (tid == 0) V[r.dst] = (r.scale_idx >= 0 ? scales[r.scale_idx] : 1.0) * part[0];
+    separable_sum_tree(V, r, part, tid);
+    if (tid == 0) V[r.dst] = separable_sum_scale(r, scales) * part[0];
   }
 }
 

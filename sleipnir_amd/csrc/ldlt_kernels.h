@@ -370,6 +370,7 @@ __device__ __forceinline__ void ride_along_sum(const KktFuse& F, uint32_t which,
   const int tid = threadIdx.x;
   double* part = reinterpret_cast<double*>(smem_raw);
   const NlpStructure::SumReduce r = F.red[which];
+  // restates separable_sum_tree (ipm_reduce.h): through the shared body the step kernels' instructions change
   double acc = 0.0;
   if (tid < 64) {
     for (int k = tid; k < r.count; k += 64) acc += F.V[r.src_off + k];

@@ -11,6 +11,7 @@
 #include <stdexcept>
 
 #include "coherent.h"
+#include "ipm_formulas.h"
 #include "ipm_reduce.h"
 
 namespace slpx {
@@ -218,8 +219,8 @@ __global__ __launch_bounds__(kFrExpandThreads) void fr_expand_kernel(FrDevice::A
   const int stride = gridDim.x * kFrExpandThreads, t0 = blockIdx.x * kFrExpandThreads + threadIdx.x;
   double acc[4] = {1.0, 1.0, 0.0, 1e300};  // alpha_max, alpha_z, D_phi, smallest eliminated pivot
   auto ftb = [&](double s, double ps, double z, double pz) {
-    if (ps < 0.0) acc[0] = fmin(acc[0], -tau / ps * s);
-    if (pz < 0.0) acc[1] = fmin(acc[1], -tau / pz * z);
+    acc[0] = ftb_candidate(acc[0], tau, ps, s);
+    acc[1] = ftb_candidate(acc[1], tau, pz, z);
   };
   for (int j = t0; j < me; j += stride) {
     const FrEq e = fr_eq_row(A, j, mu, soc != 0);
@@ -311,16 +312,11 @@ __global__ __launch_bounds__(kFrExpandThreads) void fr_expand_kernel(FrDevice::A
   const double alpha = coherent_load(&alpha_dev[0], true), alpha_z = coherent_load(&alpha_dev[1], true);
   for (int j = t0; j < n; j += stride) A.trial_in[j] = A.in[j] + alpha * A.p[j];
   if (ahead) {  // interior_point.hpp:775-801 for the full step, into the look-ahead buffers: every lane the rows it expanded
-    constexpr double kappa = 1e10;
-    auto clamp_z = [&](double zn, double sn) {
-      const double lo = 1.0 / kappa * mu / sn, hi = kappa * mu / sn;
-      return zn < lo ? lo : (zn > hi ? hi : zn);
-    };
     auto bound_row = [&](int e) {
       A.pn_t[e] = A.pn[e] + alpha * A.dpn[e];
       const double sn = A.sx[e] + alpha * A.psx[e];
       A.sx_t[e] = sn;
-      A.zx_t[e] = clamp_z(A.zx[e] + alpha_z * A.pzx[e], sn);
+      A.zx_t[e] = z_reset(A.zx[e] + alpha_z * A.pzx[e], mu, sn);
     };
     for (int j = t0; j < me; j += stride) {
       const double v = A.y[j] + alpha_z * (-A.p[n + j]);
@@ -331,7 +327,7 @@ __global__ __launch_bounds__(kFrExpandThreads) void fr_expand_kernel(FrDevice::A
     }
     for (int r = t0; r < mi; r += stride) {
       const double sn = A.s0[r] + alpha * A.ps0[r];
-      const double zn = clamp_z(A.z0[r] + alpha_z * A.pz0[r], sn);
+      const double zn = z_reset(A.z0[r] + alpha_z * A.pz0[r], mu, sn);
       A.s0_t[r] = sn;
       A.z0_t[r] = zn;
       A.trial_in[n + me + r] = zn;
@@ -402,11 +398,6 @@ __global__ __launch_bounds__(256) void fr_trial_point_kernel(int n, const double
 __global__ __launch_bounds__(256) void fr_commit_kernel(FrDevice::Args A, double alpha, double alpha_z, double mu) {
   const int stride = gridDim.x * blockDim.x, t0 = blockIdx.x * blockDim.x + threadIdx.x;
   const int n = A.n, me = A.m_e, mi = A.m_i, M = 2 * me + 2 * mi;
-  constexpr double kappa = 1e10;
-  auto clamp_z = [&](double zn, double sn) {
-    const double lo = 1.0 / kappa * mu / sn, hi = kappa * mu / sn;
-    return zn < lo ? lo : (zn > hi ? hi : zn);
-  };
   for (int j = t0; j < n; j += stride) A.in[j] = A.in[j] + alpha * A.p[j];
   for (int r = t0; r < me; r += stride) {
     const double v = A.y[r] + alpha_z * (-A.p[n + r]);
@@ -415,7 +406,7 @@ __global__ __launch_bounds__(256) void fr_commit_kernel(FrDevice::Args A, double
   }
   for (int r = t0; r < mi; r += stride) {
     const double sn = A.s0[r] + alpha * A.ps0[r];
-    const double zn = clamp_z(A.z0[r] + alpha_z * A.pz0[r], sn);
+    const double zn = z_reset(A.z0[r] + alpha_z * A.pz0[r], mu, sn);
     A.s0[r] = sn;
     A.z0[r] = zn;
     A.in[n + me + r] = zn;
@@ -424,7 +415,7 @@ __global__ __launch_bounds__(256) void fr_commit_kernel(FrDevice::Args A, double
     A.pn[e] = A.pn[e] + alpha * A.dpn[e];
     const double sn = A.sx[e] + alpha * A.psx[e];
     A.sx[e] = sn;
-    A.zx[e] = clamp_z(A.zx[e] + alpha_z * A.pzx[e], sn);
+    A.zx[e] = z_reset(A.zx[e] + alpha_z * A.pzx[e], mu, sn);
   }
 }
 
@@ -519,16 +510,8 @@ __global__ __launch_bounds__(kFrErrThreads) void fr_errors_kernel(FrDevice::Args
   if (sum_block) {
     const NlpStructure::SumReduce r = R.red[blockIdx.x - n_err_blocks];
     const int tid = threadIdx.x;
-    double a = 0.0;
-    if (tid < 64)
-      for (int k = tid; k < r.count; k += 64) a += V[r.src_off + k];
-    if (tid < 64) scratch[tid] = a;
-    __syncthreads();
-    for (int w = 32; w > 0; w >>= 1) {
-      if (tid < w) scratch[tid] += scratch[tid + w];
-      __syncthreads();
-    }
-    if (tid == 0) coherent_store(&R.Vw[r.dst], (r.scale_idx >= 0 ? R.tape_scales[r.scale_idx] : 1.0) * scratch[0], true);
+    separable_sum_tree(V, r, scratch, tid);
+    if (tid == 0) coherent_store(&R.Vw[r.dst], separable_sum_scale(r, R.tape_scales) * scratch[0], true);
   }
   double acc[NQ];
 #pragma unroll

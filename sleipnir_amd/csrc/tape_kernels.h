@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device.hpp"
+#include "ipm_reduce.h"
 
 namespace slpx {
 // Phase clocks of the middle workgroup of the launch (debug aid, read with slpx_debug_tape_clocks): wall_clock64()
@@ -39,21 +40,13 @@ __device__ unsigned long long g_tape_clocks[16];  // [0,8): 64-thread kernel, [8
 
 namespace slpx {
 
-// Separable sums (nlp.cpp): V[dst] = scale * (sum of the partials the tape tasks left in the
-// hidden tail of V), in a fixed order — strided per lane, then a pairwise tree.  One
-// 64-thread workgroup per sum.
+// Separable sums on their own launch: one workgroup per sum (separable_sum_tree, ipm_reduce.h).
 __device__ __forceinline__ void tape_reduce_body(const NlpStructure::SumReduce r,
                                                  const double* __restrict__ scales, double* __restrict__ V,
                                                  double* part, int tid) {
-  double acc = 0.0;
-  for (int k = tid; k < r.count; k += 64) acc += V[r.src_off + k];
-  part[tid] = acc;
-  __syncthreads();
-  for (int w = 32; w > 0; w >>= 1) {
-    if (tid < w) part[tid] += part[tid + w];
-    __syncthreads();
-  }
-  if (tid == 0) V[r.dst] = (r.scale_idx >= 0 ? scales[r.scale_idx] : 1.0) * part[0];
+  __builtin_assume(tid < 64);  // one wave per workgroup (tape_reduce_kernel): keeps the tree's lane guard out of the kernel
+  separable_sum_tree(V, r, part, tid);
+  if (tid == 0) V[r.dst] = separable_sum_scale(r, scales) * part[0];
 }
 
 template <int THREADS, bool FULL_OPS>

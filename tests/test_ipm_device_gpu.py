@@ -120,6 +120,43 @@ def test_direction_trial_commit(stepped):
     st.update(x=xc, s=sc, y=yc, z=zc)
 
 
+def test_trial_f_is_the_cost_in_closed_form_where_the_trial_launch_finishes_the_sums():
+    """ipm_trial_metrics_kernel finishes the tape's separable sums itself (separable_sum_tree), and the comparison
+    above takes its reference f from a sweep that runs the same tree.  Here f of the trial point is compared with the
+    cart-pole's cost in closed form, J = d_f sum u_k^2 in long double, at the smallest horizon whose cost the tape sums
+    separably in four partial terms or more (N = 100: sums of up to three terms come out right from a tree that walks
+    its levels in any order).  Bound: a double sum of N terms in whatever order is within (N + 4) 2^-53 sum |terms| of
+    it (fr_reference._sum_with_bound); the trial u_k = u + alpha p is rounded once on the device before it is squared,
+    two more roundings a term at most; the product with d_f and the reference's own conversion to double are a rounding of
+    the result each."""
+    N = 100
+    U = 2.0 ** -53
+    pp = models.cart_pole(N, 5.0 / N)
+    system = sa.System(pp)
+    info = system.info
+    n, me, mi = info["n"], info["m_e"], info["m_i"]
+    assert info["nV"] - (info["off_Hc"] + info["nnz_Hc"]) >= 4  # the partial terms in V's hidden tail
+    rng = np.random.default_rng(cases.SEED)
+    scales = np.concatenate([[0.37], rng.uniform(0.2, 1.0, me), rng.uniform(0.2, 1.0, mi)])
+    system.set_scaling(scales)
+    x, s, y, z, mu = cases.newton_state("interior", pp.get_x(), n, me, mi, scales[0])
+    system.set_state(x, s, y, z, np.array([mu]))
+    assert system.newton_step(True)[0] == 0
+    p_x = system.get("p")[0][:n]
+    d = system.ipm_direction(0.99)
+    for alpha in (d["alpha_max"], 0.25 * d["alpha_max"]):
+        t = system.ipm_trial(alpha)
+        u = (np.asarray(x, dtype=np.longdouble) + np.longdouble(alpha) * np.asarray(p_x, dtype=np.longdouble))[4 * (N + 1):]
+        terms = np.longdouble(scales[0]) * u ** 2
+        assert len(terms) == N
+        f = float(terms.sum())
+        bound = (N + 4 + 2) * U * float(np.abs(terms).sum()) + 2 * U * abs(f)
+        print(f"alpha {alpha!r}: f {t['f']!r}, closed form {f!r}, bound {bound:.3e}")
+        assert abs(t["f"] - f) <= bound, (alpha, t["f"], f, bound)
+    system.close()
+    pp.close()
+
+
 def test_error_reductions(stepped):
     st = stepped
     system, info, scales = st["system"], st["info"], st["scales"]

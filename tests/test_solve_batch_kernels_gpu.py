@@ -285,10 +285,10 @@ def check_errors(r, dev, ref, what):
 
 # ---------------------------------------------------------------- the scenario: every method in the driver's order
 
-def scenario(r, B, ids, active):
+def scenario(r, B, ids, active, nan_tz=None):
     """Runs every BatchIpmDevice method on a batch of instances `ids` (slot b holds instance ids[b]) with the mask
     `active`, inactive slots filled with SENTINEL, and records every output and buffer after every call.  Checks that no
-    call touched an inactive slot of KEPT or of its own output."""
+    call touched an inactive slot of KEPT or of its own output.  nan_tz = (slot, row): that trial z is NaN at the commit."""
     pr = r.probe(B)
     inst = [instance(r, k) for k in ids]
     act = np.asarray(active, dtype=np.uint8)
@@ -379,6 +379,8 @@ def scenario(r, B, ids, active):
             lo, hi = 1.0 / KAPPA * mu[b] / ts[b], KAPPA * mu[b] / ts[b]
             j = np.arange(mi) % 3
             tz[b] = np.where(j == 0, 0.5 * lo, np.where(j == 1, 2.0 * hi, np.sqrt(lo * hi)))
+    if nan_tz is not None:
+        tz[nan_tz[0]][nan_tz[1]] = np.nan
     pr.put("tz", tz)
     params()
     call("commit", pr.commit)
@@ -476,8 +478,13 @@ def check_scenario(r, rec, slots):
         cb = rec["commit:buf"]
         assert np.array_equal(cb["x"][b], tx) and np.array_equal(cb["s"][b], ts) and np.array_equal(cb["y"][b], ty)
         tz = rec["commit:buf"]["tz"][b]
-        z_ref = np.minimum(np.maximum(tz, 1.0 / KAPPA * mu / ts), KAPPA * mu / ts)
-        assert np.array_equal(cb["z"][b], z_ref), tag(b)
+        assert np.array_equal(cb["z"][b], z_reset(tz, mu, ts)), tag(b)
+
+
+def z_reset(tz, mu, ts):
+    """interior_point.hpp:797-801, std::clamp(z, mu / (kappa s), kappa mu / s) as its two comparisons"""
+    lo, hi = 1.0 / KAPPA * mu / ts, KAPPA * mu / ts
+    return np.where(tz < lo, lo, np.where(tz > hi, hi, tz))
 
 
 def check_trial(r, met, tb, b, sc, x, s, y, z, px, ps, py, pz, a, az, s_from_ci, tag):
@@ -534,6 +541,35 @@ def test_every_phase_against_numpy(probes, shape, B):
     if shape == "cart_pole_100":
         assert r.tail > 0  # (the cost's partial sums in V's hidden tail are part of the V compared)
         assert (rec["reg"][0][on] > 0).any()
+
+
+def test_commit_leaves_a_nan_trial_z_as_solve_does(probes):
+    """The z reset of the commit is solve()'s and the reference's, std::clamp: neither of its comparisons holds for a
+    NaN, which therefore stays (fmin / fmax would turn it into the lower end).  Instance 3 of seven gets a NaN in one
+    trial z at the commit: that entry is NaN afterwards, the rest of the instance is what it is without the NaN, and so
+    is every other instance, bit for bit."""
+    r = probes("small_mixed")
+    B, slot, j = 7, 3, 1
+    mask = MASKS[B]()
+    assert mask[slot] and r.mi == 2
+    plain = scenario(r, B, list(range(B)), mask)
+    hit = scenario(r, B, list(range(B)), mask, nan_tz=(slot, j))
+    for name in KEPT:
+        assert np.array_equal(hit["fallback:buf"][name], plain["fallback:buf"][name]), name
+    cb, cp = hit["commit:buf"], plain["commit:buf"]
+    assert np.isnan(cb["tz"][slot][j]) and not np.isnan(cp["tz"]).any()
+    for name in KEPT:
+        if name in ("z", "tz"):
+            continue
+        assert np.array_equal(cb[name], cp[name]), name
+    others = np.arange(B) != slot
+    assert np.array_equal(cb["z"][others], cp["z"][others])
+    assert not np.isnan(cp["z"]).any()
+    assert np.isnan(cb["z"][slot][j])
+    keep = np.arange(r.mi) != j
+    assert np.array_equal(cb["z"][slot][keep], cp["z"][slot][keep])
+    mu = hit["inst"][slot]["mu"]
+    assert np.array_equal(cb["z"][slot], z_reset(cb["tz"][slot], mu, cb["s"][slot]), equal_nan=True)
 
 
 def test_masked_compute(probes):
