@@ -181,6 +181,33 @@ int slpx_problem_solve_batch(slpx_problem* p, int32_t batch, const double* x0, c
  * driver: 0 none needed (constant problem / conflicting bounds), 1 interior point, 2 SQP, 3 Newton}.
  * Returns 0, -1 if no batch has been solved.  An addition within ABI version 6, detected like the one above. */
 int slpx_problem_batch_stats(const slpx_problem* p, int64_t* out);
+/* How the NEXT slpx_problem_solve_batch of this problem runs feasibility restoration
+ * (interior_point.hpp:721-771, sqp.hpp:521-556 calling feasibility_restoration.hpp:347-628).  mode 0, the default:
+ * an instance that asks for restoration is handed to the problem's batch-1 system, one instance after the other,
+ * while the batch waits.  mode 1: every instance that asks in one round of the outer loop enters ONE restoration phase
+ * together, on the batch system — the restoration iteration of each (its own barrier parameter, filter, line search,
+ * regularization memory, exits) in lockstep with the others', one masked launch per phase of the iteration; the
+ * multiplier estimate at exit (:606-617) and the KKT-error fallback of a line search (interior_point.hpp:691-716) still
+ * use the batch-1 system, per instance.  Returns 0, or -100 + slpx_last_error() (null problem, a mode other than 0 / 1);
+ * mode -1 changes nothing and returns the mode in force.  Needs no device.  An addition within ABI version 6, detected by the symbol's presence like slpx_problem_solve_batch. */
+int slpx_problem_set_batch_restoration(slpx_problem* p, int mode);
+/* The last slpx_problem_solve_batch (or slpx_problem_restoration_steps_batch) of this problem: out[4] = {instances
+ * restored in lockstep, restoration phases, lockstep rounds of the restoration loop (batched Newton-step computations),
+ * instances that used the batch-1 system for the KKT-error fallback}; all 0 after a solve in mode 0, whose hand-offs
+ * slpx_problem_batch_stats counts (and which counts 0 hand-offs in mode 1).  Returns 0, -1 if no batch has been solved.
+ * An addition within ABI version 6, detected like the one above. */
+int slpx_problem_batch_restoration_stats(const slpx_problem* p, int64_t* out);
+/* The batched twin of slpx_problem_restoration_steps (below): from B iterates x[B][n], s[B][m_i], y[B][m_e], z[B][m_i],
+ * mu[B] — all in/out but mu — `steps` iterations of feasibility restoration per instance (feasibility_restoration.hpp:
+ * 347-628) in lockstep on the batch system, left the way the reference leaves when its acceptance callback fires
+ * (:729-752), y and z replaced by the least-squares multiplier estimate (lagrange_multiplier_estimate.hpp:56-133).
+ * Scaling as in slpx_problem_restoration_steps (at the variables' current values, the same for every instance);
+ * options as slpx_problem_solve_sized (tolerance, max_iterations, timeout are read).  status[B]: the ExitStatus of
+ * that function per instance (0: restored).  Returns 0, or -100 + slpx_last_error() (no device, batch <= 0, a NULL
+ * array, callbacks registered).  An addition within ABI version 6, detected like the ones above. */
+int slpx_problem_restoration_steps_batch(slpx_problem* p, const slpx_options* opt, uint32_t options_bytes, int32_t batch,
+                                         double* x, double* s, double* y, double* z, const double* mu, int32_t steps,
+                                         int32_t* status);
 /* feasibility_restoration (solver/util/feasibility_restoration.hpp:347-628) on its own: from the
  * iterate (x[n], s[m_i], y[m_e], z[m_i], mu) — all in/out but mu — build the restoration model,
  * run `steps` iterations of its interior-point loop, leave it the way the reference does when its

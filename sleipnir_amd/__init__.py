@@ -168,6 +168,11 @@ def lib() -> ctypes.CDLL:
             vp, vp, vp, vp, vp, ctypes.POINTER(Report))
     if hasattr(L, "slpx_problem_batch_stats"):
         sig("slpx_problem_batch_stats", ctypes.c_int, vp, vp)
+    if hasattr(L, "slpx_problem_set_batch_restoration"):
+        sig("slpx_problem_set_batch_restoration", ctypes.c_int, vp, ctypes.c_int)
+        sig("slpx_problem_batch_restoration_stats", ctypes.c_int, vp, vp)
+        sig("slpx_problem_restoration_steps_batch", ctypes.c_int, vp, ctypes.POINTER(Options), ctypes.c_uint32, i32, vp, vp,
+            vp, vp, vp, i32, vp)
     if hasattr(L, "slpx_ldlt_residual"):
         sig("slpx_ldlt_residual", ctypes.c_int, vp, vp, vp)
         sig("slpx_ldlt_refine", ctypes.c_int, vp, i32, vp, vp)
@@ -264,15 +269,29 @@ class Problem:
             raise SlpxError(lib().slpx_last_error().decode())
         return status, {f[0]: getattr(rep, f[0]) for f in Report._fields_}
 
-    def solve_batch(self, x0, tolerance=1e-8, max_iterations=5000, timeout=0.0, feasible_ipm=False):
+    RESTORATION_MODES = {"handoff": 0, "lockstep": 1}
+
+    def solve_batch(self, x0, tolerance=1e-8, max_iterations=5000, timeout=0.0, feasible_ipm=False, restoration="handoff"):
         """B instances from the rows of x0 (B x n), each as solve() from that start
         (slpx_problem_solve_batch).  Returns a dict of arrays: status, x, s, y, z, cost, iterations,
         restorations, the batch's report, and how the batch ran (slpx_problem_batch_stats): rounds (lockstep
         Newton-step computations), handoffs (instances handed to the batch-1 system for restoration) and
-        driver (0 none needed, 1 interior point, 2 SQP, 3 Newton)."""
+        driver (0 none needed, 1 interior point, 2 SQP, 3 Newton).
+        restoration: "handoff" (the default: an instance that asks for feasibility restoration runs it on the batch-1
+        system while the batch waits) or "lockstep" (all instances that ask in one round run one restoration phase
+        together on the batch system; slpx_problem_set_batch_restoration).  "restoration_lockstep" in the result is
+        slpx_problem_batch_restoration_stats: instances restored in lockstep, phases, lockstep restoration rounds,
+        instances that used the batch-1 system for the KKT-error fallback."""
         L = lib()
         if not hasattr(L, "slpx_problem_solve_batch"):
             raise SlpxError(f"{LIB_PATH} has no slpx_problem_solve_batch")
+        if restoration not in self.RESTORATION_MODES:
+            raise ValueError('restoration: "handoff" or "lockstep"')
+        if hasattr(L, "slpx_problem_set_batch_restoration"):
+            if L.slpx_problem_set_batch_restoration(self._h, self.RESTORATION_MODES[restoration]) != 0:
+                raise SlpxError(L.slpx_last_error().decode())
+        elif restoration != "handoff":
+            raise SlpxError(f"{LIB_PATH} has no slpx_problem_set_batch_restoration")
         n, me, mi = self.dims
         x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).reshape(-1, n) if n else
                                   np.zeros((len(x0), 0)))
@@ -290,6 +309,8 @@ class Problem:
             raise SlpxError(L.slpx_last_error().decode())
         out["report"] = {f[0]: getattr(rep, f[0]) for f in Report._fields_}
         out["rounds"], out["handoffs"], out["driver"] = self.batch_stats()[1:]
+        if hasattr(L, "slpx_problem_batch_restoration_stats"):
+            out["restoration_lockstep"] = dict(zip(("instances", "phases", "rounds", "fallbacks"), self.batch_restoration_stats()))
         return out
 
     def batch_stats(self):
@@ -301,6 +322,39 @@ class Problem:
         if L.slpx_problem_batch_stats(self._h, st.ctypes.data) != 0:
             raise SlpxError("no batch has been solved")
         return tuple(int(v) for v in st)
+
+    def batch_restoration_stats(self):
+        """(instances restored in lockstep, restoration phases, lockstep restoration rounds, instances that used the
+        batch-1 system for a fallback) of the last batch (slpx_problem_batch_restoration_stats)."""
+        L = lib()
+        if not hasattr(L, "slpx_problem_batch_restoration_stats"):
+            raise SlpxError(f"{LIB_PATH} has no slpx_problem_batch_restoration_stats")
+        st = np.zeros(4, dtype=np.int64)
+        if L.slpx_problem_batch_restoration_stats(self._h, st.ctypes.data) != 0:
+            raise SlpxError("no batch has been solved")
+        return tuple(int(v) for v in st)
+
+    def restoration_steps_batch(self, x, s, y, z, mu, steps, tolerance=1e-8, max_iterations=5000):
+        """The batched twin of restoration_steps: `steps` restoration iterations from each of the B iterates in the rows of
+        x (B x n), s (B x m_i), y (B x m_e), z (B x m_i) with mu (B), in lockstep on the batch system
+        (slpx_problem_restoration_steps_batch).  Returns (status[B], x, s, y, z)."""
+        L = lib()
+        if not hasattr(L, "slpx_problem_restoration_steps_batch"):
+            raise SlpxError(f"{LIB_PATH} has no slpx_problem_restoration_steps_batch")
+        n, me, mi = self.dims
+        mu = np.ascontiguousarray(np.atleast_1d(np.asarray(mu, dtype=np.float64)))
+        B = mu.shape[0]
+        x, s, y, z = (np.array(np.asarray(a, dtype=np.float64).reshape(B, k), dtype=np.float64, copy=True, order="C")
+                      for a, k in ((x, n), (s, mi), (y, me), (z, mi)))
+        status = np.zeros(B, dtype=np.int32)
+        opt = Options(tolerance, max_iterations, 0.0, 0, 0, 0)
+        hold = [a if a.size else np.zeros(1) for a in (x, s, y, z)]
+        rc = L.slpx_problem_restoration_steps_batch(self._h, ctypes.byref(opt), ctypes.sizeof(Options), B,
+                                                    *(a.ctypes.data for a in hold), mu.ctypes.data, int(steps),
+                                                    status.ctypes.data)
+        if rc != 0:
+            raise SlpxError(L.slpx_last_error().decode())
+        return status, x, s, y, z
 
     def restoration_steps(self, x, s, y, z, mu, steps, tolerance=1e-8, max_iterations=5000):
         """feasibility_restoration from the given iterate, `steps` iterations (slpx_problem_restoration_steps)."""

@@ -3,9 +3,11 @@
 // ipm_decide.h: the error measures), from a few scalars per instance; the vectors stay on the device and every piece
 // of work runs in one masked launch with the other instances that need it at the same point of their iteration.
 // The loop is written once; a driver says what its iteration does differently from the others, and nothing more.
+#include <memory>
 #include <optional>
 
 #include "eq_batch.hpp"
+#include "fr_batch.hpp"
 #include "ipm_batch.hpp"
 #include "ipm_line_search.hpp"
 
@@ -175,7 +177,7 @@ struct NewtonDriver : EqDriver {
 
 template <class Driver>
 void lockstep(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales, const Options& options,
-              const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out) {
+              const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out, int restoration_mode) {
   const auto solve_start = clk::now();
   const NlpStructure& st = sys.structure();
   DeviceNlp& dev = sys.device();
@@ -187,9 +189,12 @@ void lockstep(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>
   SolveReport& rep = out.report;
   out.driver = Driver::kId;
   out.rounds = out.handoffs = 0;
+  std::fill(out.restoration_lockstep, out.restoration_lockstep + 4, int64_t{0});
+  if (restoration_mode != 0 && restoration_mode != 1) throw std::runtime_error(name + ": restoration mode must be 0 (hand-off) or 1 (lockstep)");
 
   Driver drv{st, options};
   typename Driver::Device bd(sys);
+  std::unique_ptr<BatchFrDevice> frd;  // restoration in lockstep: made when a phase is first entered
   bd.set_scales(scales);
   sys.reset_regularization();
   sys.set_gamma_min(1e-10);  // interior_point.hpp:350-352, sparse_regularized_ldlt.hpp:197
@@ -332,8 +337,53 @@ void lockstep(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>
     // ---- commit (:773-801) ----
     if (launch_for([&](const Instance& I) { return I.running && !restores(I); })) bd.commit();
 
+    // ---- feasibility restoration in lockstep (restoration_mode 1): everybody who asked in this round enters ONE
+    // restoration phase on the batch system (fr_batch.hpp); the others wait ----
+    if (restoration_mode == 1) {
+      std::vector<BatchRestorationRequest> requests;
+      for (int b = 0; b < B; ++b) {
+        Instance& I = inst[b];
+        if (!I.running || !restores(I)) continue;
+        BatchRestorationRequest r;
+        r.b = b;
+        r.scales = I.scales;
+        r.mu = drv.restoration_mu(I);
+        Vec V;
+        bd.get_instance(b, r.x, r.s, r.y, r.z, V);
+        VView cur{st, V};
+        r.c_e.assign(cur.c_e(), cur.c_e() + m_e);
+        r.c_i.assign(cur.c_i(), cur.c_i() + m_i);
+        r.g = cur.g_dense();
+        const FilterEntry initial_entry = I.current_entry;
+        r.initial_violation = initial_entry.constraint_violation;
+        Instance* ip = &I;
+        r.outer_accepts = [ip, initial_entry](const FilterEntry& trial_entry, double D_phi_restoration) {
+          return ip->filter->try_add(initial_entry, trial_entry, D_phi_restoration, Driver::search(*ip).alpha);
+        };
+        r.iterations = &I.iterations;
+        r.rep = &I.rep;
+        requests.push_back(std::move(r));
+      }
+      if (!requests.empty()) {
+        const auto t_fr = clk::now();
+        if (!frd) frd = std::make_unique<BatchFrDevice>(sys);
+        BatchRestorationStats fs;
+        restoration_phase(sys, single, *frd, options, requests, /*stop_after=*/-1, solve_start, fs);
+        out.restoration_lockstep[0] += fs.instances;
+        out.restoration_lockstep[1] += fs.phases;
+        out.restoration_lockstep[2] += fs.rounds;
+        out.restoration_lockstep[3] += fs.fallbacks;
+        drv.after_restoration(single);
+        rep.t_restoration += since(t_fr);
+        for (BatchRestorationRequest& r : requests) {
+          if (r.status != ExitStatus::SUCCESS) finish(inst[r.b], r.status);
+          bd.put_instance(r.b, r.x, r.s, r.y, r.z);
+        }
+      }
+    }
+
     // ---- feasibility restoration on the batch-1 system (:721-771, sqp.hpp:521-556), one instance at a time ----
-    for (int b = 0; b < B; ++b) {
+    for (int b = 0; b < B && restoration_mode == 0; ++b) {
       Instance& I = inst[b];
       if (!I.running || !restores(I)) continue;
       const auto t_fr = clk::now();
@@ -420,18 +470,18 @@ void lockstep(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>
 
 void interior_point_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales,
                           const Options& options, const std::vector<double>& x0, const std::vector<uint8_t>& run,
-                          BatchSolveResult& out) {
-  lockstep<IpmDriver>(sys, single, scales, options, x0, run, out);
+                          BatchSolveResult& out, int restoration_mode) {
+  lockstep<IpmDriver>(sys, single, scales, options, x0, run, out, restoration_mode);
 }
 
 void sqp_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales, const Options& options,
-               const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out) {
-  lockstep<SqpDriver>(sys, single, scales, options, x0, run, out);
+               const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out, int restoration_mode) {
+  lockstep<SqpDriver>(sys, single, scales, options, x0, run, out, restoration_mode);
 }
 
 void newton_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales, const Options& options,
                   const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out) {
-  lockstep<NewtonDriver>(sys, single, scales, options, x0, run, out);
+  lockstep<NewtonDriver>(sys, single, scales, options, x0, run, out, /*restoration_mode=*/0);
 }
 
 }  // namespace slpx

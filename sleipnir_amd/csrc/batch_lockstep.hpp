@@ -12,7 +12,8 @@
 // full sweeps of the KKT-error fallback for the instances that wait for that work — then commit, refresh, exits.  An
 // instance that has finished is frozen: the kernels skip it by its active flag.  Feasibility restoration runs on the
 // problem's own batch-1 system (`single`), one instance at a time, with that instance's scaling, iterate, barrier
-// parameter, δ/γ memory and filter; the result is written back into the batch state.
+// parameter, δ/γ memory and filter; the result is written back into the batch state.  (restoration_mode 1: the
+// instances that ask in one round run one restoration phase together on the batch system instead — fr_batch.hpp.)
 //
 // This header holds what every driver shares on the device: the reductions of batch_errors_kernel and BatchDevice,
 // the state under BatchIpmDevice (ipm_batch.hpp) and BatchEqDevice (eq_batch.hpp).
@@ -96,6 +97,9 @@ struct BatchDevice {
     SLPX_HIP_CHECK(hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, sys.device().stream()));
   }
   void scale_V(int count);
+  // the tape's inputs from m_cur (duals times the instance's d_c; with_state: s, y, z into the system's buffers too), the
+  // full tape at unit scales, the instance's scaling of what it wrote: the system's V is the iterate's
+  void sweep_iterate(bool with_state);
   void errors(const double* V, bool trial, std::vector<double>& err);
   void download_out(size_t per_instance, std::vector<double>& out);
 };
@@ -110,17 +114,23 @@ struct BatchSolveResult {
   // batch-1 system for restoration, and the driver: 0 none needed, 1 interior point, 2 SQP, 3 Newton
   int64_t rounds = 0, handoffs = 0;
   int driver = 0;
+  // restoration in lockstep (restoration_mode 1; fr_batch.hpp): instances restored, phases, lockstep rounds of the
+  // restoration loop, instances that used the batch-1 system for the KKT-error fallback — all 0 in hand-off mode
+  int64_t restoration_lockstep[4] = {0, 0, 0, 0};
 };
 
 // x0 = [B][n]; scales = [B][1 + m_e + m_i] (compute_problem_scaling at each instance's x0); `run[b]` = 0: instance b
 // is not solved here (its status in `out` is left as the caller set it).  `sys` is the batch system (batch() == B,
 // tape at unit scales), `single` the batch-1 system of the same model (restoration).  A model takes the driver
 // Problem::solve() gives it: interior_point_batch m_i > 0, sqp_batch m_i == 0 and m_e > 0, newton_batch m_e == m_i == 0.
+// restoration_mode 0: an instance that asks for feasibility restoration is handed to `single`, one after the other
+// (the default); 1: all instances that ask in one round enter one restoration phase on the batch system, in lockstep
+// (fr_batch.hpp: restoration_phase).
 void interior_point_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales,
                           const Options& options, const std::vector<double>& x0, const std::vector<uint8_t>& run,
-                          BatchSolveResult& out);
+                          BatchSolveResult& out, int restoration_mode = 0);
 void sqp_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales, const Options& options,
-               const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out);
+               const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out, int restoration_mode = 0);
 void newton_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales, const Options& options,
                   const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out);
 

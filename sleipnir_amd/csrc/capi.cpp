@@ -167,6 +167,8 @@ int slpx_problem_solve_batch(slpx_problem* p, int32_t batch, const double* x0, c
     p->batch_stats[1] = r.rounds;
     p->batch_stats[2] = r.handoffs;
     p->batch_stats[3] = r.driver;
+    std::copy(r.restoration_lockstep, r.restoration_lockstep + 4, p->batch_restoration_stats);
+    p->batch_restoration_stats_valid = true;
     for (size_t b = 0; b < B; ++b) {
       if (status) status[b] = static_cast<int32_t>(r.status[b]);
       if (cost) cost[b] = r.cost[b];
@@ -192,6 +194,56 @@ int slpx_problem_batch_stats(const slpx_problem* p, int64_t* out) {
   if (p == nullptr || out == nullptr || p->batch_stats[0] == 0) return -1;
   std::copy(p->batch_stats, p->batch_stats + 4, out);
   return 0;
+}
+
+int slpx_problem_set_batch_restoration(slpx_problem* p, int mode) {
+  if (p != nullptr && mode == -1) return p->problem.batch_restoration();  // (a query: nothing changes)
+  return guard([&] {
+    if (p == nullptr) throw std::runtime_error("slpx_problem_set_batch_restoration: null problem");
+    p->problem.set_batch_restoration(mode);
+  });
+}
+
+int slpx_problem_batch_restoration_stats(const slpx_problem* p, int64_t* out) {
+  if (p == nullptr || out == nullptr || !p->batch_restoration_stats_valid) return -1;
+  std::copy(p->batch_restoration_stats, p->batch_restoration_stats + 4, out);
+  return 0;
+}
+
+int slpx_problem_restoration_steps_batch(slpx_problem* p, const slpx_options* o, uint32_t options_bytes, int32_t batch, double* x,
+                                         double* sv, double* y, double* z, const double* mu, int32_t steps, int32_t* status) {
+  (void)options_bytes;  // (every member read here predates `spy`, the only one a shorter struct lacks)
+  return guard([&] {
+    if (p == nullptr) throw std::runtime_error("slpx_problem_restoration_steps_batch: null problem");
+    if (batch <= 0) throw std::runtime_error("slpx_problem_restoration_steps_batch: batch must be positive");
+    if (x == nullptr || mu == nullptr || status == nullptr) throw std::runtime_error("slpx_problem_restoration_steps_batch: x, mu or status is null");
+    if (p->problem.has_callbacks())
+      throw std::runtime_error("slpx_problem_restoration_steps_batch: the problem has iteration callbacks registered");
+    if (slpx_device_count() < 1) throw std::runtime_error("slpx_problem_restoration_steps_batch: no HIP device");
+    slp::Options opt;
+    if (o) {
+      opt.tolerance = o->tolerance;
+      opt.max_iterations = o->max_iterations;
+      if (o->timeout > 0) opt.timeout = o->timeout;
+    }
+    const size_t B = static_cast<size_t>(batch), n = p->problem.decision_variables().size(),
+                 me = p->problem.equality_constraints().size(), mi = p->problem.inequality_constraints().size();
+    if ((mi > 0 && (sv == nullptr || z == nullptr)) || (me > 0 && y == nullptr))
+      throw std::runtime_error("slpx_problem_restoration_steps_batch: s, y or z is null");
+    std::vector<double> vx(x, x + B * n), vs, vy, vz;
+    if (mi) vs.assign(sv, sv + B * mi), vz.assign(z, z + B * mi);
+    if (me) vy.assign(y, y + B * me);
+    slpx::BatchRestorationStats stats;
+    const std::vector<slpx::ExitStatus> st =
+        p->problem.restoration_steps_batch(opt, batch, vx, vs, vy, vz, std::vector<double>(mu, mu + B), steps, stats);
+    const int64_t counts[4] = {stats.instances, stats.phases, stats.rounds, stats.fallbacks};
+    std::copy(counts, counts + 4, p->batch_restoration_stats);
+    p->batch_restoration_stats_valid = true;
+    for (size_t b = 0; b < B; ++b) status[b] = static_cast<int32_t>(st[b]);
+    std::copy(vx.begin(), vx.end(), x);
+    if (mi) std::copy(vs.begin(), vs.end(), sv), std::copy(vz.begin(), vz.end(), z);
+    if (me) std::copy(vy.begin(), vy.end(), y);
+  });
 }
 
 int slpx_problem_restoration_steps(slpx_problem* p, const slpx_options* o, double* x, double* sv, double* y,

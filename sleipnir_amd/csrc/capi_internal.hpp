@@ -21,5 +21,8 @@ struct slpx_problem {
   double t_compile = 0.0;
   // slpx_problem_batch_stats: the last slpx_problem_solve_batch (batch = 0: none yet)
   int64_t batch_stats[4] = {0, 0, 0, 0};
+  // slpx_problem_batch_restoration_stats: of the last batch (solve or restoration steps)
+  int64_t batch_restoration_stats[4] = {0, 0, 0, 0};
+  bool batch_restoration_stats_valid = false;
   std::unique_ptr<slpx_system> borrowed;  // slpx_problem_system()
 };

@@ -738,6 +738,53 @@ void compute_p_n(const Vec& c, double rho, double mu, Vec& p, Vec& n) {
   }
 }
 
+}  // namespace
+
+// feasibility_restoration.hpp:391-432: what a restoration phase starts from (ipm.hpp)
+RestorationEntry restoration_entry(const NlpStructure& ost, const Vec& scales, const Vec& x, const Vec& s, double mu, const Vec& c_e,
+                                   const Vec& c_i) {
+  const int n = ost.n, m_e = ost.m_e, m_i = ost.m_i, M = 2 * m_e + 2 * m_i;
+  constexpr double rho = 1e3;
+  RestorationEntry out;
+
+  Vec cis(m_i);
+  for (int j = 0; j < m_i; ++j) cis[j] = c_i[j] - s[j];
+  const double fr_mu = std::max({mu, norm_inf(c_e.data(), m_e), norm_inf(cis.data(), m_i)});  // :396-397
+  const double zeta = std::sqrt(fr_mu);
+  out.fr_mu = fr_mu;
+
+  Vec p_e, n_e, p_i, n_i;
+  compute_p_n(c_e, rho, fr_mu, p_e, n_e);  // :400-401
+  compute_p_n(cis, rho, fr_mu, p_i, n_i);
+
+  // the restoration iterate (:408-423): X = [x | p_e | n_e | p_i | n_i], S = [s | 1...], y = 0, Z = fr_mu / S (.. / p, n)
+  Vec& X = out.X;
+  X.reserve(n + M);
+  for (const Vec* v : {static_cast<const Vec*>(&x), static_cast<const Vec*>(&p_e), static_cast<const Vec*>(&n_e),
+                       static_cast<const Vec*>(&p_i), static_cast<const Vec*>(&n_i)})
+    X.insert(X.end(), v->begin(), v->end());
+  out.S.assign(m_i + M, 1.0);
+  out.y.assign(m_e, 0.0);
+  Vec& Z = out.Z;
+  std::copy(s.begin(), s.end(), out.S.begin());
+  Z.reserve(m_i + M);
+  for (int j = 0; j < m_i; ++j) Z.push_back(fr_mu * (1.0 / s[j]));
+  for (int e = 0; e < M; ++e) Z.push_back(fr_mu * (1.0 / X[n + e]));
+  out.x_r = x;
+  Vec& w = out.w;
+  w.resize(n);
+  for (int k = 0; k < n; ++k) w[k] = zeta * std::min(1.0 / (x[k] * x[k]), 1.0);  // zeta D_R (:404-405)
+
+  // the error measure un-scales with {1, d_ce, [d_ci, 1...]} (:425-432); the bound rows' 1 is implied
+  Vec& fr_scales = out.fr_scales;
+  fr_scales.assign(1 + m_e + m_i, 1.0);
+  for (int j = 0; j < m_e; ++j) fr_scales[1 + j] = scales[1 + j];
+  for (int j = 0; j < m_i; ++j) fr_scales[1 + m_e + j] = scales[1 + m_e + j];
+  return out;
+}
+
+namespace {
+
 // (the restoration problem itself is never built as a model: restoration.hpp — its extra variables are eliminated from
 // the Newton-KKT system in closed form and the rest runs on the outer problem's own compiled system)
 
@@ -1154,18 +1201,11 @@ ExitStatus feasibility_restoration(NewtonSystem& outer, const Vec& scales, const
                                    Vec& x, Vec& s, Vec& y, Vec& z, double mu, int& iterations, SolveReport& rep,
                                    clk::time_point solve_start, const Vec& c_e, const Vec& c_i, const Vec& g, double initial_violation) {
   const NlpStructure& ost = outer.structure();
-  const int n = ost.n, m_e = ost.m_e, m_i = ost.m_i, M = 2 * m_e + 2 * m_i;
-  constexpr double rho = 1e3;
+  const int n = ost.n, m_i = ost.m_i;
   ++rep.restorations;
 
-  Vec cis(m_i);
-  for (int j = 0; j < m_i; ++j) cis[j] = c_i[j] - s[j];
-  const double fr_mu = std::max({mu, norm_inf(c_e.data(), m_e), norm_inf(cis.data(), m_i)});  // :396-397
-  const double zeta = std::sqrt(fr_mu);
-
-  Vec p_e, n_e, p_i, n_i;
-  compute_p_n(c_e, rho, fr_mu, p_e, n_e);  // :400-401
-  compute_p_n(cis, rho, fr_mu, p_i, n_i);
+  RestorationEntry entry = restoration_entry(ost, scales, x, s, mu, c_e, c_i);
+  const double fr_mu = entry.fr_mu;
 
   DeviceNlp& dev = outer.device();
   const auto t_build = clk::now();
@@ -1173,25 +1213,8 @@ ExitStatus feasibility_restoration(NewtonSystem& outer, const Vec& scales, const
   FrDevice& fr = outer.restoration_device();
   rep.t_restoration_setup += since(t_build);
 
-  // the restoration iterate (:408-423): X = [x | p_e | n_e | p_i | n_i], S = [s | 1...], y = 0, Z = fr_mu / S (.. / p, n)
-  Vec X;
-  X.reserve(n + M);
-  for (const Vec* v : {static_cast<const Vec*>(&x), static_cast<const Vec*>(&p_e), static_cast<const Vec*>(&n_e),
-                       static_cast<const Vec*>(&p_i), static_cast<const Vec*>(&n_i)})
-    X.insert(X.end(), v->begin(), v->end());
-  Vec S(m_i + M, 1.0), fr_y(m_e, 0.0), Z;
-  std::copy(s.begin(), s.end(), S.begin());
-  Z.reserve(m_i + M);
-  for (int j = 0; j < m_i; ++j) Z.push_back(fr_mu * (1.0 / s[j]));
-  for (int e = 0; e < M; ++e) Z.push_back(fr_mu * (1.0 / X[n + e]));
-  const Vec x_r(x);
-  Vec w(n);
-  for (int k = 0; k < n; ++k) w[k] = zeta * std::min(1.0 / (x[k] * x[k]), 1.0);  // zeta D_R (:404-405)
-
-  // the error measure un-scales with {1, d_ce, [d_ci, 1...]} (:425-432); the bound rows' 1 is implied
-  Vec fr_scales(1 + m_e + m_i, 1.0);
-  for (int j = 0; j < m_e; ++j) fr_scales[1 + j] = scales[1 + j];
-  for (int j = 0; j < m_i; ++j) fr_scales[1 + m_e + j] = scales[1 + m_e + j];
+  Vec &X = entry.X, &S = entry.S, &fr_y = entry.y, &Z = entry.Z;
+  const Vec &x_r = entry.x_r, &w = entry.w, &fr_scales = entry.fr_scales;
 
   const Vec s_outer(s);
   fr.begin(x_r.data(), w.data(), g.data(), s_outer.data(), mu, X.data() + n, S.data() + m_i, Z.data() + m_i, fr_scales);
@@ -1223,12 +1246,7 @@ ExitStatus feasibility_restoration(NewtonSystem& outer, const Vec& scales, const
 
   if (status == ExitStatus::CALLBACK_REQUESTED_STOP) {
     // back to the original problem: least-squares multipliers at the new point (:606-617)
-    Vec V(ost.nV);
-    dev.upload_x(x.data());
-    dev.upload_duals(s.data(), y.data(), z.data());
-    dev.sweep_full();
-    dev.download_V(V.data());
-    if (!lagrange_multiplier_estimate(outer, V, s, mu, y, z, rep)) return ExitStatus::FACTORIZATION_FAILED;
+    if (!restoration_multiplier_estimate(outer, x, s, y, z, mu, rep)) return ExitStatus::FACTORIZATION_FAILED;
     return ExitStatus::SUCCESS;
   } else if (status == ExitStatus::SUCCESS) {
     return ExitStatus::LOCALLY_INFEASIBLE;
@@ -1601,6 +1619,23 @@ ExitStatus feasibility_restoration_handoff(NewtonSystem& sys, const std::vector<
                                            const std::vector<double>& g, double initial_violation) {
   return feasibility_restoration(sys, scales, {}, outer_accepts, options, x, s, y, z, mu, iterations, report, solve_start, c_e,
                                  c_i, g, initial_violation);
+}
+
+bool restoration_multiplier_estimate(NewtonSystem& outer, const std::vector<double>& x, const std::vector<double>& s,
+                                     std::vector<double>& y, std::vector<double>& z, double mu, SolveReport& rep) {
+  DeviceNlp& dev = outer.device();
+  Vec V(outer.structure().nV);
+  dev.upload_x(x.data());
+  dev.upload_duals(s.data(), y.data(), z.data());
+  dev.sweep_full();
+  dev.download_V(V.data());
+  return lagrange_multiplier_estimate(outer, V, s, mu, y, z, rep);
+}
+
+double restoration_kkt_error(const NlpStructure& o, const std::vector<double>& Vo, const std::vector<double>& X,
+                             const std::vector<double>& S, const std::vector<double>& y, const std::vector<double>& Z,
+                             const std::vector<double>& x_r, const std::vector<double>& w, double mu) {
+  return restoration_kkt_error_one_norm(o, Vo, X, S, y, Z, x_r, w, /*rho=*/1e3, mu);
 }
 
 ExitStatus interior_point(NewtonSystem& sys, const std::vector<double>& scales,

@@ -125,6 +125,29 @@ ExitStatus feasibility_restoration_handoff(NewtonSystem& sys, const std::vector<
                                            const std::vector<double>& c_e, const std::vector<double>& c_i,
                                            const std::vector<double>& g, double initial_violation);
 
+// The host pieces of feasibility_restoration() for a caller that runs the restoration iterations itself (the batched
+// loop's restoration phase, fr_batch.hpp) — the code the single-problem path runs:
+//  * restoration_entry (feasibility_restoration.hpp:391-432) from the outer iterate (x, s), its barrier parameter and
+//    c_e, c_i at x: fr_mu = max(mu, ||c_e||_inf, ||c_i - s||_inf), the restoration iterate X = [x | p_e | n_e | p_i | n_i],
+//    S = [s | 1...], y = 0, Z = fr_mu / S (.. / p, n), x_R and zeta D_R, and [1 | d_ce | d_ci] the error measure un-scales with;
+//  * restoration_multiplier_estimate (:606-617): back in the outer problem, y and z replaced by the least-squares
+//    estimate (lagrange_multiplier_estimate.hpp:56-133) at (x, s); false: its factorization failed.  `outer` is a
+//    batch-1 system with the instance's scaling installed;
+//  * restoration_kkt_error: kkt_error.hpp:92-146 (one-norm) of the restoration problem from the OUTER problem's V at x —
+//    the line search's rare fallback (interior_point.hpp:691-716).
+struct RestorationEntry {
+  double fr_mu = 0.0;
+  std::vector<double> X, S, y, Z, x_r, w, fr_scales;
+};
+RestorationEntry restoration_entry(const NlpStructure& st, const std::vector<double>& scales, const std::vector<double>& x,
+                                   const std::vector<double>& s, double mu, const std::vector<double>& c_e,
+                                   const std::vector<double>& c_i);
+bool restoration_multiplier_estimate(NewtonSystem& outer, const std::vector<double>& x, const std::vector<double>& s,
+                                     std::vector<double>& y, std::vector<double>& z, double mu, SolveReport& rep);
+double restoration_kkt_error(const NlpStructure& st, const std::vector<double>& Vo, const std::vector<double>& X,
+                             const std::vector<double>& S, const std::vector<double>& y, const std::vector<double>& Z,
+                             const std::vector<double>& x_r, const std::vector<double>& w, double mu);
+
 // x in/out.  `scales` = [d_f, d_ce.., d_ci..] already installed on the device.
 ExitStatus interior_point(NewtonSystem& sys, const std::vector<double>& scales,
                           const std::vector<IterationCallback>& callbacks, const Options& options,

@@ -136,15 +136,21 @@ void BatchDevice::errors(const double* V, bool trial, std::vector<double>& err) 
   download_out(kBatchErrN, err);
 }
 
-void BatchDevice::refresh(std::vector<double>& err) {
+void BatchDevice::sweep_iterate(bool with_state) {
   DeviceNlp& dev = sys.device();
   hipStream_t st = dev.stream();
   hipLaunchKernelGGL(batch_load_state_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), dev.d_x(),
-                     sys.structure().n_inputs(), m_cur, m_scales.p, ns, dev.d_s(), dev.d_y(), dev.d_z(), 1, m_active.p);
+                     sys.structure().n_inputs(), m_cur, m_scales.p, ns, dev.d_s(), dev.d_y(), dev.d_z(), with_state ? 1 : 0,
+                     m_active.p);
   SLPX_HIP_CHECK(hipGetLastError());
   dev.sweep_full();
   scale_V(nV);
-  SLPX_HIP_CHECK(hipMemcpyAsync(m_Vcur.p, dev.d_V(), m_Vcur.n * sizeof(double), hipMemcpyDeviceToDevice, st));
+}
+
+void BatchDevice::refresh(std::vector<double>& err) {
+  DeviceNlp& dev = sys.device();
+  sweep_iterate(true);
+  SLPX_HIP_CHECK(hipMemcpyAsync(m_Vcur.p, dev.d_V(), m_Vcur.n * sizeof(double), hipMemcpyDeviceToDevice, dev.stream()));
   errors(m_Vcur.p, false, err);
 }
 

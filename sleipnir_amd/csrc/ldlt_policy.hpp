@@ -142,9 +142,12 @@ class LdltPolicy {
 
 // The loop for a batch, one attempt per launch: launch(delta, gamma, active) factors the problems with active[b] != 0
 // and returns every problem's counters.  Returns the number of launches.  (`launch_for_nobody`: the unregularized
-// launch is made even where `active` leaves nobody.)
+// launch is made even where `active` leaves nobody.)  `extra_min_pivot` (or none): per problem, the smallest pivot of
+// rows the caller eliminated outside the factorization — it joins the test of the unregularized attempt, as in
+// ldlt_run_twin (restoration.hpp: the closed-form rows of a batch of restoration problems).
 template <class Launch>
-int ldlt_run_batch(std::vector<LdltPolicy>& pol, std::vector<uint8_t>& active, bool launch_for_nobody, Launch&& launch) {
+int ldlt_run_batch(std::vector<LdltPolicy>& pol, std::vector<uint8_t>& active, bool launch_for_nobody, Launch&& launch,
+                   const std::vector<double>* extra_min_pivot = nullptr) {
   const size_t B = pol.size();
   std::vector<double> delta(B, 0.0), gamma(B, 0.0);
   int launches = 0;
@@ -158,7 +161,8 @@ int ldlt_run_batch(std::vector<LdltPolicy>& pol, std::vector<uint8_t>& active, b
     any = false;
     for (size_t b = 0; b < B; ++b)
       if (active[b]) {
-        pol[b].judge(stats[b]);
+        if (extra_min_pivot) pol[b].judge(stats[b], (*extra_min_pivot)[b]);
+        else pol[b].judge(stats[b]);
         active[b] = !pol[b].done();
         any = any || active[b];
       }

@@ -427,6 +427,36 @@ std::vector<FactorInfo> NewtonSystem::compute_hooked(const AttemptHooks& hooks) 
   return finish_twin_run(pol, run);
 }
 
+std::vector<FactorInfo> NewtonSystem::compute_hooked_batch(const BatchPrepare& prepare, const std::vector<uint8_t>& mask,
+                                                           const std::vector<double>& eliminated_min_pivot) {
+  const int B = m_opt.batch;
+  if (static_cast<int>(mask.size()) != B || static_cast<int>(eliminated_min_pivot.size()) != B)
+    throw std::runtime_error("NewtonSystem::compute_hooked_batch: one entry per problem");
+  m_last_twin_launches = m_last_twin_taken = 0;
+  std::vector<uint8_t> active = mask;
+  std::vector<LdltPolicy> pol(B);
+  for (int b = 0; b < B; ++b)
+    if (active[b]) pol[b] = start_policy(b, /*skip_first=*/false);
+  const std::vector<uint8_t> started = active;
+  std::vector<LdltStats> stats;
+  m_last_factorizations = ldlt_run_batch(
+      pol, active, /*launch_for_nobody=*/false,
+      [&](const std::vector<double>& d, const std::vector<double>& g, const std::vector<uint8_t>& a) {
+        prepare(d, g, a);
+        m_dev->system_written_by_caller(true, true);
+        m_dev->factor(d, g, a);
+        m_dev->read_stats(stats);
+        return stats.data();
+      },
+      &eliminated_min_pivot);
+  // (a problem accepted in an earlier launch kept its factors and its right-hand side: later launches skip it)
+  if (m_last_factorizations > 0) m_dev->solve();
+  std::vector<FactorInfo> info(B, FactorInfo::Success);
+  for (int b = 0; b < B; ++b)
+    if (started[b]) info[b] = remember(b, pol[b]);
+  return info;
+}
+
 bool NewtonSystem::factor_unregularized() {
   const int B = m_opt.batch;
   std::vector<double> zero(B, 0.0);

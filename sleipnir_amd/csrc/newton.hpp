@@ -117,6 +117,15 @@ class NewtonSystem {
   };
   bool last_hooked_chain_valid() const { return m_hooked_chain_valid; }
   std::vector<FactorInfo> compute_hooked(const AttemptHooks& hooks);
+  // The batched counterpart: the problems with mask[b] != 0, one attempt per launch, each with its own policy state
+  // and memory (the others are neither factored nor touched).  `prepare(delta[], gamma[], active[])` stands in front of
+  // every attempt and leaves lhs / rhs of the problems with active[b] != 0 in the batch-major arrays (lhs_raw / rhs_raw) —
+  // they take the route of a caller-written system, so every factorization family serves; the unregularized attempt is
+  // always made; `eliminated_min_pivot[b]` joins its |D| >= 1e-4 test.  The solution of every accepted attempt is in
+  // memory on return (one solve behind the loop).  No twin attempts and no look-ahead chain.
+  using BatchPrepare = std::function<void(const std::vector<double>&, const std::vector<double>&, const std::vector<uint8_t>&)>;
+  std::vector<FactorInfo> compute_hooked_batch(const BatchPrepare& prepare, const std::vector<uint8_t>& mask,
+                                               const std::vector<double>& eliminated_min_pivot);
   const std::vector<double>& hessian_regularization() const { return m_prev_delta; }
   const std::vector<double>& constraint_jacobian_regularization() const { return m_prev_gamma; }
   int last_factorizations() const { return m_last_factorizations; }

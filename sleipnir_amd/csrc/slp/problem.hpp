@@ -24,7 +24,9 @@
 
 #include "../ipm.hpp"
 #include "../eq_batch.hpp"
+#include "../fr_batch.hpp"
 #include "../ipm_batch.hpp"
+#include "../ipm_host.hpp"
 #include "../newton.hpp"
 #include "variable.hpp"
 
@@ -310,8 +312,8 @@ class ProblemF64 {
     if (!conflict) {
       const std::vector<double> x0v(x0, x0 + B * n);
       try {
-        if (m_i > 0) slpx::interior_point_batch(sys, *m_sys, scales, options, x0v, run, out);
-        else if (m_e > 0) slpx::sqp_batch(sys, *m_sys, scales, options, x0v, run, out);
+        if (m_i > 0) slpx::interior_point_batch(sys, *m_sys, scales, options, x0v, run, out, m_batch_restoration);
+        else if (m_e > 0) slpx::sqp_batch(sys, *m_sys, scales, options, x0v, run, out, m_batch_restoration);
         else slpx::newton_batch(sys, *m_sys, scales, options, x0v, run, out);
       } catch (...) {
         reinstall_scaling();
@@ -344,6 +346,95 @@ class ProblemF64 {
     m_scales = slpx::compute_problem_scaling(m_sys->structure(), V);
     dev.set_scaling(m_scales);
     return slpx::feasibility_restoration_steps(*m_sys, m_scales, options, x, s, y, z, mu, steps, &m_report);
+  }
+
+  // how solve_batch() runs feasibility restoration: 0 the hand-off to the batch-1 system (default), 1 in lockstep on the
+  // batch system (batch_lockstep.hpp)
+  void set_batch_restoration(int mode) {
+    if (mode != 0 && mode != 1) throw std::runtime_error("set_batch_restoration: mode must be 0 (hand-off) or 1 (lockstep)");
+    m_batch_restoration = mode;
+  }
+  int batch_restoration() const { return m_batch_restoration; }
+
+  // The batched twin of restoration_steps(): `steps` restoration iterations from each of `batch` iterates (x [B][n],
+  // s [B][m_i], y [B][m_e], z [B][m_i], mu [B]), in lockstep on the batch system (fr_batch.hpp: restoration_phase), with
+  // the one scaling restoration_steps() would use.  status [B]; stats: BatchRestorationStats of the phase.
+  std::vector<ExitStatus> restoration_steps_batch(const Options& options, int batch, std::vector<double>& x,
+                                                  std::vector<double>& s, std::vector<double>& y, std::vector<double>& z,
+                                                  const std::vector<double>& mu, int steps, slpx::BatchRestorationStats& stats) {
+    if (batch <= 0) throw std::runtime_error("restoration_steps_batch: batch must be positive");
+    if (has_callbacks()) throw std::runtime_error("restoration_steps_batch: the problem has callbacks registered");
+    auto& g = detail::G();
+    compile();
+    const auto& st = m_sys->structure();
+    const size_t B = static_cast<size_t>(batch), n = st.n, m_e = st.m_e, m_i = st.m_i;
+    if (x.size() != B * n || s.size() != B * m_i || y.size() != B * m_e || z.size() != B * m_i || mu.size() != B)
+      throw std::runtime_error("restoration_steps_batch: wrong lengths");
+    // the scaling of restoration_steps(): at the variables' current values
+    std::vector<double> x0(n);
+    for (size_t i = 0; i < n; ++i) x0[i] = g.val[m_decision_variables[i].expr];
+    std::vector<double> V(st.nV);
+    auto& dev = m_sys->device();
+    dev.set_scaling(std::vector<double>(st.n_scales(), 1.0));
+    std::vector<double> zeros_e(std::max<size_t>(1, m_e), 0.0), ones_i(std::max<size_t>(1, m_i), 1.0);
+    dev.upload_x(x0.data());
+    dev.upload_duals(ones_i.data(), zeros_e.data(), ones_i.data());
+    dev.sweep_full();
+    dev.download_V(V.data());
+    m_scales = slpx::compute_problem_scaling(st, V);
+    dev.set_scaling(m_scales);
+    // c_e, c_i, g at every instance's x: one batched sweep at unit scales, scaled here as the tape would
+    slpx::NewtonSystem& sys = batch_system(batch);
+    auto& bdev = sys.device();
+    std::vector<double> VB(B * st.nV), yb(std::max<size_t>(1, B * m_e), 0.0), sb(std::max<size_t>(1, B * m_i), 1.0);
+    bdev.upload_x(x.data());
+    bdev.upload_duals(sb.data(), yb.data(), sb.data());
+    bdev.sweep_full();
+    bdev.download_V(VB.data());
+    std::vector<slpx::BatchRestorationRequest> requests(B);
+    std::vector<int> iterations(B, 0);
+    std::vector<SolveReport> reports(B);
+    for (size_t b = 0; b < B; ++b) {
+      slpx::BatchRestorationRequest& r = requests[b];
+      r.b = static_cast<int>(b);
+      r.scales = m_scales;
+      r.mu = mu[b];
+      r.x.assign(x.begin() + b * n, x.begin() + (b + 1) * n);
+      r.s.assign(s.begin() + b * m_i, s.begin() + (b + 1) * m_i);
+      r.y.assign(y.begin() + b * m_e, y.begin() + (b + 1) * m_e);
+      r.z.assign(z.begin() + b * m_i, z.begin() + (b + 1) * m_i);
+      std::vector<double> Vb(VB.begin() + b * st.nV, VB.begin() + (b + 1) * st.nV);
+      for (int k = 0; k < st.nV; ++k)
+        if (st.V_scale_idx[k] >= 0) Vb[k] *= m_scales[st.V_scale_idx[k]];
+      slpx::ipm_host::VView cur{st, Vb};
+      r.c_e.assign(cur.c_e(), cur.c_e() + m_e);
+      r.c_i.assign(cur.c_i(), cur.c_i() + m_i);
+      r.g = cur.g_dense();
+      r.initial_violation = slpx::ipm_host::norm_1(r.c_e.data(), static_cast<int>(m_e));
+      for (size_t j = 0; j < m_i; ++j) r.initial_violation += std::abs(r.c_i[j] - r.s[j]);
+      r.outer_accepts = [](const slpx::FilterEntry&, double) { return false; };
+      r.iterations = &iterations[b];
+      r.rep = &reports[b];
+    }
+    slpx::BatchFrDevice frd(sys);
+    stats = slpx::BatchRestorationStats{};
+    try {
+      slpx::restoration_phase(sys, *m_sys, frd, options, requests, steps, std::chrono::steady_clock::now(), stats);
+    } catch (...) {
+      reinstall_scaling();
+      throw;
+    }
+    reinstall_scaling();
+    std::vector<ExitStatus> status(B);
+    for (size_t b = 0; b < B; ++b) {
+      const slpx::BatchRestorationRequest& r = requests[b];
+      status[b] = r.status;
+      std::copy(r.x.begin(), r.x.end(), x.begin() + b * n);
+      std::copy(r.s.begin(), r.s.end(), s.begin() + b * m_i);
+      std::copy(r.y.begin(), r.y.end(), y.begin() + b * m_e);
+      std::copy(r.z.begin(), r.z.end(), z.begin() + b * m_i);
+    }
+    return status;
   }
 
   // Compiles (once) the NLP for the device; exposed so harnesses can time setup
@@ -460,6 +551,7 @@ class ProblemF64 {
   std::vector<slpx::IterationCallback> m_iteration_callbacks, m_persistent_iteration_callbacks;
   std::unique_ptr<slpx::NewtonSystem> m_sys;
   std::map<int, std::unique_ptr<slpx::NewtonSystem>> m_batch_sys;  // solve_batch(), keyed by the batch size
+  int m_batch_restoration = 0;                                     // set_batch_restoration()
   std::vector<std::pair<NodeId, double>> m_param_snapshot;  // (parameter node, value at compile time)
   std::vector<double> m_scales, m_s, m_y, m_z;
   SolveReport m_report;

@@ -99,7 +99,9 @@ class BatchResult:
     s, z: (B, m_i), y: (B, m_e)), the unscaled cost, the iteration and restoration counts; `report` holds
     the batch's totals and wall-clock phases.  How the batch ran: `rounds` lockstep Newton-step computations,
     `handoffs` instances handed to the batch-1 system for restoration, `driver` 0 none needed, 1 interior
-    point, 2 SQP, 3 Newton."""
+    point, 2 SQP, 3 Newton.  `restoration_lockstep`: with restoration="lockstep", the instances restored in lockstep, the
+    restoration phases, the lockstep rounds of the restoration loop and the instances that used the batch-1 system for a
+    fallback (slpx_problem_batch_restoration_stats); all 0 with the hand-off."""
     status: list
     x: np.ndarray
     s: np.ndarray
@@ -112,6 +114,7 @@ class BatchResult:
     rounds: int = 0
     handoffs: int = 0
     driver: int = 0
+    restoration_lockstep: dict = dataclasses.field(default_factory=dict)
 
 
 class Problem:
@@ -195,10 +198,12 @@ class Problem:
         """B instances of this problem, one per row of `initial_guesses` (shape (B, n), decision-variable
         order), each solved as solve() would from that start, in one batched run on the device
         (slpx_problem_solve_batch).  Keyword arguments: tolerance, max_iterations, timeout, feasible_ipm
-        (the timeout covers the whole batch); diagnostics and spy are accepted and ignored.  The variables'
+        (the timeout covers the whole batch); diagnostics and spy are accepted and ignored; restoration = "handoff"
+        (default) or "lockstep": how instances that need feasibility restoration run it
+        (slpx_problem_set_batch_restoration).  The variables'
         values are left as they are.  Raises SlpxError where the library cannot run a batch (no device,
         callbacks registered)."""
-        allowed = {"tolerance", "max_iterations", "timeout", "feasible_ipm", "diagnostics", "spy"}
+        allowed = {"tolerance", "max_iterations", "timeout", "feasible_ipm", "diagnostics", "spy", "restoration"}
         for k in kwargs:
             if k not in allowed:
                 raise KeyError(f"Invalid keyword argument: {k}")
@@ -214,7 +219,14 @@ class Problem:
         r = self._p.solve_batch(guesses, timeout=timeout, **kwargs)
         return BatchResult(status=[ExitStatus(int(s)) for s in r["status"]], x=r["x"], s=r["s"], y=r["y"],
                            z=r["z"], cost=r["cost"], iterations=r["iterations"], restorations=r["restorations"],
-                           report=r["report"], rounds=r["rounds"], handoffs=r["handoffs"], driver=r["driver"])
+                           report=r["report"], rounds=r["rounds"], handoffs=r["handoffs"], driver=r["driver"],
+                           restoration_lockstep=r.get("restoration_lockstep", {}))
+
+    def restoration_steps_batch(self, x, s, y, z, mu, steps, **kwargs):
+        """`steps` iterations of feasibility restoration from each of B iterates (rows of x, s, y, z; mu of length B), in
+        lockstep on the device (slpx_problem_restoration_steps_batch).  Returns ([ExitStatus], x, s, y, z)."""
+        status, x, s, y, z = self._p.restoration_steps_batch(x, s, y, z, mu, steps, **kwargs)
+        return [ExitStatus(int(v)) for v in status], x, s, y, z
 
     def multistart(self, initial_guesses, **kwargs):
         """multistart.hpp:45-79 as one batched solve: every row of `initial_guesses` a start, then
