@@ -20,6 +20,11 @@
 //     update block) so a parent never reads a child's L.
 //   * triangular solves reuse the same tasks/rounds: forward bottom-up with
 //     contribution slots, backward top-down reading finished ancestors.
+//
+// The build is a list of phases (ldlt_symbolic.cpp: build_ldlt_plan_once) over the structs of
+// ldlt_symbolic_detail.hpp: ldlt_order.cpp (the ordering), ldlt_symbolic.cpp (pattern of L and tree, relaxed
+// supernodes, tasks, supernodes; the retry wrapper; the dense plan), ldlt_lists.cpp (entries, pair and solve lists,
+// the per-task arrays and their one table), ldlt_fronts.cpp (the multifrontal plan).
 #pragma once
 
 #include <cstdint>

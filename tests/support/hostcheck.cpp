@@ -159,6 +159,13 @@ static void hc_build(hc_handle* h, slpx_problem* p, const int32_t* perm, int32_t
     }
   if (const char* env = std::getenv("SLPX_RELAX_ZEROS")) lopt.relax_zeros = std::atoi(env);
   if (const char* env = std::getenv("SLPX_MFMA_MIN_ENTRIES")) lopt.mfma_min_entries = static_cast<uint32_t>(std::atoi(env));
+  // the product's other option sets (newton.cpp), for profiles/plan_hash_matrix.py: one problem with every round in
+  // one launch; the column-level plan of the batch-interleaved kernels with its task size
+  if (const char* env = std::getenv("SLPX_HOSTCHECK_SINGLE_PROBLEM_RULES")) lopt.single_problem_task_rules = env[0] != '0';
+  if (const char* env = std::getenv("SLPX_HOSTCHECK_COLUMN_PLAN")) {
+    lopt.supernodal = false;
+    lopt.task_entries = static_cast<uint32_t>(std::atoi(env));
+  }
   // (the product's rule, newton.cpp: plan_or_dense)
   const char* dense_env = std::getenv("SLPX_DENSE");
   if (h->k.reference_takes_dense(h->s.Ae.nnz()) && up.empty() && (dense_env == nullptr || dense_env[0] != '0') && h->k.dim <= 2048) {

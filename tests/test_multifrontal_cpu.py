@@ -175,7 +175,7 @@ def test_a_new_right_hand_side_through_the_fronts(fresh, slpx, orc, hostcheck, m
 
 
 def test_the_baseline_models_get_the_multifrontal_plan(fresh, slpx, orc, hostcheck, mf):
-    """A refused multifrontal plan (ldlt_symbolic.cpp: MfRefused, or a limit of the fronts' 16-bit addressing) degrades
+    """A refused multifrontal plan (ldlt_fronts.cpp: MfRefused, or a limit of the fronts' 16-bit addressing) degrades
     to the pair-list plan: a slower step, and nothing else would tell.  The BASELINE configurations must not get there
     (cart-pole N=1000 and N=5000, g-fold N=100)."""
     from tests.support import gfold, model

@@ -99,7 +99,7 @@ def test_ocp_helper_flywheel_known_answer_on_the_gpu(slpx, method, kind, steps):
 @pytest.mark.gpu
 def test_ocp_helper_shared_timestep_is_a_hub_the_ordering_sets_aside(slpx):
     """TimestepMethod::VARIABLE_SINGLE: one decision variable in every dynamics row.  Level-set
-    nested dissection cannot separate anything while it is in the graph (ldlt_symbolic.cpp: hubs
+    nested dissection cannot separate anything while it is in the graph (ldlt_order.cpp: hubs
     are eliminated last); the larger timestep wins (the cost is a tracking error)."""
     build_ocp_program(slpx) if not _fresh(OCP_BIN, OCP_SRC, slpx) else None
     res = subprocess.run([str(OCP_BIN), "0", "0", "200", "shared-dt"], capture_output=True, text=True, timeout=900)
