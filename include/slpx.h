@@ -223,6 +223,39 @@ int slpx_problem_restoration_steps(slpx_problem* p, const slpx_options* opt, dou
  * compiles anything).  Returns the number of generated bodies, < 0 on failure. */
 int slpx_problem_prebuild_kernels(slpx_problem* p, const char* dir);
 
+/* ---- parameters as runtime inputs -------------------------------------------------
+ * A free variable (slpx_expr_variable) that is no decision variable of the problem and that the cost or a constraint
+ * reaches is a PARAMETER of the model: an initial state, a reference, a bound, a weight.  Its value lives in a slot of
+ * the compiled tapes' constant pool, so it can change without compiling anything again, and a batch can carry a pool
+ * per instance.  (slpx_expr_set_value on a parameter keeps doing what it did: the next solve notices and compiles a
+ * new system.)  The entry points of this section (and slpx_system_set_parameters / slpx_system_parameter_pool_bytes
+ * below) are additions within ABI version 6, detected by the symbol's presence like slpx_problem_solve_batch.
+ *
+ * slpx_problem_parameters: the number n_p of parameters the model reaches; their expression ids, ascending, into
+ * ids[0 .. min(n_p, capacity)) when ids is not NULL.  That order is the order of every parameter vector below.  Needs
+ * NO device: where the problem has no compiled system the model's structure is compiled on the host for the answer
+ * (the path of slpx_problem_prebuild_kernels).  < 0: -100 + slpx_last_error(). */
+int32_t slpx_problem_parameters(slpx_problem* p, int32_t* ids, int32_t capacity);
+/* Without a device: 1 if parameter j sits in constant slot j of both tape programs (full sweep and values only), which
+ * the tape compiler promises (it hands out the parameters' slots first, in the order above), 0 if not; < 0 on error. */
+int slpx_problem_parameter_slots_in_order(slpx_problem* p);
+/* values[n_p] become the parameters' values: in the expression graph, and IN PLACE in the problem's compiled system
+ * and every batch system it holds (compiled now if there was none).  The next slpx_problem_solve / _solve_batch /
+ * slpx_problem_system does not compile again, and a handle from slpx_problem_system taken before stays valid.
+ * Returns 0, or -100 + slpx_last_error() (null problem or values, no device). */
+int slpx_problem_set_parameters(slpx_problem* p, const double* values);
+/* How many times this problem has built the system slpx_problem_solve runs on. */
+int64_t slpx_problem_compile_count(const slpx_problem* p);
+/* slpx_problem_solve_batch where instance b is the problem with the parameter row params[b][n_p], solved from x0[b];
+ * params NULL: exactly slpx_problem_solve_batch.  The bounds test (GLOBALLY_INFEASIBLE) is made per instance.  The
+ * variables' and the parameters' values are left as they are, and on return every system of the problem reads the
+ * parameters' current values again.  -100 + slpx_last_error() additionally for params given to a model without
+ * parameters. */
+int slpx_problem_solve_batch_parameters(slpx_problem* p, int32_t batch, const double* x0, const double* params,
+                                        const slpx_options* opt, uint32_t options_bytes, int32_t* status, double* x,
+                                        double* s, double* y, double* z, double* cost, int32_t* iterations,
+                                        int32_t* restorations, slpx_report* report);
+
 /* ---- compiled Newton system ------------------------------------------------------
  * One problem structure compiled for one GPU, `batch` independent value sets.
  * Replaces, per Newton step:
@@ -271,6 +304,17 @@ int slpx_system_perm(const slpx_system* s, int32_t* perm); /* fill-reducing perm
 
 /* scales = [d_f, d_ce(m_e), d_ci(m_i)] (util/problem_scaling.hpp:100-107) */
 int slpx_system_set_scaling(slpx_system* s, const double* scales);
+/* The parameters of the model (slpx_problem_parameters: count and order) at the compiled-system seam, for callers of
+ * slpx_tape_sweep / slpx_newton_step.  per_instance 0: values[n_p] for every instance (one shared constant pool);
+ * 1: values[batch][n_p], instance b reads row b (a pool per instance, in force until the next call with 0).  The
+ * expression graph is not touched: a system borrowed from a problem is better served by slpx_problem_set_parameters.
+ * Returns 0, or -100 + slpx_last_error() (null system or values; per_instance with a model without parameters).  An
+ * addition within ABI version 6, detected by the symbol's presence like slpx_problem_solve_batch. */
+int slpx_system_set_parameters(slpx_system* s, const double* values, int per_instance);
+/* Device memory the per-instance constant pools of this system take: batch x (constants of the full program +
+ * constants of the values-only program) x 8 bytes once per-instance values were installed, 0 before.  < 0: -100 +
+ * slpx_last_error().  An addition within ABI version 6, detected like the one above. */
+int64_t slpx_system_parameter_pool_bytes(slpx_system* s);
 /* x[batch][n], s[batch][m_i], y[batch][m_e], z[batch][m_i], mu[batch] (any may be NULL = keep) */
 int slpx_system_set_state(slpx_system* s, const double* x, const double* sl, const double* y,
                           const double* z, const double* mu);

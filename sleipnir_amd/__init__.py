@@ -181,6 +181,15 @@ def lib() -> ctypes.CDLL:
     if hasattr(L, "slpx_ldlt_error_bounds"):
         sig("slpx_ldlt_error_bounds", ctypes.c_int, vp, vp, vp, vp, vp)
         sig("slpx_ldlt_condest", ctypes.c_int, vp, vp, vp, vp, vp)
+    if hasattr(L, "slpx_problem_set_parameters"):
+        sig("slpx_problem_parameters", i32, vp, vp, i32)
+        sig("slpx_problem_parameter_slots_in_order", ctypes.c_int, vp)
+        sig("slpx_problem_set_parameters", ctypes.c_int, vp, vp)
+        sig("slpx_problem_compile_count", i64, vp)
+        sig("slpx_problem_solve_batch_parameters", ctypes.c_int, vp, i32, vp, vp, ctypes.POINTER(Options), ctypes.c_uint32,
+            vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(Report))
+        sig("slpx_system_set_parameters", ctypes.c_int, vp, vp, ctypes.c_int)
+        sig("slpx_system_parameter_pool_bytes", i64, vp)
     _lib = L
     return L
 
@@ -271,7 +280,8 @@ class Problem:
 
     RESTORATION_MODES = {"handoff": 0, "lockstep": 1}
 
-    def solve_batch(self, x0, tolerance=1e-8, max_iterations=5000, timeout=0.0, feasible_ipm=False, restoration="handoff"):
+    def solve_batch(self, x0, tolerance=1e-8, max_iterations=5000, timeout=0.0, feasible_ipm=False, restoration="handoff",
+                    parameters=None):
         """B instances from the rows of x0 (B x n), each as solve() from that start
         (slpx_problem_solve_batch).  Returns a dict of arrays: status, x, s, y, z, cost, iterations,
         restorations, the batch's report, and how the batch ran (slpx_problem_batch_stats): rounds (lockstep
@@ -281,8 +291,12 @@ class Problem:
         system while the batch waits) or "lockstep" (all instances that ask in one round run one restoration phase
         together on the batch system; slpx_problem_set_batch_restoration).  "restoration_lockstep" in the result is
         slpx_problem_batch_restoration_stats: instances restored in lockstep, phases, lockstep restoration rounds,
-        instances that used the batch-1 system for the KKT-error fallback."""
+        instances that used the batch-1 system for the KKT-error fallback.
+        parameters: None, or (B x n_p) — instance b is the problem with parameter row b, the order of parameters()
+        (slpx_problem_solve_batch_parameters)."""
         L = lib()
+        if parameters is not None and not hasattr(L, "slpx_problem_solve_batch_parameters"):
+            raise SlpxError(f"{LIB_PATH} has no slpx_problem_solve_batch_parameters")
         if not hasattr(L, "slpx_problem_solve_batch"):
             raise SlpxError(f"{LIB_PATH} has no slpx_problem_solve_batch")
         if restoration not in self.RESTORATION_MODES:
@@ -301,10 +315,20 @@ class Problem:
                "iterations": np.zeros(B, dtype=np.int32), "restorations": np.zeros(B, dtype=np.int32)}
         opt = Options(tolerance, max_iterations, timeout, int(feasible_ipm), 0, 0)
         rep = Report()
-        rc = L.slpx_problem_solve_batch(self._h, B, x0.ctypes.data if B else None, ctypes.byref(opt),
-                                        ctypes.sizeof(Options), *(out[k].ctypes.data for k in
-                                        ("status", "x", "s", "y", "z", "cost", "iterations", "restorations")),
-                                        ctypes.byref(rep))
+        outputs = [out[k].ctypes.data for k in ("status", "x", "s", "y", "z", "cost", "iterations", "restorations")]
+        if parameters is None:
+            rc = L.slpx_problem_solve_batch(self._h, B, x0.ctypes.data if B else None, ctypes.byref(opt),
+                                            ctypes.sizeof(Options), *outputs, ctypes.byref(rep))
+        else:
+            rows = np.ascontiguousarray(np.asarray(parameters, dtype=np.float64))
+            if rows.ndim != 2 or rows.shape[0] != B:
+                raise ValueError(f"parameters must have shape ({B}, n_p): one row per instance")
+            n_p = len(self.parameters())
+            if rows.shape[1] != n_p:
+                raise ValueError(f"parameters must have {n_p} columns, the model's parameters")
+            rc = L.slpx_problem_solve_batch_parameters(self._h, B, x0.ctypes.data if B else None,
+                                                       rows.ctypes.data if rows.size else None, ctypes.byref(opt),
+                                                       ctypes.sizeof(Options), *outputs, ctypes.byref(rep))
         if rc != 0:
             raise SlpxError(L.slpx_last_error().decode())
         out["report"] = {f[0]: getattr(rep, f[0]) for f in Report._fields_}
@@ -312,6 +336,38 @@ class Problem:
         if hasattr(L, "slpx_problem_batch_restoration_stats"):
             out["restoration_lockstep"] = dict(zip(("instances", "phases", "rounds", "fallbacks"), self.batch_restoration_stats()))
         return out
+
+    def parameters(self) -> list:
+        """Expression ids of the model's parameters — free variables that are no decision variables and that the cost
+        or a constraint reaches — ascending: the order of every parameter vector (slpx_problem_parameters; no device)."""
+        L = lib()
+        if not hasattr(L, "slpx_problem_parameters"):
+            raise SlpxError(f"{LIB_PATH} has no slpx_problem_parameters")
+        count = _check(L.slpx_problem_parameters(self._h, None, 0))
+        ids = np.zeros(max(count, 1), dtype=np.int32)
+        _check(L.slpx_problem_parameters(self._h, ids.ctypes.data, count))
+        return [int(v) for v in ids[:count]]
+
+    def parameter_slots_in_order(self) -> bool:
+        """Parameter j sits in constant slot j of both tape programs (slpx_problem_parameter_slots_in_order; no device)."""
+        return bool(_check(lib().slpx_problem_parameter_slots_in_order(self._h)))
+
+    def set_parameters(self, values):
+        """New values for all parameters, in place in every compiled system of the problem: the next solve does not
+        compile again (slpx_problem_set_parameters)."""
+        L = lib()
+        if not hasattr(L, "slpx_problem_set_parameters"):
+            raise SlpxError(f"{LIB_PATH} has no slpx_problem_set_parameters")
+        v = np.ascontiguousarray(np.asarray(values, dtype=np.float64).ravel())
+        n_p = len(self.parameters())
+        if v.shape[0] != n_p:
+            raise ValueError(f"set_parameters: {n_p} values, one per parameter")
+        if L.slpx_problem_set_parameters(self._h, v.ctypes.data if v.size else None) != 0:
+            raise SlpxError(L.slpx_last_error().decode())
+
+    def compile_count(self) -> int:
+        """How many times this problem built the system solve() runs on (slpx_problem_compile_count)."""
+        return int(lib().slpx_problem_compile_count(self._h))
 
     def batch_stats(self):
         """(batch, rounds, handoffs, driver) of the last solve_batch (slpx_problem_batch_stats)."""
@@ -474,6 +530,17 @@ class System:
     def set_scaling(self, scales):
         s = _f64(scales)
         _check(lib().slpx_system_set_scaling(self._h, s.ctypes.data))
+
+    def set_parameters(self, values, per_instance=False):
+        """The model's parameters at this system: values (n_p) for every instance, or per_instance (batch x n_p)
+        (slpx_system_set_parameters)."""
+        v = np.ascontiguousarray(np.asarray(values, dtype=np.float64))
+        _check(lib().slpx_system_set_parameters(self._h, v.ctypes.data if v.size else None, int(per_instance)))
+
+    def parameter_pool_bytes(self) -> int:
+        """Device memory of the per-instance constant pools (slpx_system_parameter_pool_bytes); 0 before the first
+        per-instance install."""
+        return int(_check(lib().slpx_system_parameter_pool_bytes(self._h)))
 
     def set_state(self, x=None, s=None, y=None, z=None, mu=None):
         x, s, y, z, mu = (_f64(a) for a in (x, s, y, z, mu))

@@ -177,7 +177,8 @@ struct NewtonDriver : EqDriver {
 
 template <class Driver>
 void lockstep(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales, const Options& options,
-              const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out, int restoration_mode) {
+              const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out, int restoration_mode,
+              const std::vector<double>* instance_params) {
   const auto solve_start = clk::now();
   const NlpStructure& st = sys.structure();
   DeviceNlp& dev = sys.device();
@@ -186,6 +187,13 @@ void lockstep(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>
   if (static_cast<int>(x0.size()) != B * n || static_cast<int>(scales.size()) != B * ns || static_cast<int>(run.size()) != B)
     throw std::runtime_error(name + ": wrong lengths");
   if (!Driver::takes(st)) throw std::runtime_error(name + ": " + Driver::kModels);
+  // per-instance parameters: row b of instance_params
+  const size_t n_p = instance_params ? st.parameter_nodes().size() : 0;
+  if (instance_params && (n_p == 0 || instance_params->size() != static_cast<size_t>(B) * n_p))
+    throw std::runtime_error(name + ": wrong length of the per-instance parameters");
+  auto params_of = [&](int b) {
+    return n_p ? Vec(instance_params->begin() + static_cast<size_t>(b) * n_p, instance_params->begin() + static_cast<size_t>(b + 1) * n_p) : Vec{};
+  };
   SolveReport& rep = out.report;
   out.driver = Driver::kId;
   out.rounds = out.handoffs = 0;
@@ -347,6 +355,7 @@ void lockstep(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>
         BatchRestorationRequest r;
         r.b = b;
         r.scales = I.scales;
+        r.params = params_of(b);
         r.mu = drv.restoration_mu(I);
         Vec V;
         bd.get_instance(b, r.x, r.s, r.y, r.z, V);
@@ -397,6 +406,7 @@ void lockstep(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>
         return I.filter->try_add(initial_entry, trial_entry, D_phi_restoration, Driver::search(I).alpha);
       };
       single.device().set_scaling(I.scales);
+      if (n_p) single.device().set_parameters(params_of(b).data(), /*per_instance=*/false);
       const auto reg = sys.regularization_state();
       single.set_regularization_state({{reg.first[b]}, {reg.second[b]}});
       const ExitStatus fr_status = feasibility_restoration_handoff(single, I.scales, outer_accepts, options, x, s, y, z,
@@ -470,18 +480,20 @@ void lockstep(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>
 
 void interior_point_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales,
                           const Options& options, const std::vector<double>& x0, const std::vector<uint8_t>& run,
-                          BatchSolveResult& out, int restoration_mode) {
-  lockstep<IpmDriver>(sys, single, scales, options, x0, run, out, restoration_mode);
+                          BatchSolveResult& out, int restoration_mode, const std::vector<double>* instance_params) {
+  lockstep<IpmDriver>(sys, single, scales, options, x0, run, out, restoration_mode, instance_params);
 }
 
 void sqp_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales, const Options& options,
-               const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out, int restoration_mode) {
-  lockstep<SqpDriver>(sys, single, scales, options, x0, run, out, restoration_mode);
+               const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out, int restoration_mode,
+               const std::vector<double>* instance_params) {
+  lockstep<SqpDriver>(sys, single, scales, options, x0, run, out, restoration_mode, instance_params);
 }
 
 void newton_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales, const Options& options,
-                  const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out) {
-  lockstep<NewtonDriver>(sys, single, scales, options, x0, run, out, /*restoration_mode=*/0);
+                  const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out,
+                  const std::vector<double>* instance_params) {
+  lockstep<NewtonDriver>(sys, single, scales, options, x0, run, out, /*restoration_mode=*/0, instance_params);
 }
 
 }  // namespace slpx

@@ -126,12 +126,20 @@ struct BatchSolveResult {
 // restoration_mode 0: an instance that asks for feasibility restoration is handed to `single`, one after the other
 // (the default); 1: all instances that ask in one round enter one restoration phase on the batch system, in lockstep
 // (fr_batch.hpp: restoration_phase).
+// instance_params (null: every instance is the model as compiled): [B][n_p] parameter rows (NlpStructure::
+// parameter_nodes order) that the caller has INSTALLED per instance on `sys` (DeviceNlp::set_parameters); wherever
+// `single` works for an instance — the restoration hand-off, the KKT-error fallback and the multiplier estimate of a
+// lockstep phase — that instance's row is installed there first, as its scaling is.  The caller puts `single`'s own
+// values back afterwards, as it does the scaling.
 void interior_point_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales,
                           const Options& options, const std::vector<double>& x0, const std::vector<uint8_t>& run,
-                          BatchSolveResult& out, int restoration_mode = 0);
+                          BatchSolveResult& out, int restoration_mode = 0,
+                          const std::vector<double>* instance_params = nullptr);
 void sqp_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales, const Options& options,
-               const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out, int restoration_mode = 0);
+               const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out, int restoration_mode = 0,
+               const std::vector<double>* instance_params = nullptr);
 void newton_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales, const Options& options,
-                  const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out);
+                  const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out,
+                  const std::vector<double>* instance_params = nullptr);
 
 }  // namespace slpx

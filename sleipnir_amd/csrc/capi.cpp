@@ -5,6 +5,7 @@
 #include <cstddef>
 #include <cstring>
 #include <memory>
+#include <span>
 #include <string>
 #include <vector>
 
@@ -33,6 +34,26 @@ int guard(F&& f) {
   }
 }
 }  // namespace
+
+namespace slpx {
+// The parameters of the problem's model (NlpStructure::parameter_nodes) without a device: from the compiled system
+// where there is one that is current, else from the model's structure compiled on the host (what
+// slpx_problem_prebuild_kernels does).  in_order: NlpStructure::parameter_slots_in_order of the same structure.
+std::vector<NodeId> problem_parameter_nodes(slpx_problem& p, bool* in_order) {
+  auto answer = [&](const NlpStructure& st) {
+    if (in_order) *in_order = st.parameter_slots_in_order();
+    return st.parameter_nodes();
+  };
+  // (a changed parameter VALUE makes the next compile() build anew, but the structure it builds is this one)
+  if (const NewtonSystem* sys = p.problem.compiled()) return answer(sys->structure());
+  std::vector<NodeId> xs, ce, ci;
+  for (auto& v : p.problem.decision_variables()) xs.push_back(v.expr);
+  for (auto& v : p.problem.equality_constraints()) ce.push_back(v.expr);
+  for (auto& v : p.problem.inequality_constraints()) ci.push_back(v.expr);
+  const NodeId f = p.problem.cost_function_type() == slp::ExpressionType::NONE ? kNull : p.problem.cost().expr;
+  return answer(build_nlp_structure(graph(), xs, f, ce, ci, TapeCompileOptions{}));
+}
+}  // namespace slpx
 
 extern "C" {
 
@@ -146,6 +167,14 @@ int slpx_problem_solve_sized(slpx_problem* p, const slpx_options* o, uint32_t op
 int slpx_problem_solve_batch(slpx_problem* p, int32_t batch, const double* x0, const slpx_options* o, uint32_t options_bytes,
                              int32_t* status, double* x, double* sv, double* y, double* z, double* cost, int32_t* iterations,
                              int32_t* restorations, slpx_report* report) {
+  return slpx_problem_solve_batch_parameters(p, batch, x0, nullptr, o, options_bytes, status, x, sv, y, z, cost, iterations,
+                                             restorations, report);
+}
+
+int slpx_problem_solve_batch_parameters(slpx_problem* p, int32_t batch, const double* x0, const double* params,
+                                        const slpx_options* o, uint32_t options_bytes, int32_t* status, double* x, double* sv,
+                                        double* y, double* z, double* cost, int32_t* iterations, int32_t* restorations,
+                                        slpx_report* report) {
   (void)options_bytes;  // (every member read here predates `spy`, the only one a shorter struct lacks)
   return guard([&] {
     if (p == nullptr) throw std::runtime_error("slpx_problem_solve_batch: null problem");
@@ -161,7 +190,7 @@ int slpx_problem_solve_batch(slpx_problem* p, int32_t batch, const double* x0, c
       if (o->timeout > 0) opt.timeout = o->timeout;
       opt.feasible_ipm = o->feasible_ipm != 0;
     }
-    const slpx::BatchSolveResult r = p->problem.solve_batch(batch, x0, opt);
+    const slpx::BatchSolveResult r = p->problem.solve_batch(batch, x0, params, opt);
     const size_t B = static_cast<size_t>(batch);
     p->batch_stats[0] = batch;
     p->batch_stats[1] = r.rounds;
@@ -340,6 +369,53 @@ int slpx_problem_prebuild_kernels(slpx_problem* p, const char* dir) {
     // (feasibility restoration has no kernels of its own to generate: it runs on this system, csrc/restoration.hpp)
   });
   return rc == 0 ? bodies : rc;
+}
+
+int32_t slpx_problem_parameters(slpx_problem* p, int32_t* ids, int32_t capacity) {
+  int32_t count = -1;
+  const int rc = guard([&] {
+    if (p == nullptr) throw std::runtime_error("slpx_problem_parameters: null problem");
+    const std::vector<slpx::NodeId> nodes = slpx::problem_parameter_nodes(*p, nullptr);
+    count = static_cast<int32_t>(nodes.size());
+    if (ids)
+      for (int32_t j = 0; j < count && j < capacity; ++j) ids[j] = nodes[j];
+  });
+  return rc == 0 ? count : rc;
+}
+int slpx_problem_parameter_slots_in_order(slpx_problem* p) {
+  bool in_order = false;
+  const int rc = guard([&] {
+    if (p == nullptr) throw std::runtime_error("slpx_problem_parameter_slots_in_order: null problem");
+    (void)slpx::problem_parameter_nodes(*p, &in_order);
+  });
+  return rc == 0 ? (in_order ? 1 : 0) : rc;
+}
+int slpx_problem_set_parameters(slpx_problem* p, const double* values) {
+  return guard([&] {
+    if (p == nullptr) throw std::runtime_error("slpx_problem_set_parameters: null problem");
+    if (values == nullptr) throw std::runtime_error("slpx_problem_set_parameters: values is null");
+    if (slpx_device_count() < 1) throw std::runtime_error("slpx_problem_set_parameters: no HIP device");
+    const size_t n_p = p->problem.parameters().size();
+    p->problem.set_parameters(std::span<const double>(values, n_p));
+  });
+}
+int64_t slpx_problem_compile_count(const slpx_problem* p) { return p ? p->problem.compile_count() : -1; }
+
+int slpx_system_set_parameters(slpx_system* s, const double* values, int per_instance) {
+  return guard([&] {
+    if (s == nullptr) throw std::runtime_error("slpx_system_set_parameters: null system");
+    if (values == nullptr) throw std::runtime_error("slpx_system_set_parameters: values is null");
+    if (per_instance != 0 && per_instance != 1) throw std::runtime_error("slpx_system_set_parameters: per_instance must be 0 or 1");
+    s->get().device().set_parameters(values, per_instance != 0);
+  });
+}
+int64_t slpx_system_parameter_pool_bytes(slpx_system* s) {
+  int64_t bytes = -1;
+  const int rc = guard([&] {
+    if (s == nullptr) throw std::runtime_error("slpx_system_parameter_pool_bytes: null system");
+    bytes = static_cast<int64_t>(s->get().device().parameter_pool_bytes());
+  });
+  return rc == 0 ? bytes : rc;
 }
 
 slpx_system* slpx_system_create(slpx_problem* p, int32_t batch, int32_t device, const int32_t* perm,

@@ -147,6 +147,13 @@ struct TapeDevice {
       jout_slot, jout_dst;
   DevBuf<int32_t> vout_scale, jout_scale;
   DevBuf<double> consts;
+  // Per-instance parameters (DeviceNlp::set_parameters): [batch][n_consts], the WHOLE pool of every instance —
+  // parameter slots with the instance's values, literals replicated — allocated when per-instance values are first
+  // installed; consts_stride = n_consts while it is in force, 0 while `consts` (shared) is.  Replicated rather than
+  // split into "parameters per instance + literals shared": the kernels keep ONE base pointer, a leaf stays
+  // "constant slot k" (no new leaf kind), and the leaf tables and generated index words do not change.
+  DevBuf<double> consts_inst;
+  uint32_t consts_stride = 0;
   DevBuf<TapeEdge> edges;
   DevBuf<uint16_t> node_rec16, slot_edge_ptr16, edges16;
   uint32_t n_small = 0, n_large = 0, n_global = 0;
@@ -466,6 +473,14 @@ class DeviceNlp {
   // Re-reads the values of the tapes' parameter leaves (free Variables that are not
   // decision variables) from the graph and refreshes their constant slots.
   void refresh_params(const Graph& g);
+  // The same with caller-given values, in the order of NlpStructure::parameter_nodes() (ascending node id).
+  // shared: values[n_p] into the parameter slots of the one pool every instance reads (and that pool is in force);
+  // per instance: values[batch][n_p], instance b's row into its own pool (TapeDevice::consts_inst), in force until
+  // the next shared install.  Buffers are rewritten in place: nothing that holds a pointer to them goes stale.
+  void set_parameters(const double* values, bool per_instance);
+  bool parameters_per_instance() const { return m_full.consts_stride != 0 || m_values.consts_stride != 0; }
+  // bytes of the per-instance pools of both programs (0 until per-instance values were installed)
+  size_t parameter_pool_bytes() const { return (m_full.consts_inst.n + m_values.consts_inst.n) * sizeof(double); }
   void debug_tape_clocks(unsigned long long* out16);
   // SLPX_TAPE_JIT_CLOCKS=1: 8 wall clocks (tape_jit.cpp) for each of the first `blocks` workgroups of the
   // generated kernel's last launch; returns the number of template workgroups, -1 if absent

@@ -95,6 +95,9 @@ struct BatchFrDevice : BatchDevice {
 struct BatchRestorationRequest {
   int b = 0;
   std::vector<double> scales;  // [d_f | d_ce | d_ci] of the instance
+  // the instance's parameter row (NlpStructure::parameter_nodes order) where the batch runs with per-instance
+  // parameters, empty otherwise: installed on the batch-1 system before it works for this instance
+  std::vector<double> params;
   double mu = 0.0;
   std::vector<double> x, s, y, z, c_e, c_i, g;
   double initial_violation = 0.0;

@@ -266,6 +266,7 @@ void restoration_phase(NewtonSystem& sys, NewtonSystem& single, BatchFrDevice& f
         // A_e, A_i at the trial point: a full sweep there
         DeviceNlp& one = single.device();
         one.set_scaling(I.req->scales);
+        if (!I.req->params.empty()) one.set_parameters(I.req->params.data(), /*per_instance=*/false);
         one.upload_x(Xt.data());
         one.upload_duals(St.data(), yt.data(), Zt.data());
         one.sweep_full();
@@ -316,6 +317,7 @@ void restoration_phase(NewtonSystem& sys, NewtonSystem& single, BatchFrDevice& f
     if (I.core == ExitStatus::CALLBACK_REQUESTED_STOP) {
       // back to the original problem: least-squares multipliers at the new point (:606-617), on the batch-1 system
       single.device().set_scaling(r.scales);
+      if (!r.params.empty()) single.device().set_parameters(r.params.data(), /*per_instance=*/false);
       r.status = restoration_multiplier_estimate(single, r.x, r.s, r.y, r.z, r.mu, *r.rep) ? ExitStatus::SUCCESS : ExitStatus::FACTORIZATION_FAILED;
     } else if (I.core == ExitStatus::SUCCESS) {
       r.status = ExitStatus::LOCALLY_INFEASIBLE;

@@ -502,10 +502,10 @@ void TapeDevice::upload(const TapeProgram& p, int batch, uint32_t n_unscaled_inp
 }
 
 TapeDev TapeDevice::view() const {
-  return TapeDev{tasks.p,         leaf_src.p,   consts.p,   node_rec.p,   lvl_ptr.p,
+  return TapeDev{tasks.p,         leaf_src.p,   consts_stride ? consts_inst.p : consts.p,   node_rec.p,   lvl_ptr.p,
                  slot_edge_ptr.p, slvl_ptr.p,   edges.p,    vout_src.p,   vout_dst.p,
                  vout_scale.p,    jout_slot.p,  jout_dst.p, jout_scale.p, node_rec16.p,
-                 slot_edge_ptr16.p, edges16.p};
+                 slot_edge_ptr16.p, edges16.p,  consts_stride};
 }
 
 DeviceNlp::DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l, int batch,
@@ -1542,15 +1542,50 @@ void DeviceNlp::debug_ldlt_clocks(unsigned int next_round, unsigned long long* o
 }
 
 void DeviceNlp::refresh_params(const Graph& g) {
-  SLPX_HIP_CHECK(hipStreamSynchronize(m_stream));
-  auto refresh = [&](const TapeProgram& prog, TapeDevice& dev) {
+  std::vector<double> values;
+  for (NodeId node : m_s_ref.parameter_nodes()) values.push_back(g.val[node]);
+  set_parameters(values.data(), /*per_instance=*/false);
+}
+
+void DeviceNlp::set_parameters(const double* values, bool per_instance) {
+  const std::vector<NodeId> nodes = m_s_ref.parameter_nodes();
+  if (nodes.empty()) {
+    if (per_instance) throw std::runtime_error("slpx: set_parameters: the model has no parameters");
+    return;
+  }
+  if (values == nullptr) throw std::runtime_error("slpx: set_parameters: values is null");
+  SLPX_HIP_CHECK(hipStreamSynchronize(m_stream));  // (no sweep in flight reads the pool that is rewritten)
+  const size_t n_p = nodes.size(), B = static_cast<size_t>(m_batch);
+  auto install = [&](const TapeProgram& prog, TapeDevice& dev) {
     if (prog.params.empty()) return;
-    std::vector<double> c = prog.consts;
-    for (const auto& [node, slot] : prog.params) c[slot] = g.val[node];
-    dev.consts.upload(c);
+    const size_t nc = prog.consts.size();
+    // where parameter j of the caller's vector sits in this program's pool (slot j: both programs claim
+    // `param_order` first — looked up all the same, so that a program that reaches fewer parameters is served too)
+    std::vector<std::pair<size_t, uint32_t>> slot_of;  // (j, slot)
+    for (const auto& [node, slot] : prog.params) {
+      const size_t j = static_cast<size_t>(std::lower_bound(nodes.begin(), nodes.end(), node) - nodes.begin());
+      if (slot >= nc) throw std::runtime_error("slpx: set_parameters: a parameter slot outside the constant pool");
+      slot_of.emplace_back(j, slot);
+    }
+    if (!per_instance) {
+      std::vector<double> c = prog.consts;
+      for (const auto& [j, slot] : slot_of) c[slot] = values[j];
+      SLPX_HIP_CHECK(hipMemcpy(dev.consts.p, c.data(), nc * sizeof(double), hipMemcpyHostToDevice));
+      dev.consts_stride = 0;
+      return;
+    }
+    std::vector<double> c(B * nc);
+    for (size_t b = 0; b < B; ++b) {
+      std::copy(prog.consts.begin(), prog.consts.end(), c.begin() + b * nc);
+      for (const auto& [j, slot] : slot_of) c[b * nc + slot] = values[b * n_p + j];
+    }
+    if (dev.consts_inst.n != c.size()) dev.consts_inst.alloc(c.size());
+    SLPX_HIP_CHECK(hipMemcpy(dev.consts_inst.p, c.data(), c.size() * sizeof(double), hipMemcpyHostToDevice));
+    dev.consts_stride = static_cast<uint32_t>(nc);
   };
-  refresh(m_s_ref.full, m_full);
-  refresh(m_s_ref.values, m_values);
+  install(m_s_ref.full, m_full);
+  install(m_s_ref.values, m_values);
+  // (a program without parameters keeps its shared pool, stride 0, in either mode)
 }
 
 void DeviceNlp::build_rhs() {

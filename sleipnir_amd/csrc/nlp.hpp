@@ -9,6 +9,7 @@
 // line-search trial points, interior_point.hpp:513-527).
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <functional>
 #include <vector>
@@ -50,6 +51,28 @@ struct NlpStructure {
   // bookkeeping for reports
   size_t graph_nodes_before = 0, graph_nodes_after = 0;
   int nonlinear_rows = 0, linear_rows = 0;
+
+  // The model's parameters — free Variables that are not decision variables — that the two programs reach, in
+  // ascending node order: the order of every parameter vector of the public interface.  Both programs claim their
+  // parameters' slots first and in this order (tape_compiler.cpp, `param_order`), so slot j is parameter j in a
+  // program that reaches all of them (parameter_slots_in_order).
+  std::vector<NodeId> parameter_nodes() const {
+    std::vector<NodeId> nodes;
+    for (const TapeProgram* prog : {&full, &values})
+      for (const auto& [node, slot] : prog->params) nodes.push_back(node);
+    std::sort(nodes.begin(), nodes.end());
+    nodes.erase(std::unique(nodes.begin(), nodes.end()), nodes.end());
+    return nodes;
+  }
+  bool parameter_slots_in_order() const {
+    const std::vector<NodeId> nodes = parameter_nodes();
+    for (const TapeProgram* prog : {&full, &values}) {
+      if (prog->params.size() != nodes.size()) return false;
+      for (const auto& [node, slot] : prog->params)
+        if (slot >= nodes.size() || nodes[slot] != node) return false;
+    }
+    return true;
+  }
 
   int n_inputs() const { return n + m_e + m_i; }
   int n_scales() const { return 1 + m_e + m_i; }

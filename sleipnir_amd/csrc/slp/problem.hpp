@@ -18,6 +18,7 @@
 #include <map>
 #include <memory>
 #include <optional>
+#include <span>
 #include <string>
 #include <utility>
 #include <vector>
@@ -259,6 +260,13 @@ class ProblemF64 {
   // are.  The driver follows the kinds of constraints present, as solve() does (problem.hpp:335, 403, 512): Newton,
   // SQP (eq_batch.hpp) or interior point, every one of them a lockstep batch on the device.
   slpx::BatchSolveResult solve_batch(int batch, const double* x0, const Options& options) {
+    return solve_batch(batch, x0, nullptr, options);
+  }
+  // ... and with params = [batch][n_p] (the order of parameters()): instance b is this problem with parameter row b,
+  // solved from x0[b]; null: the problem as it is, exactly the overload above.  The rows live in a constant pool per
+  // instance on the batch system (DeviceNlp::set_parameters) for the duration of the call: the variables' and the
+  // parameters' values are left as they are, and the shared pool is in force again on return.
+  slpx::BatchSolveResult solve_batch(int batch, const double* x0, const double* params, const Options& options) {
     if (batch <= 0) throw std::runtime_error("solve_batch: batch must be positive");
     if (x0 == nullptr) throw std::runtime_error("solve_batch: x0 is null");
     if (has_callbacks()) throw std::runtime_error("solve_batch: the problem has callbacks registered");
@@ -285,10 +293,36 @@ class ProblemF64 {
     };
     compile();
     slpx::NewtonSystem& sys = batch_system(batch);
-    // get_bounds conflict test and problem scaling at each instance's x0 (problem.hpp:597-616), from one batched
-    // sweep at unit scales
     const auto& st = sys.structure();
     auto& dev = sys.device();
+    // per-instance parameters: a pool per instance on the batch system for this call; however the call ends, the
+    // shared pool (the parameters' current values) is in force again on both systems
+    std::vector<double> pv;
+    if (params != nullptr) {
+      const size_t n_p = st.parameter_nodes().size();
+      if (n_p == 0) throw std::runtime_error("solve_batch: parameters given, but the model has none");
+      pv.assign(params, params + B * n_p);
+    }
+    struct SharedPoolAgain {
+      ProblemF64& p;
+      slpx::NewtonSystem* batch_sys;
+      void now() {
+        if (batch_sys == nullptr) return;
+        slpx::NewtonSystem* bsys = batch_sys;
+        batch_sys = nullptr;
+        p.install_current_parameters(*bsys);
+        p.install_current_parameters(*p.m_sys);
+      }
+      ~SharedPoolAgain() {  // (an exception is on its way: a second one from here is dropped)
+        try {
+          now();
+        } catch (...) {
+        }
+      }
+    } shared_pool_again{*this, params != nullptr ? &sys : nullptr};
+    if (params != nullptr) dev.set_parameters(pv.data(), /*per_instance=*/true);
+    // get_bounds conflict test and problem scaling at each instance's x0 (problem.hpp:597-616), from one batched
+    // sweep at unit scales
     std::vector<double> s1(B * std::max<size_t>(1, m_i), 1.0), y0(B * std::max<size_t>(1, m_e), 0.0);
     std::vector<double> V(B * st.nV);
     dev.upload_x(x0);
@@ -299,28 +333,36 @@ class ProblemF64 {
     std::vector<double> scales(B * ns);
     std::vector<uint8_t> run(B, 1);
     // (the test reads single-variable linear rows only: their coefficients do not depend on x0)
-    const bool conflict = has_conflicting_bounds(std::vector<double>(V.begin(), V.begin() + st.nV));
+    // One model: one verdict, from the host graph as solve() reaches it.  Per-instance parameters: a bound x >= p is
+    // another bound in every instance, so each instance's constant terms come from ITS V, and the verdict is its own.
+    const bool conflict = params == nullptr && has_conflicting_bounds(std::vector<double>(V.begin(), V.begin() + st.nV));
+    bool any_runs = false;
     for (size_t b = 0; b < B; ++b) {
       const std::vector<double> Vb(V.begin() + b * st.nV, V.begin() + (b + 1) * st.nV);
       const std::vector<double> sc = slpx::compute_problem_scaling(st, Vb);
       std::copy(sc.begin(), sc.end(), scales.begin() + b * ns);
-      if (conflict) {
+      if (conflict || (params != nullptr && has_conflicting_bounds(Vb, x0 + b * n))) {
         out.status[b] = ExitStatus::GLOBALLY_INFEASIBLE;
         run[b] = 0;
+        // (the cost an instance that is not solved reports: f at the variables' values — with ITS parameters)
+        if (params != nullptr && m_f) out.cost[b] = cost_with_parameters(st.parameter_nodes(), pv.data() + b * (pv.size() / B));
       }
+      any_runs = any_runs || run[b];
     }
-    if (!conflict) {
+    if (any_runs) {
       const std::vector<double> x0v(x0, x0 + B * n);
+      const std::vector<double>* rows = params != nullptr ? &pv : nullptr;
       try {
-        if (m_i > 0) slpx::interior_point_batch(sys, *m_sys, scales, options, x0v, run, out, m_batch_restoration);
-        else if (m_e > 0) slpx::sqp_batch(sys, *m_sys, scales, options, x0v, run, out, m_batch_restoration);
-        else slpx::newton_batch(sys, *m_sys, scales, options, x0v, run, out);
+        if (m_i > 0) slpx::interior_point_batch(sys, *m_sys, scales, options, x0v, run, out, m_batch_restoration, rows);
+        else if (m_e > 0) slpx::sqp_batch(sys, *m_sys, scales, options, x0v, run, out, m_batch_restoration, rows);
+        else slpx::newton_batch(sys, *m_sys, scales, options, x0v, run, out, rows);
       } catch (...) {
         reinstall_scaling();
         throw;
       }
       reinstall_scaling();
     }
+    shared_pool_again.now();
     restore();
     return out;
   }
@@ -457,15 +499,56 @@ class ProblemF64 {
       for (auto& v : m_inequality_constraints) ci.push_back(v.expr);
       m_sys = std::make_unique<slpx::NewtonSystem>(detail::G(), xs, m_f ? m_f->expr : slpx::kNull, ce,
                                                    ci, opt);
+      ++m_compile_count;
       m_param_snapshot.clear();
       for (const slpx::TapeProgram* prog : {&m_sys->structure().full, &m_sys->structure().values})
         for (const auto& [node, slot] : prog->params) m_param_snapshot.emplace_back(node, detail::G().val[node]);
     }
     return *m_sys;
   }
+  // Why set_parameters() may rewrite constant slots instead of compiling again: a parameter's VALUE reaches the
+  // compiled system through its slot in TapeProgram::consts and through nothing else.  The places where compile()
+  // reads a node's value (every `.val[` under csrc/ outside slp/):
+  //   * tape_compiler.cpp — the value of an OP_CONST node becomes a literal of the pool, the value of a free Variable
+  //     that is no input becomes the initial content of a slot of ITS OWN (never shared with a literal), and the
+  //     generated kernels never write such a slot's value into their source (tape_jit.cpp: `!any_param`);
+  //   * nlp.cpp, linear_row_adjoints — the cached entries of a LINEAR row read the value of the OTHER operand of a
+  //     product or of a divisor.  That operand is of type CONSTANT, or the row would not be LINEAR: a Variable is
+  //     LINEAR whether a decision variable or not, LINEAR x LINEAR is QUADRATIC, a LINEAR divisor makes the row
+  //     NONLINEAR (graph.hpp: mul, div) — both go through the tape.  A CONSTANT expression has no
+  //     Variable under it, so no parameter;
+  //   * nlp.cpp, the values baked into V_static_raw — roots and partial sums of type CONSTANT only, for the same
+  //     reason free of parameters.  A root made of parameters alone (a bound p_lo <= p_hi) is LINEAR: on the tape;
+  //   * capi.cpp — reads and writes of variables' values by the caller, not part of a compiled system.
+  // The sparsity patterns, the KKT plan and the factorization plan depend on the graph's shape, never on a value.
+  // What does read parameters' values OUTSIDE the compiled system is has_conflicting_bounds (the host graph, at
+  // solve()): set_parameters() writes the values into the graph too, and solve_batch() with per-instance rows takes
+  // each instance's bounds from its own V instead.
+  //
+  // The model's parameters: the free Variables that are not decision variables and that the cost or a constraint
+  // reaches, in ascending node order — the order of every parameter vector here.  Compiles (once) if need be.
+  std::vector<NodeId> parameters() { return compile().structure().parameter_nodes(); }
+  // New values for all parameters, in place: the variables get them, and so do the constant slots of the compiled
+  // system and of every batch system — nothing is compiled again (compile_count() stays), and handles to the system
+  // stay valid.  Variable::set_value on a parameter, by contrast, is noticed by the next compile() and builds anew.
+  void set_parameters(std::span<const double> values) {
+    slpx::NewtonSystem& sys = compile();
+    const std::vector<NodeId> nodes = sys.structure().parameter_nodes();
+    if (values.size() != nodes.size()) throw std::runtime_error("set_parameters: wrong number of values");
+    auto& g = detail::G();
+    for (size_t j = 0; j < nodes.size(); ++j) g.val[nodes[j]] = values[j];
+    for (auto& [node, value] : m_param_snapshot) value = g.val[node];
+    install_current_parameters(sys);
+    for (auto& [batch, bsys] : m_batch_sys)
+      if (bsys) install_current_parameters(*bsys);
+  }
+  // how many times this problem built a system for solve() (compile()): what set_parameters() leaves alone
+  int64_t compile_count() const { return m_compile_count; }
   // true when the next compile() / solve() will build a new system (handles from
   // slpx_problem_system taken before that are stale)
   bool needs_compile() const { return !m_sys; }
+  // the system of the last compile(), null if the model changed since (or never compiled): nothing is built
+  const slpx::NewtonSystem* compiled() const { return m_sys.get(); }
 
   const SolveReport& report() const { return m_report; }
   const VariableF64& cost() const { return *m_f; }
@@ -512,7 +595,30 @@ class ProblemF64 {
     return t;
   }
 
-  bool has_conflicting_bounds(const std::vector<double>& V) {
+  // the parameters' current values (the graph's) into the one pool every instance of `sys` reads, which is then in
+  // force: after set_parameters(), and after per-instance rows or one instance's row were installed for a batch
+  void install_current_parameters(slpx::NewtonSystem& sys) {
+    if (sys.has_device()) sys.device().refresh_params(detail::G());
+  }
+
+  // f at the variables' current values with `values` for the parameters `nodes` (which keep their own values)
+  double cost_with_parameters(const std::vector<NodeId>& nodes, const double* values) {
+    auto& g = detail::G();
+    std::vector<double> saved(nodes.size());
+    for (size_t j = 0; j < nodes.size(); ++j) {
+      saved[j] = g.val[nodes[j]];
+      g.val[nodes[j]] = values[j];
+    }
+    const double cost = m_f->value();
+    for (size_t j = 0; j < nodes.size(); ++j) g.val[nodes[j]] = saved[j];
+    (void)m_f->value();  // (values of interior nodes as they were)
+    return cost;
+  }
+
+  // x0 (null: as solve() does it — the constant term of a bound row from the host graph, at the variables' and the
+  // parameters' values there): the point V was swept at.  The constant term of row r is then c_i(x0) - coef x0[col],
+  // from V alone: what an instance of a batch with parameters of its own has, and the graph has not.
+  bool has_conflicting_bounds(const std::vector<double>& V, const double* x0 = nullptr) {
     const auto& st = m_sys->structure();
     auto& g = detail::G();
     const double inf = std::numeric_limits<double>::infinity();
@@ -530,11 +636,16 @@ class ProblemF64 {
     bool conflict = false;
     for (int r = 0; r < st.m_i; ++r) {
       if (m_inequality_constraints[r].type() != ExpressionType::LINEAR || cnt[r] != 1) continue;
-      const NodeId var = m_decision_variables[col[r]].expr;
-      const double saved = g.val[var];
-      g.val[var] = 0.0;
-      const double constant_term = m_inequality_constraints[r].value();
-      g.val[var] = saved;
+      double constant_term;
+      if (x0 != nullptr) {
+        constant_term = V[st.off_ci + r] - coef[r] * x0[col[r]];
+      } else {
+        const NodeId var = m_decision_variables[col[r]].expr;
+        const double saved = g.val[var];
+        g.val[var] = 0.0;
+        constant_term = m_inequality_constraints[r].value();
+        g.val[var] = saved;
+      }
       const double detected = -constant_term / coef[r];
       auto& [lo, hi] = b[col[r]];
       if (coef[r] < 0.0 && detected < hi) hi = detected;
@@ -552,7 +663,8 @@ class ProblemF64 {
   std::unique_ptr<slpx::NewtonSystem> m_sys;
   std::map<int, std::unique_ptr<slpx::NewtonSystem>> m_batch_sys;  // solve_batch(), keyed by the batch size
   int m_batch_restoration = 0;                                     // set_batch_restoration()
-  std::vector<std::pair<NodeId, double>> m_param_snapshot;  // (parameter node, value at compile time)
+  std::vector<std::pair<NodeId, double>> m_param_snapshot;  // (parameter node, value the compiled system holds)
+  int64_t m_compile_count = 0;                              // compile_count()
   std::vector<double> m_scales, m_s, m_y, m_z;
   SolveReport m_report;
 };

@@ -63,6 +63,15 @@ struct TapeDev {
   const uint16_t* node_rec16;
   const uint16_t* slot_edge_ptr16;
   const uint16_t* edges16;
+  // doubles between the constant pools of two batch instances (blockIdx.y): 0 = one pool shared by all of them,
+  // n_consts = a pool per instance (DeviceNlp::set_parameters).  Every reader starts from tape_consts().
+  uint32_t consts_stride;
 };
+
+// The constant pool of this workgroup's batch instance: a kernel argument plus a blockIdx expression, so the address is
+// wave-uniform and loads at uniform offsets from it stay scalar loads.
+__device__ __forceinline__ const double* tape_consts(const double* consts, uint32_t consts_stride) {
+  return consts + static_cast<unsigned long long>(blockIdx.y) * consts_stride;
+}
 
 }  // namespace slpx

@@ -69,10 +69,11 @@ __device__ __forceinline__ void tape_write_outputs(uint32_t count, uint32_t off,
   }
 }
 
-// One task, start to finish, by a workgroup of THREADS lanes; `in` / `V` already point at
-// the workgroup's problem, `smem_raw` at t.lds_bytes of 16-byte aligned LDS.
+// One task, start to finish, by a workgroup of THREADS lanes; `in` / `V` / `consts` already point at
+// the workgroup's problem (consts: tape_consts, tape_device.h), `smem_raw` at t.lds_bytes of 16-byte aligned LDS.
 template <int THREADS, bool FULL_OPS>
 __device__ __forceinline__ void tape_sweep_lds_body(const TapeDev& T, const TapeTask t,
+                                                    const double* __restrict__ consts,
                                                     const double* __restrict__ in,
                                                     const double* __restrict__ in_scale,
                                                     const double* __restrict__ scales, double* __restrict__ V,
@@ -128,7 +129,7 @@ __device__ __forceinline__ void tape_sweep_lds_body(const TapeDev& T, const Tape
     for (int u = 0; u < kTapeUnroll; ++u) {
       const bool is_const = (src[u] & kLeafConstFlag) != 0u;
       const uint32_t xi = is_const ? 0u : src[u];
-      c[u] = T.consts[is_const ? (src[u] & ~kLeafConstFlag) : 0u];
+      c[u] = consts[is_const ? (src[u] & ~kLeafConstFlag) : 0u];
       x[u] = in[xi];
       w[u] = in_scale[xi];
     }

@@ -56,9 +56,9 @@ __global__ __launch_bounds__(THREADS) void tape_sweep_lds_kernel(
     int v_stride, int do_reverse) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int b = blockIdx.y;
-  tape_sweep_lds_body<THREADS, FULL_OPS>(T, T.tasks[task_list[blockIdx.x]], in + static_cast<size_t>(b) * in_stride,
-                                         in_scale, scales, V + static_cast<size_t>(b) * v_stride, do_reverse,
-                                         smem_raw);
+  tape_sweep_lds_body<THREADS, FULL_OPS>(T, T.tasks[task_list[blockIdx.x]], tape_consts(T.consts, T.consts_stride),
+                                         in + static_cast<size_t>(b) * in_stride, in_scale, scales,
+                                         V + static_cast<size_t>(b) * v_stride, do_reverse, smem_raw);
 }
 
 // Fallback for components too large for LDS: same program (32-bit records), working
@@ -73,13 +73,14 @@ __global__ __launch_bounds__(1024) void tape_sweep_global_kernel(
   const int tid = threadIdx.x;
   in += static_cast<size_t>(b) * in_stride;
   V += static_cast<size_t>(b) * v_stride;
+  const double* __restrict__ consts = tape_consts(T.consts, T.consts_stride);
   double* val = scratch + static_cast<size_t>(b) * scratch_stride + t.scratch_off;
   double* part = val + t.n_leaf + t.n_node;
   double* adj = part + 2 * t.n_node;
 
   for (uint32_t i = tid; i < t.n_leaf; i += THREADS) {
     const uint32_t src = T.leaf_src[t.leaf_off + i];
-    val[i] = (src & kLeafConstFlag) ? T.consts[src & ~kLeafConstFlag] : in[src] * in_scale[src];
+    val[i] = (src & kLeafConstFlag) ? consts[src & ~kLeafConstFlag] : in[src] * in_scale[src];
   }
   __syncthreads();
   const uint32_t* lvl = T.lvl_ptr + t.lvl_off;

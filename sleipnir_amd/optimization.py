@@ -200,10 +200,12 @@ class Problem:
         (slpx_problem_solve_batch).  Keyword arguments: tolerance, max_iterations, timeout, feasible_ipm
         (the timeout covers the whole batch); diagnostics and spy are accepted and ignored; restoration = "handoff"
         (default) or "lockstep": how instances that need feasibility restoration run it
-        (slpx_problem_set_batch_restoration).  The variables'
+        (slpx_problem_set_batch_restoration); parameters = array (B, n_p): instance b is this problem with row b for
+        the values of parameters() (slpx_problem_solve_batch_parameters).  The variables' and the parameters'
         values are left as they are.  Raises SlpxError where the library cannot run a batch (no device,
         callbacks registered)."""
-        allowed = {"tolerance", "max_iterations", "timeout", "feasible_ipm", "diagnostics", "spy", "restoration"}
+        allowed = {"tolerance", "max_iterations", "timeout", "feasible_ipm", "diagnostics", "spy", "restoration",
+                   "parameters"}
         for k in kwargs:
             if k not in allowed:
                 raise KeyError(f"Invalid keyword argument: {k}")
@@ -221,6 +223,21 @@ class Problem:
                            z=r["z"], cost=r["cost"], iterations=r["iterations"], restorations=r["restorations"],
                            report=r["report"], rounds=r["rounds"], handoffs=r["handoffs"], driver=r["driver"],
                            restoration_lockstep=r.get("restoration_lockstep", {}))
+
+    def parameters(self) -> list:
+        """The model's parameters: the free Variables that are not decision variables of this problem and that its cost
+        or a constraint reaches, in the order of every parameter vector (ascending expression id).  Needs no device."""
+        return [Variable._wrap(node) for node in self._p.parameters()]
+
+    def set_parameters(self, values):
+        """New values for parameters(), in that order, written in place into the compiled problem: the next solve() or
+        solve_batch() does not compile again (Variable.set_value on a parameter does).  An MPC loop:
+
+            for x_now in measurements:
+                problem.set_parameters(x_now)
+                problem.solve()
+        """
+        self._p.set_parameters(values)
 
     def restoration_steps_batch(self, x, s, y, z, mu, steps, **kwargs):
         """`steps` iterations of feasibility restoration from each of B iterates (rows of x, s, y, z; mu of length B), in
