@@ -256,6 +256,55 @@ int slpx_problem_solve_batch_parameters(slpx_problem* p, int32_t batch, const do
                                         double* s, double* y, double* z, double* cost, int32_t* iterations,
                                         int32_t* restorations, slpx_report* report);
 
+/* ---- warm starts --------------------------------------------------------------------
+ * A solve may begin at a caller-given primal-dual iterate instead of s = 1, y = 0, z = 1, mu = 0.1 d_f: typically
+ * the iterate the previous solve of a neighbouring problem ended at (an MPC loop around slpx_problem_set_parameters).
+ * The entry points of this section are additions within ABI version 6, detected by the symbol's presence like
+ * slpx_problem_solve_batch.
+ *
+ * UNITS.  A solve runs on a scaled problem (cost scale d_f, row scales d_ce, d_ci, computed anew at every solve's x0),
+ * so scaled values do not carry over from one solve to the next.  Everything in this section is in the USER'S units:
+ *     s_u = s / d_ci     y_u = y d_ce / d_f     z_u = z d_ci / d_f     mu_u = mu / d_f
+ * — y_u, z_u are the multipliers of f - y^T c_e - z^T c_i as the model was written.  slpx_problem_get_duals and the
+ * s, y, z outputs of slpx_problem_solve_batch[_parameters] return the SCALED iterate of the solve, as they always have:
+ * callers that compare iterates with the reference's read them, and changing their units would change those callers.
+ *
+ * SAFEGUARD, per instance, in the scaled space of the new solve (mu_min = d_f tolerance / 10, c_i the constraint value
+ * at x0): a NaN or Inf in x, in a given array or in mu ends the instance with NONFINITE_INITIAL_GUESS (-7) before any
+ * iteration.  mu: the given one where > 0, floored at mu_min; else the mean of s_j z_j over the rows where both are
+ * given and positive, within [mu_min, 0.1 d_f]; else 0.1 d_f.  s_j absent or <= 0: max(c_i_j, mu).  z_j absent or
+ * <= 0: mu / s_j; then every z_j is clamped into [mu / (1e10 s_j), 1e10 mu / s_j], as after every step of the
+ * iteration.  y absent: 0.  The number of entries replaced or moved by the clamp is reported (`repaired`); an iterate
+ * this library returned for the same scales passes with 0 and every bit unchanged.  Filter, regularization memory
+ * and counters start as in a cold solve.  Without inequality constraints only x and y are read (SQP), without any
+ * constraints only x (Newton); the other members are accepted and ignored.  A warm start that gives nothing beside
+ * x — no array, and no mu above 0 — is the cold start. */
+typedef struct slpx_warm_start {
+  const double *s, *y, *z; /* [m_i], [m_e], [m_i]; NULL: absent */
+  double mu;               /* <= 0: choose */
+} slpx_warm_start;
+/* slpx_problem_solve_sized from the variables' values (slpx_problem_set_x) and *ws; ws NULL: exactly
+ * slpx_problem_solve_sized. */
+int slpx_problem_solve_warm(slpx_problem* p, const slpx_options* opt, uint32_t options_bytes, const slpx_warm_start* ws,
+                            slpx_report* report);
+/* The iterate the last slpx_problem_solve* ended at (any of the outputs may be NULL): x[n], s[m_i], y[m_e], z[m_i], *mu
+ * (0 where the solver has no barrier).  Returns 0; -100 + slpx_last_error() for a null problem or before any solve
+ * that ran a solver.  Needs no device. */
+int slpx_problem_get_iterate(const slpx_problem* p, double* x, double* s, double* y, double* z, double* mu);
+/* How many entries of its warm start the last slpx_problem_solve_warm repaired; < 0: null problem. */
+int32_t slpx_problem_warm_start_repaired(const slpx_problem* p);
+/* slpx_problem_solve_batch_parameters (params may be NULL) with instance b started from s0[b][m_i], y0[b][m_e],
+ * z0[b][m_i], mu0[b] — each of the four may be NULL — and with the outputs s, y, z, mu[B] in the user's units: what the
+ * next call takes as s0, y0, z0, mu0.  repaired[B] (may be NULL): the safeguard's count per instance.  With s0 = y0 =
+ * z0 = mu0 = NULL every instance runs exactly as in slpx_problem_solve_batch_parameters; only the units of the dual
+ * outputs differ.  The safeguard runs on the device, one workgroup per instance.  Returns 0, or -100 +
+ * slpx_last_error() as slpx_problem_solve_batch_parameters. */
+int slpx_problem_solve_batch_warm(slpx_problem* p, int32_t batch, const double* x0, const double* params, const double* s0,
+                                  const double* y0, const double* z0, const double* mu0, const slpx_options* opt,
+                                  uint32_t options_bytes, int32_t* status, double* x, double* s, double* y, double* z,
+                                  double* mu, double* cost, int32_t* iterations, int32_t* restorations, int32_t* repaired,
+                                  slpx_report* report);
+
 /* ---- compiled Newton system ------------------------------------------------------
  * One problem structure compiled for one GPU, `batch` independent value sets.
  * Replaces, per Newton step:

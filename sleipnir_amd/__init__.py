@@ -63,6 +63,11 @@ class Report(ctypes.Structure):
                 ("t_restoration", ctypes.c_double)]
 
 
+class WarmStart(ctypes.Structure):
+    """slpx_warm_start: s, y, z in the user's units (NULL: absent), mu (<= 0: choose)."""
+    _fields_ = [("s", ctypes.c_void_p), ("y", ctypes.c_void_p), ("z", ctypes.c_void_p), ("mu", ctypes.c_double)]
+
+
 def build(force: bool = False, verbose: bool = False) -> Path:
     """Compile libslpx.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     # (at most 16 jobs: a shared build host may count far more CPUs than one build may use)
@@ -190,6 +195,13 @@ def lib() -> ctypes.CDLL:
             vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(Report))
         sig("slpx_system_set_parameters", ctypes.c_int, vp, vp, ctypes.c_int)
         sig("slpx_system_parameter_pool_bytes", i64, vp)
+    if hasattr(L, "slpx_problem_solve_warm"):
+        sig("slpx_problem_solve_warm", ctypes.c_int, vp, ctypes.POINTER(Options), ctypes.c_uint32, ctypes.POINTER(WarmStart),
+            ctypes.POINTER(Report))
+        sig("slpx_problem_get_iterate", ctypes.c_int, vp, vp, vp, vp, vp, vp)
+        sig("slpx_problem_warm_start_repaired", i32, vp)
+        sig("slpx_problem_solve_batch_warm", ctypes.c_int, vp, i32, vp, vp, vp, vp, vp, vp, ctypes.POINTER(Options),
+            ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(Report))
     _lib = L
     return L
 
@@ -270,18 +282,56 @@ class Problem:
         lib().slpx_problem_set_x(self._h, x.ctypes.data)
 
     def solve(self, tolerance=1e-8, max_iterations=5000, timeout=0.0, feasible_ipm=False,
-              diagnostics=False, spy=False):
+              diagnostics=False, spy=False, warm_start=None):
+        """warm_start: None, or a dict with any of s, y, z (arrays in the user's units) and mu — the rest of the iterate
+        the solve begins at, x being the variables' values (slpx_problem_solve_warm; include/slpx.h: warm starts)."""
         opt = Options(tolerance, max_iterations, timeout, int(feasible_ipm), int(diagnostics), int(spy))
         rep = Report()
-        status = lib().slpx_problem_solve_sized(self._h, ctypes.byref(opt), ctypes.sizeof(Options), ctypes.byref(rep))
+        if warm_start is None:
+            status = lib().slpx_problem_solve_sized(self._h, ctypes.byref(opt), ctypes.sizeof(Options), ctypes.byref(rep))
+        else:
+            L = lib()
+            if not hasattr(L, "slpx_problem_solve_warm"):
+                raise SlpxError(f"{LIB_PATH} has no slpx_problem_solve_warm")
+            n, me, mi = self.dims
+            hold = {}
+            for k, count in (("s", mi), ("y", me), ("z", mi)):
+                v = warm_start.get(k)
+                if v is not None:
+                    v = np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel())
+                    if v.shape[0] != count:
+                        raise ValueError(f"warm_start: {k} must have {count} entries")
+                    hold[k] = v
+            mu = warm_start.get("mu")
+            ws = WarmStart(*(hold[k].ctypes.data if k in hold and hold[k].size else None for k in ("s", "y", "z")),
+                           0.0 if mu is None else float(mu))
+            status = L.slpx_problem_solve_warm(self._h, ctypes.byref(opt), ctypes.sizeof(Options), ctypes.byref(ws),
+                                               ctypes.byref(rep))
         if status == -100:
             raise SlpxError(lib().slpx_last_error().decode())
         return status, {f[0]: getattr(rep, f[0]) for f in Report._fields_}
 
+    def iterate(self):
+        """(x, s, y, z, mu) the last solve ended at, in the user's units (slpx_problem_get_iterate)."""
+        L = lib()
+        if not hasattr(L, "slpx_problem_get_iterate"):
+            raise SlpxError(f"{LIB_PATH} has no slpx_problem_get_iterate")
+        n, me, mi = self.dims
+        x, s, y, z = np.zeros(n), np.zeros(mi), np.zeros(me), np.zeros(mi)
+        mu = ctypes.c_double()
+        if L.slpx_problem_get_iterate(self._h, *(a.ctypes.data if a.size else None for a in (x, s, y, z)),
+                                      ctypes.addressof(mu)) != 0:
+            raise SlpxError(L.slpx_last_error().decode())
+        return x, s, y, z, mu.value
+
+    def warm_start_repaired(self) -> int:
+        """Entries of its warm start the last solve's safeguard replaced or clamped (slpx_problem_warm_start_repaired)."""
+        return int(lib().slpx_problem_warm_start_repaired(self._h))
+
     RESTORATION_MODES = {"handoff": 0, "lockstep": 1}
 
     def solve_batch(self, x0, tolerance=1e-8, max_iterations=5000, timeout=0.0, feasible_ipm=False, restoration="handoff",
-                    parameters=None):
+                    parameters=None, warm_start=None):
         """B instances from the rows of x0 (B x n), each as solve() from that start
         (slpx_problem_solve_batch).  Returns a dict of arrays: status, x, s, y, z, cost, iterations,
         restorations, the batch's report, and how the batch ran (slpx_problem_batch_stats): rounds (lockstep
@@ -293,8 +343,13 @@ class Problem:
         slpx_problem_batch_restoration_stats: instances restored in lockstep, phases, lockstep restoration rounds,
         instances that used the batch-1 system for the KKT-error fallback.
         parameters: None, or (B x n_p) — instance b is the problem with parameter row b, the order of parameters()
-        (slpx_problem_solve_batch_parameters)."""
+        (slpx_problem_solve_batch_parameters).
+        warm_start: None, or a dict with any of s (B x m_i), y (B x m_e), z (B x m_i), mu (B) in the user's units, possibly
+        empty: instance b begins there (slpx_problem_solve_batch_warm), and s, y, z of the result are in the user's units
+        too, with "mu" (B) and "repaired" (B) added."""
         L = lib()
+        if warm_start is not None and not hasattr(L, "slpx_problem_solve_batch_warm"):
+            raise SlpxError(f"{LIB_PATH} has no slpx_problem_solve_batch_warm")
         if parameters is not None and not hasattr(L, "slpx_problem_solve_batch_parameters"):
             raise SlpxError(f"{LIB_PATH} has no slpx_problem_solve_batch_parameters")
         if not hasattr(L, "slpx_problem_solve_batch"):
@@ -316,16 +371,36 @@ class Problem:
         opt = Options(tolerance, max_iterations, timeout, int(feasible_ipm), 0, 0)
         rep = Report()
         outputs = [out[k].ctypes.data for k in ("status", "x", "s", "y", "z", "cost", "iterations", "restorations")]
-        if parameters is None:
-            rc = L.slpx_problem_solve_batch(self._h, B, x0.ctypes.data if B else None, ctypes.byref(opt),
-                                            ctypes.sizeof(Options), *outputs, ctypes.byref(rep))
-        else:
+        rows = None
+        if parameters is not None:
             rows = np.ascontiguousarray(np.asarray(parameters, dtype=np.float64))
             if rows.ndim != 2 or rows.shape[0] != B:
                 raise ValueError(f"parameters must have shape ({B}, n_p): one row per instance")
             n_p = len(self.parameters())
             if rows.shape[1] != n_p:
                 raise ValueError(f"parameters must have {n_p} columns, the model's parameters")
+        if warm_start is not None:
+            hold = {}
+            for k, count in (("s", mi), ("y", me), ("z", mi), ("mu", 1)):
+                v = warm_start.get(k)
+                if v is not None:
+                    v = np.asarray(v, dtype=np.float64)
+                    if v.size != B * count:
+                        raise ValueError(f"warm_start: {k} must have shape ({B}, {count})")
+                    v = np.ascontiguousarray(v.reshape(B, count))
+                    hold[k] = v
+            out["mu"] = np.zeros(B)
+            out["repaired"] = np.zeros(B, dtype=np.int32)
+            rc = L.slpx_problem_solve_batch_warm(
+                self._h, B, x0.ctypes.data if B else None, rows.ctypes.data if rows is not None and rows.size else None,
+                *(hold[k].ctypes.data if k in hold and hold[k].size else None for k in ("s", "y", "z", "mu")),
+                ctypes.byref(opt), ctypes.sizeof(Options),
+                *(out[k].ctypes.data for k in ("status", "x", "s", "y", "z", "mu", "cost", "iterations", "restorations",
+                                               "repaired")), ctypes.byref(rep))
+        elif parameters is None:
+            rc = L.slpx_problem_solve_batch(self._h, B, x0.ctypes.data if B else None, ctypes.byref(opt),
+                                            ctypes.sizeof(Options), *outputs, ctypes.byref(rep))
+        else:
             rc = L.slpx_problem_solve_batch_parameters(self._h, B, x0.ctypes.data if B else None,
                                                        rows.ctypes.data if rows.size else None, ctypes.byref(opt),
                                                        ctypes.sizeof(Options), *outputs, ctypes.byref(rep))

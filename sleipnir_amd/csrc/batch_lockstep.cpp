@@ -10,6 +10,7 @@
 #include "fr_batch.hpp"
 #include "ipm_batch.hpp"
 #include "ipm_line_search.hpp"
+#include "warm_start.h"
 
 namespace slpx {
 
@@ -51,11 +52,13 @@ struct IpmDriver {
 
   template <class I>
   static auto& search(I& inst) { return inst.ls; }
+  static constexpr bool kWarmStarts = true;
   void set_initial_iterate(Device& bd, const Vec& x0) const {
     const size_t B = bd.B;
     bd.set_iterate(x0, Vec(B * st.m_i, 1.0), Vec(B * st.m_e, 0.0), Vec(B * st.m_i, 1.0));
   }
   void init(Instance& I) const { I.mu = 0.1 * I.scales[0]; }  // interior_point.hpp:74-79
+  void init_warm(Instance& I, double mu) const { I.mu = mu; }
   void setup(Instance& I) const { I.mu_min = barrier_floor(I.scales[0], options.tolerance); }
   void launch_parameters(Device& bd, int b, const Instance& I) const {
     bd.mu[b] = I.mu;
@@ -100,6 +103,7 @@ struct EqDriver {
   Vec dphi, mu0;
 
   void init(Instance& I) const { I.identity = scaling_is_identity(st, I.scales); }
+  void init_warm(Instance&, double) const {}  // (no barrier)
   void after_refresh(Instance& I) const {
     // (m_i = 0, and for Newton m_e = 0 too: the divisors of the scale factors are 0, the quotients NaN, and fmax
     // drops a NaN as std::max does one in its second argument: both factors are 1, as on the host)
@@ -122,6 +126,7 @@ struct SqpDriver : EqDriver {
 
   template <class I>
   static auto& search(I& inst) { return inst.ls; }
+  static constexpr bool kWarmStarts = true;  // x and y
   void set_initial_iterate(Device& bd, const Vec& x0) const {
     bd.set_iterate(x0, Vec(static_cast<size_t>(bd.B) * st.m_e, 0.0));  // problem.hpp:503-504: y = 0
   }
@@ -154,6 +159,7 @@ struct NewtonDriver : EqDriver {
 
   template <class I>
   static auto& search(I& inst) { return inst.newton; }
+  static constexpr bool kWarmStarts = false;  // x only: the other blocks are accepted and ignored
   void set_initial_iterate(Device& bd, const Vec& x0) const { bd.set_iterate(x0, Vec{}); }
   void setup(Instance& I) const { I.newton.f = I.cur.f; }
   // the fallback looks at the full step (newton.hpp:226); every other trial point is at t_alpha
@@ -178,7 +184,7 @@ struct NewtonDriver : EqDriver {
 template <class Driver>
 void lockstep(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales, const Options& options,
               const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out, int restoration_mode,
-              const std::vector<double>* instance_params) {
+              const std::vector<double>* instance_params, const BatchWarmStart* warm) {
   const auto solve_start = clk::now();
   const NlpStructure& st = sys.structure();
   DeviceNlp& dev = sys.device();
@@ -215,6 +221,32 @@ void lockstep(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>
     I.running = run[b] != 0;
   }
   drv.set_initial_iterate(bd, x0);
+  // A warm start (warm_start.h) in place of the constants, for the instances that run and whose input is finite — the
+  // others keep the cold start: s, y, z converted and safeguarded on the device, the first barrier parameter from it
+  if (warm) out.repaired.assign(B, 0);
+  // (nothing given beside x0 — no block, and no barrier parameter above 0 — is the cold start, as in a single solve)
+  bool warm_given = warm && (warm->s || warm->y || warm->z);
+  for (int b = 0; warm && warm->mu && !warm_given && b < B; ++b) warm_given = !(warm->mu[b] <= 0.0);
+  if (Driver::kWarmStarts && warm_given) {
+    BatchWarmStart ws = *warm;
+    if (m_i == 0) ws.s = ws.z = ws.mu = nullptr;  // SQP: x and y
+    Vec mu_min(B), first;
+    for (int b = 0; b < B; ++b) mu_min[b] = barrier_floor(inst[b].scales[0], options.tolerance);
+    bd.warm_start(ws, run, mu_min, first);
+    for (int b = 0; b < B; ++b) {
+      Instance& I = inst[b];
+      if (!I.running) continue;
+      const double* w = first.data() + static_cast<size_t>(b) * 3;
+      if (w[2] != 0.0) {
+        I.status = ExitStatus::NONFINITE_INITIAL_GUESS;
+        I.running = false;
+        Driver::search(I).want = Want::Done;
+        continue;
+      }
+      drv.init_warm(I, w[0]);
+      out.repaired[b] = static_cast<int>(w[1]);
+    }
+  }
 
   // the per-instance parameters of the next launches, for the instances `pred` selects
   auto launch_for = [&](auto pred) {
@@ -449,6 +481,12 @@ void lockstep(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>
   out.cost.resize(B);
   out.iterations.resize(B);
   out.restorations.resize(B);
+  if (warm) {  // the end iterate in the user's units (warm_start.h): what the next warm start takes
+    bd.unscaled_iterate(run, out.s_u, out.y_u, out.z_u);
+    out.mu_u.assign(B, 0.0);
+    for (int b = 0; b < B; ++b)
+      if (run[b]) out.mu_u[b] = warm_unscale_mu(inst[b].mu, inst[b].scales[0]);
+  }
   const auto& reg_delta = sys.hessian_regularization();
   const auto& reg_gamma = sys.constraint_jacobian_regularization();
   for (int b = 0; b < B; ++b) {
@@ -480,20 +518,21 @@ void lockstep(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>
 
 void interior_point_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales,
                           const Options& options, const std::vector<double>& x0, const std::vector<uint8_t>& run,
-                          BatchSolveResult& out, int restoration_mode, const std::vector<double>* instance_params) {
-  lockstep<IpmDriver>(sys, single, scales, options, x0, run, out, restoration_mode, instance_params);
+                          BatchSolveResult& out, int restoration_mode, const std::vector<double>* instance_params,
+                          const BatchWarmStart* warm) {
+  lockstep<IpmDriver>(sys, single, scales, options, x0, run, out, restoration_mode, instance_params, warm);
 }
 
 void sqp_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales, const Options& options,
                const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out, int restoration_mode,
-               const std::vector<double>* instance_params) {
-  lockstep<SqpDriver>(sys, single, scales, options, x0, run, out, restoration_mode, instance_params);
+               const std::vector<double>* instance_params, const BatchWarmStart* warm) {
+  lockstep<SqpDriver>(sys, single, scales, options, x0, run, out, restoration_mode, instance_params, warm);
 }
 
 void newton_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales, const Options& options,
                   const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out,
-                  const std::vector<double>* instance_params) {
-  lockstep<NewtonDriver>(sys, single, scales, options, x0, run, out, /*restoration_mode=*/0, instance_params);
+                  const std::vector<double>* instance_params, const BatchWarmStart* warm) {
+  lockstep<NewtonDriver>(sys, single, scales, options, x0, run, out, /*restoration_mode=*/0, instance_params, warm);
 }
 
 }  // namespace slpx

@@ -57,6 +57,14 @@ struct BatchIter {
   double *x, *s, *y, *z;
 };
 
+// A warm start of a batch (warm_start.h: units and safeguard): the iterate every instance begins at, in the USER'S
+// units, host arrays [B][m_i], [B][m_e], [B][m_i] and the barrier parameter [B] (<= 0: choose); a null block is
+// absent.  Passing one, even with every block null, also asks for the end iterate in the user's units
+// (BatchSolveResult::s_u, y_u, z_u, mu_u) and the repair counts.
+struct BatchWarmStart {
+  const double *s = nullptr, *y = nullptr, *z = nullptr, *mu = nullptr;
+};
+
 // The device state every batched driver has (methods: ipm_batch_launch.hip): the iterate's x and y, the trial
 // point's, the correction's, the current point's V of every instance, batch-major, and the per-instance parameters
 // of a launch.  Launches take effect for the instances flagged in `active` only.  A derived device adds the buffers
@@ -83,12 +91,23 @@ struct BatchDevice {
   // the full tape at the iterate, scaled; the system's s, y, z, V are then the iterate's (what the Newton step reads),
   // a copy of V is kept as the current point's, and the errors are reduced -> err [B][kBatchErrN]
   void refresh(std::vector<double>& err);
+  // The first iterate from a warm start (batch_warm_start_kernel): s, y, z of every instance with run[b] != 0 and a
+  // finite input are written into the iterate — x must be there (set_iterate) and the system's V must be the sweep at
+  // x with unit scales, as the caller's scaling sweep leaves it.  mu_min [B]; out [B][3]: the first barrier parameter
+  // (scaled), the entries repaired, 1 for a non-finite input (then nothing of the instance was written).
+  void warm_start(const BatchWarmStart& ws, const std::vector<uint8_t>& run, const std::vector<double>& mu_min,
+                  std::vector<double>& out);
+  // s, y, z of the iterate in the user's units (batch_unscale_iterate_kernel); instances with run[b] == 0 read 0
+  void unscaled_iterate(const std::vector<uint8_t>& run, std::vector<double>& s_u, std::vector<double>& y_u,
+                        std::vector<double>& z_u);
 
  protected:
   explicit BatchDevice(NewtonSystem& sys);
   DevBuf<int32_t> m_scale_idx, m_mode;
   DevBuf<uint8_t> m_is_static, m_active, m_first;
   DevBuf<double> m_static_raw, m_scales, m_alpha, m_alpha_soc, m_out, m_Vcur;
+  DevBuf<uint8_t> m_ws_run;                                 // warm start: made at its first use
+  DevBuf<double> m_ws_s, m_ws_y, m_ws_z, m_ws_mu, m_ws_out;
   DevBuf<double> m_x, m_y, m_tx, m_ty, m_sx, m_sy, m_tce, m_sce;  // iterate, trial, correction; trial c_e, its accumulator
   BatchIter m_cur{}, m_trial{};            // the iterate and the trial point, with the derived device's s and z
   const double* m_mu_of_errors = nullptr;  // [B] the barrier parameter batch_errors_kernel reads
@@ -117,6 +136,10 @@ struct BatchSolveResult {
   // restoration in lockstep (restoration_mode 1; fr_batch.hpp): instances restored, phases, lockstep rounds of the
   // restoration loop, instances that used the batch-1 system for the KKT-error fallback — all 0 in hand-off mode
   int64_t restoration_lockstep[4] = {0, 0, 0, 0};
+  // with a BatchWarmStart only: the end iterate in the user's units (warm_start.h), and how many entries of the given
+  // iterate the safeguard replaced or clamped, [B]
+  std::vector<double> s_u, y_u, z_u, mu_u;
+  std::vector<int> repaired;
 };
 
 // x0 = [B][n]; scales = [B][1 + m_e + m_i] (compute_problem_scaling at each instance's x0); `run[b]` = 0: instance b
@@ -131,15 +154,17 @@ struct BatchSolveResult {
 // `single` works for an instance — the restoration hand-off, the KKT-error fallback and the multiplier estimate of a
 // lockstep phase — that instance's row is installed there first, as its scaling is.  The caller puts `single`'s own
 // values back afterwards, as it does the scaling.
+// warm (null: the cold start, the bits of every release before it): see BatchWarmStart; the system's V must then be the
+// sweep at x0 with unit scales (what the scaling was computed from).  Newton reads x0 only.
 void interior_point_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales,
                           const Options& options, const std::vector<double>& x0, const std::vector<uint8_t>& run,
                           BatchSolveResult& out, int restoration_mode = 0,
-                          const std::vector<double>* instance_params = nullptr);
+                          const std::vector<double>* instance_params = nullptr, const BatchWarmStart* warm = nullptr);
 void sqp_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales, const Options& options,
                const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out, int restoration_mode = 0,
-               const std::vector<double>* instance_params = nullptr);
+               const std::vector<double>* instance_params = nullptr, const BatchWarmStart* warm = nullptr);
 void newton_batch(NewtonSystem& sys, NewtonSystem& single, const std::vector<double>& scales, const Options& options,
                   const std::vector<double>& x0, const std::vector<uint8_t>& run, BatchSolveResult& out,
-                  const std::vector<double>* instance_params = nullptr);
+                  const std::vector<double>* instance_params = nullptr, const BatchWarmStart* warm = nullptr);
 
 }  // namespace slpx

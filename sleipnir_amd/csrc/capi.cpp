@@ -132,6 +132,12 @@ int slpx_problem_solve(slpx_problem* p, const slpx_options* o, slpx_report* repo
 }
 
 int slpx_problem_solve_sized(slpx_problem* p, const slpx_options* o, uint32_t options_bytes, slpx_report* report) {
+  return slpx_problem_solve_warm(p, o, options_bytes, nullptr, report);
+}
+
+int slpx_problem_solve_warm(slpx_problem* p, const slpx_options* o, uint32_t options_bytes, const slpx_warm_start* ws,
+                            slpx_report* report) {
+  if (p == nullptr) return guard([] { throw std::runtime_error("slpx_problem_solve_warm: null problem"); });
   const bool spy = o != nullptr && options_bytes >= offsetof(slpx_options, spy) + sizeof(int32_t) && o->spy != 0;
   int status = -100;
   int rc = guard([&] {
@@ -151,7 +157,17 @@ int slpx_problem_solve_sized(slpx_problem* p, const slpx_options* o, uint32_t op
                                p->problem.inequality_constraint_type() <= slp::ExpressionType::CONSTANT;
     if (!nothing_to_do) p->problem.compile();
     p->t_compile = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    status = static_cast<int>(p->problem.solve(opt, spy));
+    if (ws == nullptr) {
+      status = static_cast<int>(p->problem.solve(opt, spy));
+    } else {
+      const size_t m_e = p->problem.equality_constraints().size(), m_i = p->problem.inequality_constraints().size();
+      slpx::WarmStart warm;
+      if (ws->s) warm.s.assign(ws->s, ws->s + m_i);
+      if (ws->y) warm.y.assign(ws->y, ws->y + m_e);
+      if (ws->z) warm.z.assign(ws->z, ws->z + m_i);
+      warm.mu = ws->mu;
+      status = static_cast<int>(p->problem.solve(opt, spy, warm));
+    }
     if (report) {
       const auto& r = p->problem.report();
       *report = slpx_report{r.iterations,    r.factorizations, r.solves,       r.value_sweeps,
@@ -171,11 +187,53 @@ int slpx_problem_solve_batch(slpx_problem* p, int32_t batch, const double* x0, c
                                              restorations, report);
 }
 
+namespace {
+// slpx_problem_solve_batch_parameters (warm == nullptr: s, y, z out are the scaled iterate) and
+// slpx_problem_solve_batch_warm (s, y, z, mu out in the user's units)
+int solve_batch_impl(slpx_problem* p, int32_t batch, const double* x0, const double* params, const slpx::BatchWarmStart* warm,
+                     const slpx_options* o, int32_t* status, double* x, double* sv, double* y, double* z, double* mu,
+                     double* cost, int32_t* iterations, int32_t* restorations, int32_t* repaired, slpx_report* report);
+}  // namespace
+
 int slpx_problem_solve_batch_parameters(slpx_problem* p, int32_t batch, const double* x0, const double* params,
                                         const slpx_options* o, uint32_t options_bytes, int32_t* status, double* x, double* sv,
                                         double* y, double* z, double* cost, int32_t* iterations, int32_t* restorations,
                                         slpx_report* report) {
   (void)options_bytes;  // (every member read here predates `spy`, the only one a shorter struct lacks)
+  return solve_batch_impl(p, batch, x0, params, nullptr, o, status, x, sv, y, z, nullptr, cost, iterations, restorations,
+                          nullptr, report);
+}
+
+int slpx_problem_solve_batch_warm(slpx_problem* p, int32_t batch, const double* x0, const double* params, const double* s0,
+                                  const double* y0, const double* z0, const double* mu0, const slpx_options* o,
+                                  uint32_t options_bytes, int32_t* status, double* x, double* sv, double* y, double* z,
+                                  double* mu, double* cost, int32_t* iterations, int32_t* restorations, int32_t* repaired,
+                                  slpx_report* report) {
+  (void)options_bytes;
+  const slpx::BatchWarmStart warm{s0, y0, z0, mu0};
+  return solve_batch_impl(p, batch, x0, params, &warm, o, status, x, sv, y, z, mu, cost, iterations, restorations, repaired,
+                          report);
+}
+
+int slpx_problem_get_iterate(const slpx_problem* p, double* x, double* sv, double* y, double* z, double* mu) {
+  return guard([&] {
+    if (p == nullptr) throw std::runtime_error("slpx_problem_get_iterate: null problem");
+    if (!p->problem.has_iterate()) throw std::runtime_error("slpx_problem_get_iterate: the problem has not been solved");
+    const auto it = p->problem.iterate();
+    if (x) std::copy(it.x.begin(), it.x.end(), x);
+    if (sv) std::copy(it.s.begin(), it.s.end(), sv);
+    if (y) std::copy(it.y.begin(), it.y.end(), y);
+    if (z) std::copy(it.z.begin(), it.z.end(), z);
+    if (mu) *mu = it.mu;
+  });
+}
+
+int32_t slpx_problem_warm_start_repaired(const slpx_problem* p) { return p ? p->problem.warm_start_repaired() : -1; }
+
+namespace {
+int solve_batch_impl(slpx_problem* p, int32_t batch, const double* x0, const double* params, const slpx::BatchWarmStart* warm,
+                     const slpx_options* o, int32_t* status, double* x, double* sv, double* y, double* z, double* mu,
+                     double* cost, int32_t* iterations, int32_t* restorations, int32_t* repaired, slpx_report* report) {
   return guard([&] {
     if (p == nullptr) throw std::runtime_error("slpx_problem_solve_batch: null problem");
     if (batch <= 0) throw std::runtime_error("slpx_problem_solve_batch: batch must be positive");
@@ -190,7 +248,7 @@ int slpx_problem_solve_batch_parameters(slpx_problem* p, int32_t batch, const do
       if (o->timeout > 0) opt.timeout = o->timeout;
       opt.feasible_ipm = o->feasible_ipm != 0;
     }
-    const slpx::BatchSolveResult r = p->problem.solve_batch(batch, x0, params, opt);
+    const slpx::BatchSolveResult r = p->problem.solve_batch(batch, x0, params, opt, warm);
     const size_t B = static_cast<size_t>(batch);
     p->batch_stats[0] = batch;
     p->batch_stats[1] = r.rounds;
@@ -205,9 +263,14 @@ int slpx_problem_solve_batch_parameters(slpx_problem* p, int32_t batch, const do
       if (restorations) restorations[b] = r.restorations[b];
     }
     if (x) std::copy(r.x.begin(), r.x.end(), x);
-    if (sv) std::copy(r.s.begin(), r.s.end(), sv);
-    if (y) std::copy(r.y.begin(), r.y.end(), y);
-    if (z) std::copy(r.z.begin(), r.z.end(), z);
+    const auto& rs = warm ? r.s_u : r.s;
+    const auto& ry = warm ? r.y_u : r.y;
+    const auto& rz = warm ? r.z_u : r.z;
+    if (sv) std::copy(rs.begin(), rs.end(), sv);
+    if (y) std::copy(ry.begin(), ry.end(), y);
+    if (z) std::copy(rz.begin(), rz.end(), z);
+    if (warm && mu) std::copy(r.mu_u.begin(), r.mu_u.end(), mu);
+    if (warm && repaired) std::copy(r.repaired.begin(), r.repaired.end(), repaired);
     if (report) {
       const auto& q = r.report;
       *report = slpx_report{q.iterations,   q.factorizations, q.solves,        q.value_sweeps,
@@ -218,6 +281,7 @@ int slpx_problem_solve_batch_parameters(slpx_problem* p, int32_t batch, const do
     }
   });
 }
+}  // namespace
 
 int slpx_problem_batch_stats(const slpx_problem* p, int64_t* out) {
   if (p == nullptr || out == nullptr || p->batch_stats[0] == 0) return -1;

@@ -3,6 +3,7 @@
 #include "ipm_formulas.h"
 #include "ipm_line_search.hpp"
 #include "restoration.hpp"
+#include "warm_start.h"
 
 #include <algorithm>
 #include <chrono>
@@ -1555,11 +1556,39 @@ ExitStatus newton_core(NewtonSystem& sys, const Vec& scales, const std::vector<I
 
 ExitStatus sqp(NewtonSystem& sys, const std::vector<double>& scales, const std::vector<IterationCallback>& callbacks,
                const Options& options, std::vector<double>& x, std::vector<double>* y_out, SolveReport* report) {
+  return sqp(sys, scales, callbacks, options, x, y_out, report, nullptr);
+}
+
+namespace {
+void check_warm_length(const Vec& v, int want, const char* what) {
+  if (!v.empty() && static_cast<int>(v.size()) != want)
+    throw std::runtime_error(std::string("warm start: ") + what + " has the wrong length");
+}
+bool any_bad(const Vec& v) {
+  for (double e : v)
+    if (warm_bad(e)) return true;
+  return false;
+}
+}  // namespace
+
+ExitStatus sqp(NewtonSystem& sys, const std::vector<double>& scales, const std::vector<IterationCallback>& callbacks,
+               const Options& options, std::vector<double>& x, std::vector<double>* y_out, SolveReport* report,
+               const WarmStart* warm) {
   const auto solve_start = clk::now();
   SolveReport local;
   SolveReport& rep = report ? *report : local;
   rep = SolveReport{};
-  Vec y(sys.structure().m_e, 0.0);  // problem.hpp:503-504
+  const int m_e = sys.structure().m_e;
+  Vec y(m_e, 0.0);  // problem.hpp:503-504
+  if (warm) {
+    check_warm_length(warm->y, m_e, "y");
+    if (any_bad(x) || any_bad(warm->y)) {
+      if (y_out) *y_out = y;
+      return ExitStatus::NONFINITE_INITIAL_GUESS;
+    }
+    if (!warm->y.empty())
+      for (int j = 0; j < m_e; ++j) y[j] = warm_scale_dual(warm->y[j], scales[1 + j], scales[0]);
+  }
   int iterations = 0;
   const ExitStatus status = sqp_core(sys, scales, callbacks, options, x, y, iterations, rep, solve_start);
   if (y_out) *y_out = y;
@@ -1643,6 +1672,14 @@ ExitStatus interior_point(NewtonSystem& sys, const std::vector<double>& scales,
                           std::vector<double>& x, std::vector<double>* s_out,
                           std::vector<double>* y_out, std::vector<double>* z_out,
                           SolveReport* report) {
+  return interior_point(sys, scales, callbacks, options, x, s_out, y_out, z_out, report, nullptr, nullptr, nullptr);
+}
+
+ExitStatus interior_point(NewtonSystem& sys, const std::vector<double>& scales,
+                          const std::vector<IterationCallback>& callbacks, const Options& options,
+                          std::vector<double>& x, std::vector<double>* s_out, std::vector<double>* y_out,
+                          std::vector<double>* z_out, SolveReport* report, const WarmStart* warm,
+                          const double* c_i_unit, WarmStartResult* result) {
   const NlpStructure& st = sys.structure();
   const auto solve_start = clk::now();
   SolveReport local;
@@ -1651,12 +1688,51 @@ ExitStatus interior_point(NewtonSystem& sys, const std::vector<double>& scales,
   // interior_point.hpp:74-79
   Vec s(st.m_i, 1.0), y(st.m_e, 0.0), z(st.m_i, 1.0);
   double mu = 0.1 * scales[0];
+  if (result) *result = WarmStartResult{};
+  if (warm) {  // warm_start.h, steps 1-5
+    const int m_e = st.m_e, m_i = st.m_i;
+    check_warm_length(warm->s, m_i, "s");
+    check_warm_length(warm->y, m_e, "y");
+    check_warm_length(warm->z, m_i, "z");
+    if (c_i_unit == nullptr) throw std::runtime_error("warm start: c_i at x0 is missing");
+    if (any_bad(x) || any_bad(warm->s) || any_bad(warm->y) || any_bad(warm->z) || warm_bad(warm->mu)) {
+      if (s_out) *s_out = s;
+      if (y_out) *y_out = y;
+      if (z_out) *z_out = z;
+      if (result) result->mu = mu;
+      return ExitStatus::NONFINITE_INITIAL_GUESS;
+    }
+    const double d_f = scales[0];
+    const double* d_ce = scales.data() + 1;
+    const double* d_ci = scales.data() + 1 + m_e;
+    const bool has_s = !warm->s.empty(), has_z = !warm->z.empty();
+    double sum = 0.0, count = 0.0;
+    if (has_s && has_z)
+      for (int j = 0; j < m_i; ++j) {
+        const double sj = warm_scale_s(warm->s[j], d_ci[j]), zj = warm_scale_dual(warm->z[j], d_ci[j], d_f);
+        if (warm_counts(sj, zj)) {
+          sum += sj * zj;
+          count += 1.0;
+        }
+      }
+    mu = warm_mu(sum, count, warm->mu, d_f, barrier_floor(d_f, options.tolerance));
+    if (!warm->y.empty())
+      for (int j = 0; j < m_e; ++j) y[j] = warm_scale_dual(warm->y[j], d_ce[j], d_f);
+    int repaired = 0;
+    for (int j = 0; j < m_i; ++j) {
+      const double d = d_ci[j];
+      s[j] = warm_slack(has_s, has_s ? warm_scale_s(warm->s[j], d) : 0.0, d * c_i_unit[j], mu, &repaired);
+      z[j] = warm_dual(has_z, has_z ? warm_scale_dual(warm->z[j], d, d_f) : 0.0, mu, s[j], &repaired);
+    }
+    if (result) result->repaired = repaired;
+  }
   int iterations = 0;
   const ExitStatus status = ipm_core(sys, scales, callbacks, options, false, x, s, y, z, mu, iterations, rep, solve_start);
   rep.t_total = since(solve_start);
   if (s_out) *s_out = s;
   if (y_out) *y_out = y;
   if (z_out) *z_out = z;
+  if (result) result->mu = mu;
   rep.iterations = iterations;
   return status;
 }

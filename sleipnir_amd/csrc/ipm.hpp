@@ -89,6 +89,19 @@ struct SolveReport {
   double t_restoration_setup = 0, t_restoration = 0;
 };
 
+// A warm start (warm_start.h: units and safeguard): the primal-dual iterate a solve begins at, beside x, in the
+// USER'S units.  An empty vector is an absent block; mu <= 0: chosen from s and z.
+struct WarmStart {
+  std::vector<double> s, y, z;
+  double mu = 0.0;
+};
+// What a solve leaves for the next one, beside x and the duals: the barrier parameter it ended at (scaled; 0 where there
+// is none) and how many entries of a given warm start the safeguard replaced or clamped.
+struct WarmStartResult {
+  double mu = 0.0;
+  int repaired = 0;
+};
+
 // Scaling at x0 (util/problem_scaling.hpp:100-107) from an unscaled V.
 std::vector<double> compute_problem_scaling(const NlpStructure& s, const std::vector<double>& V_raw);
 
@@ -101,6 +114,11 @@ ExitStatus sqp(NewtonSystem& sys, const std::vector<double>& scales, const std::
 ExitStatus newton(NewtonSystem& sys, const std::vector<double>& scales,
                   const std::vector<IterationCallback>& callbacks, const Options& options,
                   std::vector<double>& x, SolveReport* report = nullptr);
+// ... from a warm start (null: exactly the overload above): y converted to the solve's scales; a NaN or Inf in x or y
+// ends the solve with NONFINITE_INITIAL_GUESS before any iteration.  s, z and mu are not read.
+ExitStatus sqp(NewtonSystem& sys, const std::vector<double>& scales, const std::vector<IterationCallback>& callbacks,
+               const Options& options, std::vector<double>& x, std::vector<double>* y_out, SolveReport* report,
+               const WarmStart* warm);
 
 // feasibility_restoration (util/feasibility_restoration.hpp:347-628) on its own, from a given
 // iterate: sets the restoration problem up around (x, s), runs `steps` iterations of its
@@ -154,5 +172,14 @@ ExitStatus interior_point(NewtonSystem& sys, const std::vector<double>& scales,
                           std::vector<double>& x, std::vector<double>* s_out = nullptr,
                           std::vector<double>* y_out = nullptr, std::vector<double>* z_out = nullptr,
                           SolveReport* report = nullptr);
+// ... from a warm start (null: the cold start s = 1, y = 0, z = 1, mu = 0.1 d_f — exactly the overload above), converted
+// and safeguarded on the host with the formulas of warm_start.h.  c_i_unit: c_i(x0) of the sweep at unit scales the
+// scaling was computed from (read only with a warm start).  result (may be null): the barrier parameter the solve
+// ended at, and the repair count.
+ExitStatus interior_point(NewtonSystem& sys, const std::vector<double>& scales,
+                          const std::vector<IterationCallback>& callbacks, const Options& options,
+                          std::vector<double>& x, std::vector<double>* s_out, std::vector<double>* y_out,
+                          std::vector<double>* z_out, SolveReport* report, const WarmStart* warm,
+                          const double* c_i_unit, WarmStartResult* result);
 
 }  // namespace slpx

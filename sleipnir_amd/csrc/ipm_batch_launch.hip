@@ -7,6 +7,7 @@
 
 #include "eq_batch_kernels.h"
 #include "ipm_batch_kernels.h"
+#include "warm_start_batch_kernels.h"
 
 namespace slpx {
 
@@ -152,6 +153,72 @@ void BatchDevice::refresh(std::vector<double>& err) {
   sweep_iterate(true);
   SLPX_HIP_CHECK(hipMemcpyAsync(m_Vcur.p, dev.d_V(), m_Vcur.n * sizeof(double), hipMemcpyDeviceToDevice, dev.stream()));
   errors(m_Vcur.p, false, err);
+}
+
+void BatchDevice::warm_start(const BatchWarmStart& ws, const std::vector<uint8_t>& run, const std::vector<double>& mu_min,
+                             std::vector<double>& out) {
+  DeviceNlp& dev = sys.device();
+  const size_t Bs = B;
+  if (run.size() != Bs || mu_min.size() != Bs) throw std::runtime_error("BatchDevice::warm_start: wrong lengths");
+  auto put = [&](DevBuf<double>& buf, const double* h, size_t count) -> const double* {
+    if (h == nullptr || count == 0) return nullptr;
+    if (buf.n != count) buf.alloc(count);
+    SLPX_HIP_CHECK(hipMemcpy(buf.p, h, count * sizeof(double), hipMemcpyHostToDevice));
+    return buf.p;
+  };
+  std::vector<double> mu_in(2 * Bs);
+  for (size_t b = 0; b < Bs; ++b) {
+    mu_in[2 * b] = ws.mu ? ws.mu[b] : 0.0;
+    mu_in[2 * b + 1] = mu_min[b];
+  }
+  BatchWarmArgs A{};
+  A.n = n;
+  A.m_e = m_e;
+  A.m_i = m_i;
+  A.s0 = put(m_ws_s, ws.s, Bs * m_i);
+  A.y0 = put(m_ws_y, ws.y, Bs * m_e);
+  A.z0 = put(m_ws_z, ws.z, Bs * m_i);
+  A.mu_in = put(m_ws_mu, mu_in.data(), 2 * Bs);
+  A.V = dev.d_V();
+  A.v_stride = nV;
+  A.off_ci = sys.structure().off_ci;
+  A.S = m_scales.p;
+  A.ns = ns;
+  A.cur = m_cur;
+  if (m_ws_run.n != Bs) m_ws_run.alloc(Bs);
+  SLPX_HIP_CHECK(hipMemcpy(m_ws_run.p, run.data(), Bs, hipMemcpyHostToDevice));
+  A.run = m_ws_run.p;
+  if (m_ws_out.n != Bs * kWarmOutN) m_ws_out.alloc(Bs * kWarmOutN);
+  m_ws_out.zero(dev.stream());
+  A.out = m_ws_out.p;
+  hipLaunchKernelGGL(batch_warm_start_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), A);
+  SLPX_HIP_CHECK(hipGetLastError());
+  out.resize(Bs * kWarmOutN);
+  dev.download(m_ws_out.p, out.data(), out.size());
+}
+
+void BatchDevice::unscaled_iterate(const std::vector<uint8_t>& run, std::vector<double>& s_u, std::vector<double>& y_u,
+                                   std::vector<double>& z_u) {
+  DeviceNlp& dev = sys.device();
+  const size_t Bs = B;
+  if (run.size() != Bs) throw std::runtime_error("BatchDevice::unscaled_iterate: wrong lengths");
+  // (the three outputs in the buffers a warm start's inputs came in: they are not needed any more)
+  const size_t Bi = at_least_1(Bs * m_i), Be = at_least_1(Bs * m_e);
+  if (m_ws_s.n != Bi) m_ws_s.alloc(Bi);
+  if (m_ws_y.n != Be) m_ws_y.alloc(Be);
+  if (m_ws_z.n != Bi) m_ws_z.alloc(Bi);
+  for (auto* b : {&m_ws_s, &m_ws_y, &m_ws_z}) b->zero(dev.stream());
+  if (m_ws_run.n != Bs) m_ws_run.alloc(Bs);
+  SLPX_HIP_CHECK(hipMemcpy(m_ws_run.p, run.data(), Bs, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(batch_unscale_iterate_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), m_e, m_i, m_cur, m_scales.p,
+                     ns, m_ws_run.p, m_ws_s.p, m_ws_y.p, m_ws_z.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  s_u.resize(Bs * m_i);
+  y_u.resize(Bs * m_e);
+  z_u.resize(Bs * m_i);
+  if (!s_u.empty()) dev.download(m_ws_s.p, s_u.data(), s_u.size());
+  if (!y_u.empty()) dev.download(m_ws_y.p, y_u.data(), y_u.size());
+  if (!z_u.empty()) dev.download(m_ws_z.p, z_u.data(), z_u.size());
 }
 
 // ---- BatchIpmDevice (ipm_batch.hpp) ----

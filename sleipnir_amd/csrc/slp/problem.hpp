@@ -29,6 +29,7 @@
 #include "../ipm_batch.hpp"
 #include "../ipm_host.hpp"
 #include "../newton.hpp"
+#include "../warm_start.h"
 #include "variable.hpp"
 
 namespace slp {
@@ -182,7 +183,46 @@ class ProblemF64 {
   }
 
   // problem.hpp:281-679
-  ExitStatus solve(const Options& options = Options{}, bool spy = false) {
+  ExitStatus solve(const Options& options = Options{}, bool spy = false) { return solve_from(options, spy, nullptr); }
+  // ... from a warm start (warm_start.h): the variables' values are x, `warm` the rest of the iterate in the user's
+  // units — what iterate() returned after an earlier solve, typically of a neighbouring problem (set_parameters).
+  ExitStatus solve(const Options& options, bool spy, const slpx::WarmStart& warm) { return solve_from(options, spy, &warm); }
+
+  // The primal-dual iterate the last solve() ended at, in the user's units (warm_start.h): the duals are those of
+  // f - y^T c_e - z^T c_i as written, whatever scaling the solve ran with.  (slack(), equality_duals(),
+  // inequality_duals() keep returning the scaled ones.)
+  struct Iterate {
+    std::vector<double> x, s, y, z;
+    double mu = 0.0;
+  };
+  bool has_iterate() const { return m_has_iterate; }
+  Iterate iterate() const {
+    if (!m_has_iterate) throw std::runtime_error("iterate: the problem has not been solved");
+    const size_t m_e = m_y.size(), m_i = m_s.size();
+    Iterate it;
+    it.x = m_iterate_x;
+    it.s.resize(m_i);
+    it.y.resize(m_e);
+    it.z.resize(m_i);
+    const double d_f = m_scales[0];
+    for (size_t j = 0; j < m_e; ++j) it.y[j] = slpx::warm_unscale_dual(m_y[j], m_scales[1 + j], d_f);
+    for (size_t j = 0; j < m_i; ++j) {
+      const double d = m_scales[1 + m_e + j];
+      it.s[j] = slpx::warm_unscale_s(m_s[j], d);
+      it.z[j] = slpx::warm_unscale_dual(m_z[j], d, d_f);
+    }
+    it.mu = slpx::warm_unscale_mu(m_warm_result.mu, d_f);
+    return it;
+  }
+  // how many entries of the last solve's warm start the safeguard replaced or clamped (0 after a cold start)
+  int warm_start_repaired() const { return m_warm_result.repaired; }
+
+ private:
+  ExitStatus solve_from(const Options& options, bool spy, const slpx::WarmStart* warm) {
+    // (nothing given beside x: the cold start, as in a batch)
+    if (warm && warm->s.empty() && warm->y.empty() && warm->z.empty() && warm->mu <= 0.0) warm = nullptr;
+    m_has_iterate = false;
+    m_warm_result = slpx::WarmStartResult{};
     auto& g = detail::G();
     std::vector<double> x(m_decision_variables.size());
     for (size_t i = 0; i < x.size(); ++i) x[i] = m_decision_variables[i].value();
@@ -239,19 +279,24 @@ class ProblemF64 {
       m_s.clear();
       m_y.clear();
       m_z.clear();
-      status = slpx::newton(*m_sys, m_scales, callbacks, options, x, &m_report);
+      status = slpx::newton(*m_sys, m_scales, callbacks, options, x, &m_report);  // (a warm start: x only)
     } else if (m_inequality_constraints.empty()) {
       m_s.clear();
       m_z.clear();
-      status = slpx::sqp(*m_sys, m_scales, callbacks, options, x, &m_y, &m_report);
+      status = slpx::sqp(*m_sys, m_scales, callbacks, options, x, &m_y, &m_report, warm);
     } else {
-      status = slpx::interior_point(*m_sys, m_scales, callbacks, options, x, &m_s, &m_y, &m_z,
-                                    &m_report);
+      // (c_i at x0 for a warm start's slack repair: from the sweep at unit scales the scaling came from)
+      status = slpx::interior_point(*m_sys, m_scales, callbacks, options, x, &m_s, &m_y, &m_z, &m_report, warm,
+                                    V.data() + m_sys->structure().off_ci, &m_warm_result);
     }
     // problem.hpp:676
     for (size_t i = 0; i < x.size(); ++i) g.val[m_decision_variables[i].expr] = x[i];
+    m_iterate_x = x;
+    m_has_iterate = true;
     return status;
   }
+
+ public:
 
   bool has_callbacks() const { return !m_iteration_callbacks.empty() || !m_persistent_iteration_callbacks.empty(); }
 
@@ -266,7 +311,10 @@ class ProblemF64 {
   // solved from x0[b]; null: the problem as it is, exactly the overload above.  The rows live in a constant pool per
   // instance on the batch system (DeviceNlp::set_parameters) for the duration of the call: the variables' and the
   // parameters' values are left as they are, and the shared pool is in force again on return.
-  slpx::BatchSolveResult solve_batch(int batch, const double* x0, const double* params, const Options& options) {
+  // warm (null: every instance starts cold): the rest of each instance's first iterate in the user's units, and the
+  // request for the end iterate in those units (batch_lockstep.hpp: BatchWarmStart).
+  slpx::BatchSolveResult solve_batch(int batch, const double* x0, const double* params, const Options& options,
+                                     const slpx::BatchWarmStart* warm = nullptr) {
     if (batch <= 0) throw std::runtime_error("solve_batch: batch must be positive");
     if (x0 == nullptr) throw std::runtime_error("solve_batch: x0 is null");
     if (has_callbacks()) throw std::runtime_error("solve_batch: the problem has callbacks registered");
@@ -282,6 +330,13 @@ class ProblemF64 {
     out.cost.assign(B, m_f ? m_f->value() : 0.0);
     out.iterations.assign(B, 0);
     out.restorations.assign(B, 0);
+    if (warm) {
+      out.s_u.assign(B * m_i, 0.0);
+      out.y_u.assign(B * m_e, 0.0);
+      out.z_u.assign(B * m_i, 0.0);
+      out.mu_u.assign(B, 0.0);
+      out.repaired.assign(B, 0);
+    }
     // problem.hpp:304-313
     if (cost_function_type() <= ExpressionType::CONSTANT && equality_constraint_type() <= ExpressionType::CONSTANT &&
         inequality_constraint_type() <= ExpressionType::CONSTANT)
@@ -353,9 +408,9 @@ class ProblemF64 {
       const std::vector<double> x0v(x0, x0 + B * n);
       const std::vector<double>* rows = params != nullptr ? &pv : nullptr;
       try {
-        if (m_i > 0) slpx::interior_point_batch(sys, *m_sys, scales, options, x0v, run, out, m_batch_restoration, rows);
-        else if (m_e > 0) slpx::sqp_batch(sys, *m_sys, scales, options, x0v, run, out, m_batch_restoration, rows);
-        else slpx::newton_batch(sys, *m_sys, scales, options, x0v, run, out, rows);
+        if (m_i > 0) slpx::interior_point_batch(sys, *m_sys, scales, options, x0v, run, out, m_batch_restoration, rows, warm);
+        else if (m_e > 0) slpx::sqp_batch(sys, *m_sys, scales, options, x0v, run, out, m_batch_restoration, rows, warm);
+        else slpx::newton_batch(sys, *m_sys, scales, options, x0v, run, out, rows, warm);
       } catch (...) {
         reinstall_scaling();
         throw;
@@ -386,6 +441,7 @@ class ProblemF64 {
     dev.sweep_full();
     dev.download_V(V.data());
     m_scales = slpx::compute_problem_scaling(m_sys->structure(), V);
+    m_has_iterate = false;  // (m_scales are no longer the last solve's)
     dev.set_scaling(m_scales);
     return slpx::feasibility_restoration_steps(*m_sys, m_scales, options, x, s, y, z, mu, steps, &m_report);
   }
@@ -424,6 +480,7 @@ class ProblemF64 {
     dev.sweep_full();
     dev.download_V(V.data());
     m_scales = slpx::compute_problem_scaling(st, V);
+    m_has_iterate = false;
     dev.set_scaling(m_scales);
     // c_e, c_i, g at every instance's x: one batched sweep at unit scales, scaled here as the tape would
     slpx::NewtonSystem& sys = batch_system(batch);
@@ -666,6 +723,11 @@ class ProblemF64 {
   std::vector<std::pair<NodeId, double>> m_param_snapshot;  // (parameter node, value the compiled system holds)
   int64_t m_compile_count = 0;                              // compile_count()
   std::vector<double> m_scales, m_s, m_y, m_z;
+  // iterate(): x, the barrier parameter and the repair count of the last solve(); m_scales, m_s, m_y, m_z are its too
+  // as long as m_has_iterate holds
+  std::vector<double> m_iterate_x;
+  slpx::WarmStartResult m_warm_result;
+  bool m_has_iterate = false;
   SolveReport m_report;
 };
 

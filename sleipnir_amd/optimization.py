@@ -21,7 +21,8 @@ from sleipnir_amd.autodiff import (EqualityConstraints, ExpressionType, Inequali
                                    VariableMatrix, _is_scalar)
 
 __all__ = ["ExitStatus", "Problem", "OCP", "DynamicsType", "TimestepMethod", "TranscriptionMethod",
-           "EqualityConstraints", "InequalityConstraints", "IterationInfo", "bounds", "multistart"]
+           "EqualityConstraints", "InequalityConstraints", "IterationInfo", "bounds", "multistart",
+           "Iterate", "BatchIterate", "BatchResult"]
 
 
 class ExitStatus(enum.IntEnum):
@@ -94,6 +95,28 @@ class IterationInfo:
 
 
 @dataclasses.dataclass
+class Iterate:
+    """A primal-dual iterate in the user's units, whatever scaling the solve ran with: x, the slacks s of the
+    inequality constraints, the multipliers y, z of f - y^T c_e - z^T c_i as the model was written, and the barrier
+    parameter mu.  What Problem.iterate() returns and Problem.solve(warm_start=...) takes; any of s, y, z may be None
+    (absent) and mu None or <= 0 (chosen from s and z)."""
+    x: object = None
+    s: object = None
+    y: object = None
+    z: object = None
+    mu: object = None
+
+    def _blocks(self):
+        return {k: getattr(self, k) for k in ("s", "y", "z", "mu") if getattr(self, k) is not None}
+
+
+@dataclasses.dataclass
+class BatchIterate(Iterate):
+    """Iterate for B instances: x (B, n), s and z (B, m_i), y (B, m_e), mu (B).  x is not read by solve_batch, whose
+    initial_guesses are the instances' x."""
+
+
+@dataclasses.dataclass
 class BatchResult:
     """What Problem.solve_batch returns: per instance the ExitStatus, the end iterate (x: (B, n),
     s, z: (B, m_i), y: (B, m_e)), the unscaled cost, the iteration and restoration counts; `report` holds
@@ -115,6 +138,10 @@ class BatchResult:
     handoffs: int = 0
     driver: int = 0
     restoration_lockstep: dict = dataclasses.field(default_factory=dict)
+    # with solve_batch(warm_start=...) only: the end iterates in the user's units (s, y, z above are then in those units
+    # too), and per instance the entries of the warm start its safeguard replaced or clamped
+    iterate: object = None
+    repaired: object = None
 
 
 class Problem:
@@ -180,19 +207,36 @@ class Problem:
         """problem.hpp:281-679.  Keyword arguments: tolerance, max_iterations, timeout,
         feasible_ipm, diagnostics, spy (bind_problem.cpp:80-112); anything else is a KeyError like
         the reference's."""
-        allowed = {"tolerance", "max_iterations", "timeout", "feasible_ipm", "diagnostics", "spy"}
+        allowed = {"tolerance", "max_iterations", "timeout", "feasible_ipm", "diagnostics", "spy", "warm_start"}
         for k in kwargs:
             if k not in allowed:
                 raise KeyError(f"Invalid keyword argument: {k}")
         timeout = kwargs.pop("timeout", 0.0)
         if timeout is None or math.isinf(timeout):
             timeout = 0.0
+        # warm_start = Iterate (no reference counterpart): the solve begins there; its x, where given, becomes the
+        # variables' values first
+        warm = kwargs.pop("warm_start", None)
+        if warm is not None:
+            if warm.x is not None:
+                self._p.set_x(np.asarray(warm.x, dtype=np.float64).ravel())
+            kwargs["warm_start"] = warm._blocks()
         # problem.hpp:304-313: nothing to do for a problem without cost and constraints
         if all(t <= ExpressionType.CONSTANT for t in self._p.types()):
             self.report = None
             return ExitStatus.SUCCESS
         status, self.report = self._p.solve(timeout=timeout, **kwargs)
         return ExitStatus(status)
+
+    def iterate(self) -> "Iterate":
+        """The primal-dual iterate the last solve() ended at, in the user's units (slpx_problem_get_iterate): pass it
+        to the next solve(warm_start=...), of this problem after set_parameters() or of any with the same rows."""
+        x, s, y, z, mu = self._p.iterate()
+        return Iterate(x=x, s=s, y=y, z=z, mu=mu)
+
+    def warm_start_repaired(self) -> int:
+        """How many entries of its warm start the last solve's safeguard replaced or clamped."""
+        return self._p.warm_start_repaired()
 
     def solve_batch(self, initial_guesses, **kwargs) -> "BatchResult":
         """B instances of this problem, one per row of `initial_guesses` (shape (B, n), decision-variable
@@ -202,10 +246,13 @@ class Problem:
         (default) or "lockstep": how instances that need feasibility restoration run it
         (slpx_problem_set_batch_restoration); parameters = array (B, n_p): instance b is this problem with row b for
         the values of parameters() (slpx_problem_solve_batch_parameters).  The variables' and the parameters'
-        values are left as they are.  Raises SlpxError where the library cannot run a batch (no device,
+        values are left as they are.  warm_start = BatchIterate (possibly empty): instance b begins at row b of its s,
+        y, z and mu instead of the cold start — its x is not read, initial_guesses are the instances' x — and the
+        result carries `iterate` (what the next call takes) and `repaired`, with s, y, z in the user's units
+        (slpx_problem_solve_batch_warm).  Raises SlpxError where the library cannot run a batch (no device,
         callbacks registered)."""
         allowed = {"tolerance", "max_iterations", "timeout", "feasible_ipm", "diagnostics", "spy", "restoration",
-                   "parameters"}
+                   "parameters", "warm_start"}
         for k in kwargs:
             if k not in allowed:
                 raise KeyError(f"Invalid keyword argument: {k}")
@@ -218,7 +265,17 @@ class Problem:
         n = len(self._decision_variables)
         if guesses.ndim != 2 or guesses.shape[1] != n or guesses.shape[0] < 1:
             raise ValueError(f"initial_guesses must have shape (B, {n}) with B >= 1")
+        warm = kwargs.pop("warm_start", None)
+        if warm is not None:
+            kwargs["warm_start"] = warm._blocks()
         r = self._p.solve_batch(guesses, timeout=timeout, **kwargs)
+        if warm is not None:
+            return BatchResult(status=[ExitStatus(int(s)) for s in r["status"]], x=r["x"], s=r["s"], y=r["y"],
+                               z=r["z"], cost=r["cost"], iterations=r["iterations"], restorations=r["restorations"],
+                               report=r["report"], rounds=r["rounds"], handoffs=r["handoffs"], driver=r["driver"],
+                               restoration_lockstep=r.get("restoration_lockstep", {}),
+                               iterate=BatchIterate(x=r["x"], s=r["s"], y=r["y"], z=r["z"], mu=r["mu"]),
+                               repaired=r["repaired"])
         return BatchResult(status=[ExitStatus(int(s)) for s in r["status"]], x=r["x"], s=r["s"], y=r["y"],
                            z=r["z"], cost=r["cost"], iterations=r["iterations"], restorations=r["restorations"],
                            report=r["report"], rounds=r["rounds"], handoffs=r["handoffs"], driver=r["driver"],
@@ -233,9 +290,10 @@ class Problem:
         """New values for parameters(), in that order, written in place into the compiled problem: the next solve() or
         solve_batch() does not compile again (Variable.set_value on a parameter does).  An MPC loop:
 
+            problem.solve()
             for x_now in measurements:
                 problem.set_parameters(x_now)
-                problem.solve()
+                problem.solve(warm_start=problem.iterate())
         """
         self._p.set_parameters(values)
 
