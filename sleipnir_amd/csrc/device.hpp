@@ -21,6 +21,7 @@
 #include <utility>
 #include <vector>
 
+#include "device_layout.h"
 #include "kkt_plan.hpp"
 #include "ldlt_symbolic.hpp"
 #include "nlp.hpp"
@@ -170,7 +171,7 @@ struct TapeDevice {
   DevBuf<uint64_t> tmpl_params_dev;        // ... on the device: the kernel's last argument points here
   hipModule_t tmpl_mod = nullptr;
   uint32_t n_bodies = 0;
-  DevBuf<uint32_t> tmpl_inst;  // per body: leaf bindings + output destinations, transposed (kernels.hip)
+  DevBuf<uint32_t> tmpl_inst;  // per body: leaf bindings + output destinations, transposed (device_images.hpp: pack_template_tables)
   DevBuf<uint32_t> tmpl_table[2];
   uint32_t tmpl_blocks[2] = {0, 0};
   uint32_t n_templated_tasks = 0;
@@ -245,6 +246,33 @@ struct KktDev {
   int off_f, off_ce, off_ci, off_g, off_Ae, off_Ai;
 };
 
+// The KKT and LDLT plans on the device, like TapeDevice: the buffers, upload() from the host plan (the derived tables
+// through the packers of device_images.hpp), view() = what the kernels take.
+struct KktPlanDevice {
+  DevBuf<int32_t> dptr, dsrc, pptr, pa, pb, pr, g_src, ae_colptr, ae_rowidx, ai_colptr, ai_rowidx, ai_rowptr, ai_col, ai_src,
+      fast_src, diag_pos;
+  int n = 0, m_e = 0, m_i = 0, dim = 0, nnz_lhs = 0;
+  int off_f = 0, off_ce = 0, off_ci = 0, off_g = 0, off_Ae = 0, off_Ai = 0;
+  void upload(const NlpStructure& s, const KktPlan& k);
+  KktDev view() const;
+};
+struct LdltPlanDevice {
+  DevBuf<LdltTask> tasks;
+  DevBuf<int32_t> ent_src, perm;
+  DevBuf<uint8_t> ent_flags;
+  DevBuf<uint16_t> ent_col;
+  DevBuf<uint32_t> ent_out, ent_pair_ptr, ent_contrib_ptr, contrib_idx, ext_dst, lvl_ptr, col_perm, col_lvl_ptr, fwd_ptr,
+      fwd_contrib_ptr, scontrib_idx, sext_ptr, sext_dst, bwd_ptr, round_ptr;
+  DevBuf<LdltPair> pairs;
+  DevBuf<LdltSolveItem> fwd_items, sext_items, bwd_items;
+  DevBuf<LdltSn> sn_desc;
+  DevBuf<uint32_t> sn_lvl_ptr, col_sn, lvl_pack, col_lvl_pack;
+  DevBuf<uint2> bwd_range;
+  int n_rounds = 0;
+  void upload(const LdltPlan& l);
+  LdltDev view() const;  // (clock_task: nobody)
+};
+
 // Work that rides in another kernel's launch (one problem, single-launch factorization).  Every
 // kernel boundary of a Newton step costs 1-2 us of idle GPU plus the consumer's start-up, and an
 // assembly pass in front of the factorization is a chain of three dependent trips to memory
@@ -263,13 +291,8 @@ struct KktDev {
 //    the factorization's inertia counters to the host — at the START of the launch: the host
 //    learns the verdict of the attempt while the solve is still running and has the next
 //    launch queued by the time it ends.
-// One addend of an lhs / rhs entry that is a sum (kkt_kernels.h: kkt_terms_value); twelve bytes,
-// staged into LDS with the task's plan.  kind = b >> 28, row = b & 0x0fffffff:
-//   0  direct += V[a]                 1  g = V[a]                  2  aey += V[a] * y[row]
-//   3  ait += V[a] * (-(z/s)[row] * V[c] + mu / s[row] + z[row])   4  prod += (V[a] * (z/s)[row]) * V[c]
-struct KktTerm {
-  int32_t a, b, c;
-};
+// The static side of both — KktTerm, BsRow, BsTerm of device_layout.h — is made by build_inline_kkt and
+// build_inline_backsub of device_images.cpp.
 struct KktFuse {
   int inline_kkt = 0;
   int n_blocks = 0;  // separable sums riding along
@@ -289,14 +312,6 @@ struct KktFuse {
   double* store_rhs = nullptr;
   const NlpStructure::SumReduce* red = nullptr;
   const double* scales = nullptr;
-};
-struct BsRow {
-  int32_t r;       // row of A_i
-  uint32_t terms;  // first term (relative to the task's block) | number of terms << 20
-};
-struct BsTerm {
-  int32_t a;     // V slot of the A_i value
-  uint32_t ref;  // the task's own column (local index) or 0x80000000 | permuted column of an ancestor
 };
 struct BacksubFuse {
   int on = 0;
@@ -705,6 +720,21 @@ class DeviceNlp {
   void write_reg(const std::vector<double>& delta, const std::vector<double>& gamma,
                  const std::vector<uint8_t>& active);
   void enqueue_factor(int parity, hipStream_t stream);
+  // the constructor's phases, in its order (kernels.hip)
+  void choose_chain_mode();
+  void upload_tapes();
+  void raise_lds_limits();
+  void upload_kkt_plan();
+  void upload_ldlt_plan();
+  void choose_launch_modes();
+  void upload_inline_kkt(const struct InlineKkt& ik);
+  void upload_inline_backsub(const struct InlineBacksub& ib);
+  void upload_mf(const struct MfImages& im);  // the multifrontal step where every task is resident at once; sets m_mf
+  void alloc_dense_buffers();
+  void alloc_value_buffers();
+  void arm_handover_buffers();
+  void alloc_interleaved_buffers();
+  void alloc_pinned();
 
   DeviceArena m_arena;  // the plan arrays uploaded by the constructor (DevBuf::upload places them here)
   const NlpStructure& m_s_ref;
@@ -716,20 +746,11 @@ class DeviceNlp {
 
   TapeDevice m_full, m_values;
   DevBuf<NlpStructure::SumReduce> m_reduces;
-  // KKT plan
-  DevBuf<int32_t> m_dptr, m_dsrc, m_pptr, m_pa, m_pb, m_pr, m_gsrc, m_ae_colptr, m_ae_rowidx,
-      m_ai_colptr, m_ai_rowidx, m_ai_rowptr, m_ai_col, m_ai_src, m_diag_pos, m_fast_src;
+  // the KKT and LDLT plans, and what the hot path hands the kernels of them
+  KktPlanDevice m_kplan;
   KktDev m_kdev{};
-  // LDLT plan
-  DevBuf<LdltTask> m_ltasks;
-  DevBuf<int32_t> m_ent_src, m_perm;
-  DevBuf<uint8_t> m_ent_flags;
-  DevBuf<uint16_t> m_ent_col;
-  DevBuf<uint32_t> m_ent_out, m_ent_pair_ptr, m_ent_contrib_ptr, m_contrib_idx, m_ext_dst, m_llvl_ptr,
-      m_col_perm, m_col_lvl_ptr, m_fwd_ptr, m_fwd_contrib_ptr, m_scontrib_idx, m_sext_ptr,
-      m_sext_dst, m_bwd_ptr;
-  DevBuf<LdltPair> m_pairs;
-  DevBuf<LdltSn> m_sn_desc;
+  LdltPlanDevice m_lplan;
+  LdltDev m_ldev{};
   DevBuf<int32_t> m_lhs_colptr, m_lhs_rowidx, m_lhs_rowptr, m_lhs_rowent, m_lhs_rowcol;  // refine_solution (uploaded on first use)
   // the dense branch (LdltPlan::dense, ldlt_dense_kernels.h): the factors of every problem as a dim x dim matrix
   bool m_dense = false, m_dense_pivoted = false;
@@ -763,10 +784,6 @@ class DeviceNlp {
     m_fact_delta[b] = delta;
     m_fact_gamma[b] = gamma;
   }
-  DevBuf<uint32_t> m_sn_lvl_ptr, m_col_sn, m_lvl_pack, m_col_lvl_pack;
-  DevBuf<uint2> m_bwd_range;
-  DevBuf<LdltSolveItem> m_fwd_items, m_sext_items, m_bwd_items;
-  LdltDev m_ldev{};
   // per-batch values
   DevBuf<double> m_in, m_in_scale, m_scales, m_V, m_s, m_y, m_z, m_mu, m_lhs, m_rhs, m_p, m_ps,
       m_pz, m_D, m_Lx, m_contrib, m_scontrib, m_zv, m_xg, m_scratch;
@@ -812,12 +829,6 @@ class DeviceNlp {
   int m_mf_threads = 1024;            // 512 where the 1024-thread workgroups of every task are not resident at once
   int m_twin_threads = 1024;          // ... of a launch of two attempts (twin_available)
   uint32_t m_mf_lds = 0;
-  // host copies of the inline KKT / back-substitution plans (build_mf packs them into the task images)
-  std::vector<int32_t> m_h_vsrc;
-  std::vector<KktTerm> m_h_terms;
-  std::vector<uint2> m_h_task_terms;
-  std::vector<BsRow> m_h_bs_plan;
-  std::vector<uint4> m_h_bs_task_plan;
   DevBuf<LdltMfTask> m_mf_tasks;
   DevBuf<LdltFront> m_mf_fronts;
   uint32_t m_mf_image_stride16 = 0;
@@ -836,17 +847,14 @@ class DeviceNlp {
   DevBuf<double> m_Lx_tw, m_D_tw, m_zv_tw, m_p_tw, m_ps_tw, m_pz_tw, m_mf_contrib_tw, m_xg_tw, m_xg2_tw;
   DevBuf<LdltStats> m_stats_tw;
   int m_stats_tw_cur = 0, m_xg_tw_parity = 0;
-  void build_mf(const LdltPlan& l);
   DevBuf<unsigned int> m_ipm_err_done;
   DevBuf<BsRow> m_bs_plan;            // BacksubFuse::plan (rows and terms share the 8-byte element size)
   DevBuf<uint4> m_bs_task_plan;
   uint32_t m_solve_lds_inline = 0;    // dynamic LDS of the backward solve with the rows staged
-  void build_inline_backsub(const KktPlan& k, const LdltPlan& l);
   DevBuf<int32_t> m_ent_vsrc;
   DevBuf<KktTerm> m_kkt_terms;
   DevBuf<uint2> m_task_terms;
   uint32_t m_factor_lds_inline = 0;   // dynamic LDS of the factorization with the terms staged
-  void build_inline_kkt(const NlpStructure& s, const KktPlan& k, const LdltPlan& l);
   bool m_lhs_stale = false, m_rhs_stale = false;  // memory does not hold the system of the current state
   void solve_after_factor_impl(const LdltStats* publish);
   // all rounds of a factorization / backward solve in one launch (device-side round
@@ -862,7 +870,6 @@ class DeviceNlp {
   DevBuf<uint32_t> m_il_meta, m_il_meta_off;  // per task: the plan slices the factor kernel stages
   uint32_t m_il_factor_lds = 0, m_il_solve_lds = 0;
   bool m_slot_handoff = false;        // factorization rounds hand over through the update block slots
-  DevBuf<uint32_t> m_round_ptr;
   DevBuf<unsigned int> m_fround_cnt, m_bround_cnt;  // [2][batch][n_rounds]
   std::vector<double> m_V_static;  // scaled static values (host copy)
   // interior-point iteration state (ipm_enable)

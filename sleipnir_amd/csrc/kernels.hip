@@ -23,6 +23,7 @@
 #include <unordered_map>
 
 #include "device.hpp"
+#include "device_images.hpp"
 #include "kkt_kernels.h"
 #include "ldlt_kernels.h"
 #include "ldlt_mf_kernels.h"
@@ -410,45 +411,13 @@ void TapeDevice::upload(const TapeProgram& p, int batch, uint32_t n_unscaled_inp
   n_templated_tasks = 0;
   tmpl_blocks[0] = tmpl_blocks[1] = 0;
   if (n_bodies) {
-    std::vector<uint32_t> inst, table[2];
-    for (const TapeTemplateGroup& g : jit.groups) {
-      // the family's leaf bindings and output destinations, transposed: row r of instance i at
-      // [r * n_inst + i] (rows: leaves | value dst | value scale | jacobian dst | jacobian scale),
-      // so that the lanes of a wave — consecutive instances — read consecutive words
-      const uint32_t n_inst = static_cast<uint32_t>(g.tasks.size()), inst_off = static_cast<uint32_t>(inst.size());
-      const TapeTask& rep = p.tasks[g.tasks.front()];
-      const uint32_t rows = rep.n_leaf + 2 * rep.n_vout + 2 * rep.n_jout;
-      inst.resize(inst.size() + static_cast<size_t>(rows) * n_inst);
-      for (uint32_t i = 0; i < n_inst; ++i) {
-        const TapeTask& t = p.tasks[g.tasks[i]];
-        uint32_t* col = inst.data() + inst_off + i;
-        uint32_t r = 0;
-        for (uint32_t q = 0; q < rep.n_leaf; ++q) col[static_cast<size_t>(r++) * n_inst] = p.leaf_src[t.leaf_off + q];
-        for (uint32_t q = 0; q < rep.n_vout; ++q) col[static_cast<size_t>(r++) * n_inst] = p.vout_dst[t.vout_off + q];
-        for (uint32_t q = 0; q < rep.n_vout; ++q)
-          col[static_cast<size_t>(r++) * n_inst] = static_cast<uint32_t>(p.vout_scale[t.vout_off + q]);
-        for (uint32_t q = 0; q < rep.n_jout; ++q) col[static_cast<size_t>(r++) * n_inst] = p.jout_dst[t.jout_off + q];
-        for (uint32_t q = 0; q < rep.n_jout; ++q)
-          col[static_cast<size_t>(r++) * n_inst] = static_cast<uint32_t>(p.jout_scale[t.jout_off + q]);
-      }
-      n_templated_tasks += n_inst;
-      // Adjoint rows are split into wave-uniform groups while the launch would otherwise
-      // leave most SIMDs idle; with enough instances x batch items every lane runs all
-      // groups (-1) and the forward part is not recomputed per group.
-      const uint32_t waves = (n_inst + tmpl_threads - 1) / tmpl_threads;  // workgroups of one row group
-      const bool split = ((n_inst + 63) / 64) * static_cast<uint32_t>(batch) < 512 && g.n_groups > 1;
-      const int mode[2] = {0, split ? static_cast<int>(g.n_groups) : -1};
-      for (int m = 0; m < 2; ++m) {
-        table[m].push_back(tmpl_blocks[m]);
-        table[m].push_back(n_inst);
-        table[m].push_back(inst_off);
-        table[m].push_back(static_cast<uint32_t>(mode[m]));
-        tmpl_blocks[m] += waves * static_cast<uint32_t>(std::max(1, mode[m]));
-      }
+    const TemplateTables tt = pack_template_tables(p, jit.groups, batch, tmpl_threads);
+    n_templated_tasks = tt.n_templated_tasks;
+    tmpl_inst.upload(tt.inst);
+    for (int m = 0; m < 2; ++m) {
+      tmpl_table[m].upload(tt.table[m]);
+      tmpl_blocks[m] = tt.blocks[m];
     }
-    tmpl_inst.upload(inst);
-    tmpl_table[0].upload(table[0]);
-    tmpl_table[1].upload(table[1]);
   }
   auto interpreted = [&](const std::vector<uint32_t>& list) {
     std::vector<uint32_t> out;
@@ -508,6 +477,123 @@ TapeDev TapeDevice::view() const {
                  slot_edge_ptr16.p, edges16.p,  consts_stride};
 }
 
+void KktPlanDevice::upload(const NlpStructure& s, const KktPlan& k) {
+  dptr.upload(k.dptr);
+  dsrc.upload(k.dsrc);
+  pptr.upload(k.pptr);
+  pa.upload(k.pa);
+  pb.upload(k.pb);
+  pr.upload(k.pr);
+  g_src.upload(k.g_src);
+  ae_colptr.upload(s.Ae.colptr);
+  ae_rowidx.upload(s.Ae.rowidx);
+  ai_colptr.upload(s.Ai.colptr);
+  ai_rowidx.upload(s.Ai.rowidx);
+  ai_rowptr.upload(k.ai_rowptr);
+  ai_col.upload(k.ai_col);
+  ai_src.upload(k.ai_src);
+  fast_src.upload(k.fast_src);
+  diag_pos.upload(lhs_diagonal_positions(k));
+  n = k.n, m_e = k.m_e, m_i = k.m_i, dim = k.dim, nnz_lhs = k.lhs.nnz();
+  off_f = s.off_f, off_ce = s.off_ce, off_ci = s.off_ci, off_g = s.off_g, off_Ae = s.off_Ae, off_Ai = s.off_Ai;
+}
+
+KktDev KktPlanDevice::view() const {
+  KktDev K{};
+  K.n = n, K.m_e = m_e, K.m_i = m_i, K.dim = dim, K.nnz_lhs = nnz_lhs;
+  K.dptr = dptr.p;
+  K.dsrc = dsrc.p;
+  K.pptr = pptr.p;
+  K.pa = pa.p;
+  K.pb = pb.p;
+  K.pr = pr.p;
+  K.g_src = g_src.p;
+  K.ae_colptr = ae_colptr.p;
+  K.ae_rowidx = ae_rowidx.p;
+  K.ai_colptr = ai_colptr.p;
+  K.ai_rowidx = ai_rowidx.p;
+  K.ai_rowptr = ai_rowptr.p;
+  K.ai_col = ai_col.p;
+  K.ai_src = ai_src.p;
+  K.fast_src = fast_src.p;
+  K.off_f = off_f, K.off_ce = off_ce, K.off_ci = off_ci, K.off_g = off_g, K.off_Ae = off_Ae, K.off_Ai = off_Ai;
+  return K;
+}
+
+void LdltPlanDevice::upload(const LdltPlan& l) {
+  tasks.upload(l.tasks);
+  ent_src.upload(l.ent_src);
+  ent_flags.upload(l.ent_flags);
+  ent_col.upload(l.ent_col);
+  ent_out.upload(l.ent_out);
+  ent_pair_ptr.upload(l.ent_pair_ptr);
+  ent_contrib_ptr.upload(l.ent_contrib_ptr);
+  contrib_idx.upload(l.contrib_idx);
+  ext_dst.upload(l.ext_dst);
+  lvl_ptr.upload(l.lvl_ptr);
+  pairs.upload(l.pairs);
+  col_perm.upload(l.col_perm);
+  col_lvl_ptr.upload(l.col_lvl_ptr);
+  fwd_ptr.upload(l.fwd_ptr);
+  fwd_contrib_ptr.upload(l.fwd_contrib_ptr);
+  scontrib_idx.upload(l.scontrib_idx);
+  fwd_items.upload(l.fwd_items);
+  sext_ptr.upload(l.sext_ptr);
+  sext_dst.upload(l.sext_dst);
+  sext_items.upload(l.sext_items);
+  bwd_ptr.upload(l.bwd_ptr);
+  bwd_items.upload(l.bwd_items);
+  perm.upload(l.perm);
+  round_ptr.upload(l.round_ptr);
+  sn_desc.upload(l.sn_desc);
+  sn_lvl_ptr.upload(l.sn_lvl_ptr);
+  col_sn.upload(l.col_sn);
+  const LdltLevelTables lt = pack_ldlt_level_tables(l);
+  lvl_pack.upload(lt.lvl_pack);
+  col_lvl_pack.upload(lt.col_lvl_pack);
+  bwd_range.upload(lt.bwd_range);
+  n_rounds = l.n_rounds;
+}
+
+LdltDev LdltPlanDevice::view() const {
+  LdltDev L{};
+  L.tasks = tasks.p;
+  L.ent_src = ent_src.p;
+  L.ent_flags = ent_flags.p;
+  L.ent_col = ent_col.p;
+  L.ent_out = ent_out.p;
+  L.ent_pair_ptr = ent_pair_ptr.p;
+  L.ent_contrib_ptr = ent_contrib_ptr.p;
+  L.contrib_idx = contrib_idx.p;
+  L.ext_dst = ext_dst.p;
+  L.lvl_ptr = lvl_ptr.p;
+  L.pairs = pairs.p;
+  L.col_perm = col_perm.p;
+  L.col_lvl_ptr = col_lvl_ptr.p;
+  L.fwd_ptr = fwd_ptr.p;
+  L.fwd_contrib_ptr = fwd_contrib_ptr.p;
+  L.scontrib_idx = scontrib_idx.p;
+  L.fwd_items = fwd_items.p;
+  L.sext_ptr = sext_ptr.p;
+  L.sext_dst = sext_dst.p;
+  L.sext_items = sext_items.p;
+  L.bwd_ptr = bwd_ptr.p;
+  L.bwd_items = bwd_items.p;
+  L.perm = perm.p;
+  L.round_ptr = round_ptr.p;
+  L.n_rounds = n_rounds;
+  L.sn_desc = sn_desc.p;
+  L.sn_lvl_ptr = sn_lvl_ptr.p;
+  L.col_sn = col_sn.p;
+  L.lvl_pack = lvl_pack.p;
+  L.col_lvl_pack = col_lvl_pack.p;
+  L.bwd_range = bwd_range.p;
+  L.clock_task = 0xffffffffu;
+  return L;
+}
+
+// The phases below run in this order; every upload() of theirs goes into the system's arena — a few allocations, one
+// copy each (commit at the end) — so their order is also the order of the plan arrays in memory.
 DeviceNlp::DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l, int batch,
                      int device)
     : m_s_ref(s), m_k_ref(k), m_l_ref(l), m_batch(batch), m_device(device) {
@@ -516,141 +602,103 @@ DeviceNlp::DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l,
     throw std::runtime_error("slpx: no HIP device available (the product path has no CPU fallback)");
   SLPX_HIP_CHECK(hipSetDevice(device));
   SetupLap lap;
-  // every upload() of this constructor goes into the system's arena: a few allocations, one copy each (commit below)
   struct ArenaGuard {
     ~ArenaGuard() { DeviceArena::current() = nullptr; }
   } arena_guard;
   DeviceArena::current() = &m_arena;
 
-  // Chained steps (sweep_full_for_step): for one problem whose multifrontal step kernel leaves the sweep
-  // room on the chip (at most CUs - 64 workgroups: cart-pole N=5000's 265 do not, and there chaining costs
-  // 25 %, profiles/r03_chain_ab.txt).  SLPX_CHAIN_TAPE=0: off.
-  {
-    int cus = 0;
-    SLPX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m_device));
-    if (batch == 1 && l.mf && static_cast<int>(l.tasks.size() + s.reduces.size()) + 64 <= cus) m_chain_mode = 1;
-    if (const char* env = std::getenv("SLPX_CHAIN_TAPE"))
-      if (env[0] == '0') m_chain_mode = 0;
-  }
-  m_full.upload(s.full, batch, static_cast<uint32_t>(s.n), m_chain_mode);
-  m_values.upload(s.values, batch, static_cast<uint32_t>(s.n));
-  m_reduces.upload(s.reduces);
+  choose_chain_mode();
+  upload_tapes();
   lap("  upload: tapes (+ code objects)");
-  // allow > 64 KB dynamic LDS
+  raise_lds_limits();
+  upload_kkt_plan();
+  lap("  upload: kernel attributes, KKT plan");
+  upload_ldlt_plan();
+  lap("  upload: LDLT plan");
+  choose_launch_modes();
+  // (the host copies of the inline plans live until the task images are packed from them)
+  const InlineKkt inline_kkt = m_fuse_kkt ? build_inline_kkt(s, k, l) : InlineKkt{};
+  if (m_fuse_kkt) upload_inline_kkt(inline_kkt);
+  lap("    images: inline KKT terms");
+  const InlineBacksub inline_backsub = m_fuse_backsub ? build_inline_backsub(k, l) : InlineBacksub{};
+  if (m_fuse_backsub) upload_inline_backsub(inline_backsub);
+  lap("    images: back-substitution rows");
+  // (one problem's factorization and solve in one launch: the multifrontal step; the pair-list kernels — batches,
+  // plans without fronts — take a launch per round and phase.  SLPX_LDLT_MF=0: the pair lists)
+  const char* mf_env = std::getenv("SLPX_LDLT_MF");
+  if (m_fuse_launches && m_fuse_backsub && m_fuse_kkt && l.mf && !(mf_env && mf_env[0] == '0'))
+    upload_mf(build_mf_images(l, inline_kkt, inline_backsub));
+  lap("    images: multifrontal task images");
+  m_fuse_solve = m_mf;
+  m_chain_on = m_mf && m_chain_mode != 0;
+  lap("  upload: inline KKT / back-substitution / multifrontal images");
+  alloc_dense_buffers();  // (before the armed buffers, whose uploads follow its pattern arrays in the arena)
+  alloc_value_buffers();
+  arm_handover_buffers();
+  alloc_interleaved_buffers();
+  alloc_pinned();
+  DeviceArena::current() = nullptr;
+  m_arena.commit();
+  lap("  upload: value buffers");
+  set_scaling(std::vector<double>(s.n_scales(), 1.0));
+  lap("  upload: scaling, static V");
+}
+
+// Chained steps (sweep_full_for_step): for one problem whose multifrontal step kernel leaves the sweep
+// room on the chip (at most CUs - 64 workgroups: cart-pole N=5000's 265 do not, and there chaining costs
+// 25 %, profiles/r03_chain_ab.txt).  SLPX_CHAIN_TAPE=0: off.  (Before the tapes: their kernel is generated for it.)
+void DeviceNlp::choose_chain_mode() {
+  const NlpStructure& s = m_s_ref;
+  const LdltPlan& l = m_l_ref;
+  int cus = 0;
+  SLPX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m_device));
+  if (m_batch == 1 && l.mf && static_cast<int>(l.tasks.size() + s.reduces.size()) + 64 <= cus) m_chain_mode = 1;
+  if (const char* env = std::getenv("SLPX_CHAIN_TAPE"))
+    if (env[0] == '0') m_chain_mode = 0;
+}
+
+void DeviceNlp::upload_tapes() {
+  const NlpStructure& s = m_s_ref;
+  m_full.upload(s.full, m_batch, static_cast<uint32_t>(s.n), m_chain_mode);
+  m_values.upload(s.values, m_batch, static_cast<uint32_t>(s.n));
+  m_reduces.upload(s.reduces);
+}
+
+// allow > 64 KB dynamic LDS
+void DeviceNlp::raise_lds_limits() {
   for (const void* fn : {reinterpret_cast<const void*>(&tape_sweep_lds_kernel<256, true>),
                          reinterpret_cast<const void*>(&tape_sweep_lds_kernel<256, false>),
                          reinterpret_cast<const void*>(&tape_sweep_lds_kernel<64, true>),
-                         reinterpret_cast<const void*>(&tape_sweep_lds_kernel<64, false>)})
+                         reinterpret_cast<const void*>(&tape_sweep_lds_kernel<64, false>),
+                         reinterpret_cast<const void*>(&ldlt_factor_kernel<256>),
+                         reinterpret_cast<const void*>(&ldlt_factor_kernel<1024>),
+                         reinterpret_cast<const void*>(&ldlt_fwd_kernel),
+                         reinterpret_cast<const void*>(&ldlt_bwd_kernel)})
     SLPX_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_factor_kernel<256>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_factor_kernel<1024>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_fwd_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_bwd_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+}
 
-  m_dptr.upload(k.dptr);
-  m_dsrc.upload(k.dsrc);
-  m_pptr.upload(k.pptr);
-  m_pa.upload(k.pa);
-  m_pb.upload(k.pb);
-  m_pr.upload(k.pr);
-  m_gsrc.upload(k.g_src);
-  m_ae_colptr.upload(s.Ae.colptr);
-  m_ae_rowidx.upload(s.Ae.rowidx);
-  m_ai_colptr.upload(s.Ai.colptr);
-  m_ai_rowidx.upload(s.Ai.rowidx);
-  m_ai_rowptr.upload(k.ai_rowptr);
-  m_ai_col.upload(k.ai_col);
-  m_ai_src.upload(k.ai_src);
-  m_fast_src.upload(k.fast_src);
-  {
-    std::vector<int32_t> diag_pos(std::max(1, k.n), 0);
-    for (int c = 0; c < k.n; ++c)
-      for (int p = k.lhs.colptr[c]; p < k.lhs.colptr[c + 1]; ++p)
-        if (k.lhs.rowidx[p] == c) diag_pos[c] = p;
-    m_diag_pos.upload(diag_pos);
-  }
-  m_kdev = KktDev{k.n,           k.m_e,        k.m_i,        k.dim,         k.lhs.nnz(),  m_dptr.p,
-                  m_dsrc.p,      m_pptr.p,     m_pa.p,       m_pb.p,        m_pr.p,       m_gsrc.p,
-                  m_ae_colptr.p, m_ae_rowidx.p, m_ai_colptr.p, m_ai_rowidx.p, m_ai_rowptr.p,
-                  m_ai_col.p,    m_ai_src.p,   m_fast_src.p, s.off_f,      s.off_ce,     s.off_ci,     s.off_g,
-                  s.off_Ae,      s.off_Ai};
+void DeviceNlp::upload_kkt_plan() {
+  m_kplan.upload(m_s_ref, m_k_ref);
+  m_kdev = m_kplan.view();
+}
 
-  lap("  upload: kernel attributes, KKT plan");
-  m_ltasks.upload(l.tasks);
-  m_ent_src.upload(l.ent_src);
-  m_ent_flags.upload(l.ent_flags);
-  m_ent_col.upload(l.ent_col);
-  m_ent_out.upload(l.ent_out);
-  m_ent_pair_ptr.upload(l.ent_pair_ptr);
-  m_ent_contrib_ptr.upload(l.ent_contrib_ptr);
-  m_contrib_idx.upload(l.contrib_idx);
-  m_ext_dst.upload(l.ext_dst);
-  m_llvl_ptr.upload(l.lvl_ptr);
-  m_pairs.upload(l.pairs);
-  m_col_perm.upload(l.col_perm);
-  m_col_lvl_ptr.upload(l.col_lvl_ptr);
-  m_fwd_ptr.upload(l.fwd_ptr);
-  m_fwd_contrib_ptr.upload(l.fwd_contrib_ptr);
-  m_scontrib_idx.upload(l.scontrib_idx);
-  m_fwd_items.upload(l.fwd_items);
-  m_sext_ptr.upload(l.sext_ptr);
-  m_sext_dst.upload(l.sext_dst);
-  m_sext_items.upload(l.sext_items);
-  m_bwd_ptr.upload(l.bwd_ptr);
-  m_bwd_items.upload(l.bwd_items);
-  m_perm.upload(l.perm);
-  m_ldev = LdltDev{m_ltasks.p,       m_ent_src.p,  m_ent_flags.p,       m_ent_col.p,
-                   m_ent_out.p,      m_ent_pair_ptr.p, m_ent_contrib_ptr.p, m_contrib_idx.p,
-                   m_ext_dst.p,      m_llvl_ptr.p, m_pairs.p,           m_col_perm.p,
-                   m_col_lvl_ptr.p,  m_fwd_ptr.p,  m_fwd_contrib_ptr.p, m_scontrib_idx.p,
-                   m_fwd_items.p,    m_sext_ptr.p, m_sext_dst.p,        m_sext_items.p,
-                   m_bwd_ptr.p,      m_bwd_items.p, m_perm.p,            nullptr,
-                   l.n_rounds};
-  m_round_ptr.upload(l.round_ptr);
-  m_ldev.round_ptr = m_round_ptr.p;
-  m_ldev.clock_task = 0xffffffffu;
-  m_sn_desc.upload(l.sn_desc);
-  m_sn_lvl_ptr.upload(l.sn_lvl_ptr);
-  m_col_sn.upload(l.col_sn);
-  m_ldev.sn_desc = m_sn_desc.p;
-  m_ldev.sn_lvl_ptr = m_sn_lvl_ptr.p;
-  m_ldev.col_sn = m_col_sn.p;
-  {
-    std::vector<uint32_t> lp(l.lvl_ptr.size()), cp(l.col_lvl_ptr.size());
-    for (size_t i = 0; i < lp.size(); ++i) {
-      if (l.lvl_ptr[i] > 0xffffu || l.col_lvl_ptr[i] > 0xffffu || l.sn_lvl_ptr[i] > 0xffffu)
-        throw std::runtime_error("slpx: an LDLT task exceeds the 16-bit packing of its level table");
-      lp[i] = l.lvl_ptr[i] | (l.sn_lvl_ptr[i] << 16);
-      cp[i] = l.col_lvl_ptr[i] | (l.sn_lvl_ptr[i] << 16);
-    }
-    m_lvl_pack.upload(lp);
-    m_col_lvl_pack.upload(cp);
-    std::vector<uint2> rng(l.col_perm.size(), uint2{0, 0});
-    for (const LdltTask& t : l.tasks)
-      for (uint32_t i = 0; i < t.n_col; ++i) {
-        const uint32_t cs = l.col_sn[t.col_off + i];
-        rng[t.col_off + i] = uint2{l.bwd_ptr[t.colptr_off + i] + ((cs >> 8) - (cs & 0xffu) - 1u),
-                                   l.bwd_ptr[t.colptr_off + i + 1]};
-      }
-    m_bwd_range.upload(rng);
-  }
-  m_ldev.lvl_pack = m_lvl_pack.p;
-  m_ldev.col_lvl_pack = m_col_lvl_pack.p;
-  m_ldev.bwd_range = m_bwd_range.p;
-  {
-    std::vector<unsigned int> zero(2 * static_cast<size_t>(batch) * std::max(1, l.n_rounds), 0u);
-    m_fround_cnt.upload(zero);
-    m_bround_cnt.upload(zero);
-  }
+void DeviceNlp::upload_ldlt_plan() {
+  m_lplan.upload(m_l_ref);
+  m_ldev = m_lplan.view();
+  // the round counters of the single-launch kernels ([2][batch][n_rounds]), cleared once here
+  std::vector<unsigned int> zero(2 * static_cast<size_t>(m_batch) * std::max(1, m_l_ref.n_rounds), 0u);
+  m_fround_cnt.upload(zero);
+  m_bround_cnt.upload(zero);
+}
+
+// Which kernels serve this system: from the plans' shape and the batch, and the switches that overrule it.
+void DeviceNlp::choose_launch_modes() {
+  const LdltPlan& l = m_l_ref;
+  const int batch = m_batch;
   // Rounds in one launch pay off while every task of the launch is resident at once (a
   // single problem: 137 tasks on 256 CUs).  With a batch the later-round workgroups would
   // spin on CUs the earlier rounds of other problems are waiting for (measured at batch
   // 512: factorization 0.93 -> 4.2 ms), so batches keep one launch per round.
-  lap("  upload: LDLT plan");
   m_dense = l.dense;
   m_il = !m_dense && interleaved_for(batch);
   m_single_launch = !m_il && static_cast<size_t>(batch) * l.tasks.size() <= 1024;
@@ -662,19 +710,59 @@ DeviceNlp::DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l,
   if (const char* env = std::getenv("SLPX_FUSE_KKT")) m_fuse_kkt = m_fuse_kkt && env[0] != '0';
   if (const char* env = std::getenv("SLPX_FUSE_BACKSUB")) m_fuse_backsub = m_fuse_backsub && env[0] != '0';
   if (const char* env = std::getenv("SLPX_FUSE_KKT_STORE")) m_fuse_kkt_store = env[0] != '0';
-  if (m_fuse_kkt) build_inline_kkt(s, k, l);
-  lap("    images: inline KKT terms");
-  if (m_fuse_backsub) build_inline_backsub(k, l);
-  lap("    images: back-substitution rows");
-  // (one problem's factorization and solve in one launch: the multifrontal step; the pair-list kernels — batches,
-  // plans without fronts — take a launch per round and phase)
-  if (m_fuse_launches && m_fuse_backsub && m_fuse_kkt && l.mf) build_mf(l);
-  lap("    images: multifrontal task images");
-  m_fuse_solve = m_mf;
-  m_chain_on = m_mf && m_chain_mode != 0;
-  lap("  upload: inline KKT / back-substitution / multifrontal images");
+  // hand-overs through the data: the factorization's update slots (ldlt_kernels.h: slot_take) where each has exactly
+  // one reader, the backward solve's x (slot_read)
+  m_slot_handoff = m_single_launch && update_slots_have_one_reader(l);
+  m_xg_by_data = m_single_launch;
+}
 
-  const size_t B = static_cast<size_t>(batch);
+void DeviceNlp::upload_inline_kkt(const InlineKkt& ik) {
+  m_factor_lds_inline = ik.factor_lds;
+  if (!ik.ok) {
+    m_fuse_kkt = false;  // (the stand-alone assembly kernels then)
+    return;
+  }
+  m_ent_vsrc.upload(ik.vsrc);
+  m_kkt_terms.upload(ik.terms);
+  m_task_terms.upload(ik.task_terms);
+}
+
+void DeviceNlp::upload_inline_backsub(const InlineBacksub& ib) {
+  m_solve_lds_inline = ib.solve_lds;
+  if (!ib.ok) {
+    m_fuse_backsub = false;  // (the stand-alone back-substitution kernel then)
+    return;
+  }
+  m_bs_plan.upload(ib.plan);
+  m_bs_task_plan.upload(ib.task_plan);
+}
+
+// the dense branch: dim x dim per problem, the pattern of lhs for the scatter; LDS: column k and its scaled copy
+void DeviceNlp::alloc_dense_buffers() {
+  if (!m_dense) return;
+  const KktPlan& k = m_k_ref;
+  const LdltPlan& l = m_l_ref;
+  const size_t B = static_cast<size_t>(m_batch);
+  m_dense_A.alloc(B * static_cast<size_t>(l.n) * l.n);
+  m_dense_colptr.upload(k.lhs.colptr);
+  m_dense_rowidx.upload(k.lhs.rowidx);
+  m_dense_lds = 16u * static_cast<uint32_t>(l.n) + 320u;
+  m_dense_pivoted = l.dense_pivoted;
+  if (m_dense_pivoted) {
+    m_dense_trans.alloc(B * static_cast<size_t>(l.n));
+    m_dense_trans.zero();
+    SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_dense_pivoted_factor_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  }
+  if (m_dense_lds > 160u * 1024u) throw std::runtime_error("slpx: the dense factorization holds two columns in LDS: at most 10 000 rows");
+  SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_dense_factor_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_dense_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+}
+
+void DeviceNlp::alloc_value_buffers() {
+  const NlpStructure& s = m_s_ref;
+  const KktPlan& k = m_k_ref;
+  const LdltPlan& l = m_l_ref;
+  const size_t B = static_cast<size_t>(m_batch);
   m_in.alloc(B * s.n_inputs());
   m_in.zero();
   m_V.alloc(B * s.nV);
@@ -690,42 +778,11 @@ DeviceNlp::DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l,
   m_D.alloc(B * l.n);
   m_Lx.alloc(B * std::max<int64_t>(1, l.nnzL));
   m_contrib.alloc(B * std::max<uint32_t>(1, l.n_contrib));
-  {
-    // slot hand-over (ldlt_kernels.h: slot_take) needs every slot to have exactly one reader
-    std::vector<uint8_t> readers(std::max<uint32_t>(1, l.n_contrib), 0);
-    bool single_reader = true;
-    for (const LdltTask& t : l.tasks)  // (each task's slice is padded to a multiple of four)
-      for (uint32_t c = 0; c < t.n_contrib_idx; ++c)
-        single_reader = single_reader && ++readers[l.contrib_idx[t.contrib_off + c]] == 1;
-    m_slot_handoff = m_single_launch && single_reader;
-    if (m_slot_handoff) {
-      std::vector<double> empty(m_contrib.n);
-      const unsigned long long bits = kSlotEmpty;
-      double e;
-      std::memcpy(&e, &bits, sizeof(e));
-      std::fill(empty.begin(), empty.end(), e);
-      SLPX_HIP_CHECK(hipMemcpy(m_contrib.p, empty.data(), empty.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-  }
-  if (m_dense) {
-    // dim x dim per problem, the pattern of lhs for the scatter; LDS: column k and its scaled copy
-    m_dense_A.alloc(B * static_cast<size_t>(l.n) * l.n);
-    m_dense_colptr.upload(k.lhs.colptr);
-    m_dense_rowidx.upload(k.lhs.rowidx);
-    m_dense_lds = 16u * static_cast<uint32_t>(l.n) + 320u;
-    m_dense_pivoted = l.dense_pivoted;
-    if (m_dense_pivoted) {
-      m_dense_trans.alloc(B * static_cast<size_t>(l.n));
-      m_dense_trans.zero();
-      SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_dense_pivoted_factor_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    if (m_dense_lds > 160u * 1024u) throw std::runtime_error("slpx: the dense factorization holds two columns in LDS: at most 10 000 rows");
-    SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_dense_factor_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_dense_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  }
   m_scontrib.alloc(B * std::max<uint32_t>(1, l.n_scontrib));
   m_zv.alloc(B * l.n);
   m_xg.alloc(B * l.n);
+  const uint64_t scratch = std::max(s.full.global_scratch_doubles, s.values.global_scratch_doubles);
+  m_scratch.alloc(B * std::max<uint64_t>(1, scratch));
   // Every value buffer starts at zero, not at whatever the allocator hands back: the right-hand
   // side rides in the factorization as an extra row, and compute() may come before any rhs was
   // set (RegularizedLDLT::compute(lhs), regularized_ldlt.hpp:72) — recycled memory of an earlier
@@ -735,108 +792,69 @@ DeviceNlp::DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l,
   for (DevBuf<double>* buf : {&m_V, &m_s, &m_y, &m_z, &m_mu, &m_lhs, &m_rhs, &m_p, &m_ps, &m_pz, &m_D, &m_Lx, &m_scontrib, &m_zv})
     buf->zero();
   SLPX_HIP_CHECK(hipDeviceSynchronize());  // (the memsets ran on the null stream, the kernels will not)
+}
+
+// What the kernels hand over through the data starts out armed (kSlotEmpty), the counters cleared.
+void DeviceNlp::arm_handover_buffers() {
+  const LdltPlan& l = m_l_ref;
+  const size_t B = static_cast<size_t>(m_batch);
+  const double empty = std::bit_cast<double>(kSlotEmpty);
+  if (m_slot_handoff) {
+    const std::vector<double> armed(m_contrib.n, empty);
+    SLPX_HIP_CHECK(hipMemcpy(m_contrib.p, armed.data(), armed.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
   // the backward solve's hand-over through the data (ldlt_kernels.h: slot_read): two buffers of
   // x, both armed
-  m_xg_by_data = m_single_launch;
   if (m_xg_by_data) {
-    const std::vector<double> armed(static_cast<size_t>(B) * l.n, std::bit_cast<double>(kSlotEmpty));
+    const std::vector<double> armed(B * l.n, empty);
     m_xg.upload(armed);
     m_xg2.upload(armed);
   }
-  {
-    // two inertia-counter buffers (see factor()), both cleared once here
-    std::vector<LdltStats> zero(2 * static_cast<size_t>(B), LdltStats{0, 0, 0, 0, 0x7ff0000000000000ull});
-    m_stats.upload(zero);
-  }
+  // two inertia-counter buffers (see factor()), both cleared once here
+  m_stats.upload(std::vector<LdltStats>(2 * B, LdltStats{0, 0, 0, 0, 0x7ff0000000000000ull}));
+}
+
+// batch-interleaved LDLT (ldlt_il_kernels.h): [chunk of 64 problems][index][lane]
+void DeviceNlp::alloc_interleaved_buffers() {
+  if (!m_il) return;
+  const KktPlan& k = m_k_ref;
+  const LdltPlan& l = m_l_ref;
+  const size_t B = static_cast<size_t>(m_batch);
+  const size_t C = (B + 63) / 64, W = 64;
+  m_lhs_il.alloc(C * k.lhs.nnz() * W);
+  m_rhs_il.alloc(C * l.n * W);
+  m_Lx_il.alloc(C * std::max<int64_t>(1, l.nnzL) * W);
+  m_D_il.alloc(C * l.n * W);
+  m_contrib_il.alloc(C * std::max<uint32_t>(1, l.n_contrib) * W);
+  m_scontrib_il.alloc(C * std::max<uint32_t>(1, l.n_scontrib) * W);
+  m_zv_il.alloc(C * l.n * W);
+  m_xg_il.alloc(C * l.n * W);
+  m_stats_part.alloc(l.tasks.size() * B);
+  for (auto* buf : {&m_Lx_il, &m_D_il, &m_zv_il, &m_xg_il, &m_contrib_il, &m_scontrib_il}) buf->zero();
+  const IlMeta im = pack_il_meta(l);
+  m_il_meta.upload(im.meta);
+  m_il_meta_off.upload(im.meta_off);
+  m_il_factor_lds = im.factor_lds;
+  m_il_solve_lds = im.solve_lds;
+  if (m_il_factor_lds > 160u * 1024u)
+    throw std::runtime_error("slpx: an LDLT task does not fit the interleaved kernel's LDS (LdltOptions::task_entries)");
+  SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_factor_il_kernel),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  SLPX_HIP_CHECK(hipDeviceSynchronize());
+}
+
+// what the host and the kernels pass each other through pinned memory: (delta, gamma), the counters, the sequence word
+void DeviceNlp::alloc_pinned() {
+  const size_t B = static_cast<size_t>(m_batch);
   SLPX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&m_h_reg), 2 * static_cast<size_t>(std::max<int>(B, 6)) * sizeof(double)));  // (B = 1: a twin attempt's second pair)
   if (B > 8) m_reg_dev.alloc(2 * B);
-  if (m_il) {
-    // batch-interleaved LDLT (ldlt_il_kernels.h): [chunk of 64 problems][index][lane]
-    const size_t C = (B + 63) / 64, W = 64;
-    m_lhs_il.alloc(C * k.lhs.nnz() * W);
-    m_rhs_il.alloc(C * l.n * W);
-    m_Lx_il.alloc(C * std::max<int64_t>(1, l.nnzL) * W);
-    m_D_il.alloc(C * l.n * W);
-    m_contrib_il.alloc(C * std::max<uint32_t>(1, l.n_contrib) * W);
-    m_scontrib_il.alloc(C * std::max<uint32_t>(1, l.n_scontrib) * W);
-    m_zv_il.alloc(C * l.n * W);
-    m_xg_il.alloc(C * l.n * W);
-    m_stats_part.alloc(l.tasks.size() * B);
-    for (auto* buf : {&m_Lx_il, &m_D_il, &m_zv_il, &m_xg_il, &m_contrib_il, &m_scontrib_il}) buf->zero();
-    // per task: the plan slices the factor kernel keeps in LDS, packed back to back
-    // [n_cref, n_words | pairs (2 words each) | pair ptr | src | out |
-    //  flags + column | ext dst | level ptr | per-slot update-block refs]
-    uint32_t fbytes = 0, col = 0, solve_bytes = 0;
-    std::vector<uint32_t> meta, meta_off;
-    for (const LdltTask& t : l.tasks) {
-      const uint32_t n_cref = l.ent_contrib_ptr[t.contrib_ptr_off + t.n_ent];
-      meta_off.push_back(static_cast<uint32_t>(meta.size()));
-      const size_t head = meta.size();
-      meta.push_back(n_cref);
-      meta.push_back(0);
-      for (uint32_t q = 0; q < t.n_pairs; ++q) {
-        const LdltPair& pr = l.pairs[t.pair_off + q];
-        meta.push_back(static_cast<uint32_t>(pr.a) | (static_cast<uint32_t>(pr.b) << 16));
-        meta.push_back(pr.k);
-      }
-      for (uint32_t i = 0; i < t.n_ent + t.n_ext + 1; ++i) meta.push_back(l.ent_pair_ptr[t.pair_ptr_off + i]);
-      for (uint32_t i = 0; i < t.n_ent; ++i) meta.push_back(static_cast<uint32_t>(l.ent_src[t.ent_off + i]));
-      for (uint32_t i = 0; i < t.n_ent; ++i) meta.push_back(l.ent_out[t.ent_off + i]);
-      for (uint32_t i = 0; i < t.n_ent; ++i)
-        meta.push_back(static_cast<uint32_t>(l.ent_flags[t.ent_off + i]) | (static_cast<uint32_t>(l.ent_col[t.ent_off + i]) << 8));
-      for (uint32_t i = 0; i < t.n_ext; ++i) meta.push_back(l.ext_dst[t.ext_off + i]);
-      for (uint32_t i = 0; i < t.n_lvl + 1; ++i) meta.push_back(l.lvl_ptr[t.lvl_off + i]);
-      // update-block refs, flat per entry slot (entry e belongs to slot e % kIlSlots), entry order and
-      // block order within an entry as in the plan
-      {
-        const size_t ptr_at = meta.size();
-        meta.insert(meta.end(), kIlSlots + 1, 0u);  // filled below: first ref of each slot, total
-        uint32_t n_refs = 0;
-        for (uint32_t sidx = 0; sidx < kIlSlots; ++sidx) {
-          meta[ptr_at + sidx] = n_refs;
-          for (uint32_t e = sidx; e < t.n_ent; e += kIlSlots)
-            for (uint32_t cix = l.ent_contrib_ptr[t.contrib_ptr_off + e]; cix < l.ent_contrib_ptr[t.contrib_ptr_off + e + 1]; ++cix) {
-              meta.push_back(e);
-              meta.push_back(l.contrib_idx[t.contrib_off + cix]);
-              ++n_refs;
-            }
-        }
-        meta[ptr_at + kIlSlots] = n_refs;
-      }
-      const uint32_t n_words = static_cast<uint32_t>(meta.size() - head - 2);
-      meta[head + 1] = n_words;
-      fbytes = std::max(fbytes, std::max<uint32_t>((t.n_ent + t.n_col) * kIlW * 8u, 3u * kIlSlots * kIlW * 8u) + 4u * n_words + 16u);
-      col = std::max(col, t.n_col + 1);
-      solve_bytes = std::max(solve_bytes, t.n_col * 64u * 8u + 4u * (3u * t.n_col + t.n_lvl + 4u) + 8u * t.n_bwd_items + 16u);
-    }
-    if (meta.empty()) meta.push_back(0);
-    if (meta_off.empty()) meta_off.push_back(0);
-    m_il_meta.upload(meta);
-    m_il_meta_off.upload(meta_off);
-    m_il_factor_lds = fbytes;
-    m_il_solve_lds = std::max(col * 64u * 8u, solve_bytes);  // fwd: y rows; bwd: x rows + its plan slices
-    if (m_il_factor_lds > 160u * 1024u)
-      throw std::runtime_error("slpx: an LDLT task does not fit the interleaved kernel's LDS (LdltOptions::task_entries)");
-    SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_factor_il_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    SLPX_HIP_CHECK(hipDeviceSynchronize());
-  }
   SLPX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&m_h_stats), static_cast<size_t>(std::max<int>(B, 2)) * sizeof(LdltStats)));
-  {
-    unsigned long long* seq = nullptr;
-    SLPX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&seq), sizeof(unsigned long long)));
-    *seq = 0;
-    m_h_seq = seq;
-    m_seq_dev.alloc(1);
-    m_seq_dev.zero();
-  }
-  const uint64_t scratch = std::max(s.full.global_scratch_doubles, s.values.global_scratch_doubles);
-  m_scratch.alloc(B * std::max<uint64_t>(1, scratch));
-  DeviceArena::current() = nullptr;
-  m_arena.commit();
-  lap("  upload: value buffers");
-  set_scaling(std::vector<double>(s.n_scales(), 1.0));
-  lap("  upload: scaling, static V");
+  unsigned long long* seq = nullptr;
+  SLPX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&seq), sizeof(unsigned long long)));
+  *seq = 0;
+  m_h_seq = seq;
+  m_seq_dev.alloc(1);
+  m_seq_dev.zero();
 }
 
 DeviceNlp::~DeviceNlp() {
@@ -1108,247 +1126,13 @@ static inline int grid_for(int work, int block, int cap = 2048) {
   return std::max(1, std::min((work + block - 1) / block, cap));
 }
 
-// The static side of KktFuse: for every entry of the factorization plan what it is made of.
-void DeviceNlp::build_inline_kkt(const NlpStructure& s, const KktPlan& k, const LdltPlan& l) {
-  std::vector<int32_t> vsrc(l.ent_src.size(), -1);
-  std::vector<KktTerm> terms;
-  std::vector<uint2> task_terms(l.tasks.size(), uint2{0, 0});
-  auto term = [](int kind, int a, int row, int c) { return KktTerm{a, (kind << 28) | row, c}; };
-  bool ok = s.nV < (1 << 30) && k.m_i < (1 << 28) && k.m_e < (1 << 28);
-  uint32_t widest = 0;
-  for (size_t ti = 0; ti < l.tasks.size() && ok; ++ti) {
-    const LdltTask& t = l.tasks[ti];
-    const size_t block = terms.size();
-    for (uint32_t i = 0; i < t.n_ent; ++i) {
-      const size_t e = t.ent_off + i;
-      const int32_t s0 = l.ent_src[e];
-      if (s0 < 0) continue;
-      const size_t first = terms.size();
-      if (l.ent_flags[e] & 4) {  // rhs entry s0 (kkt_kernels.h: kkt_rhs_entry)
-        const int j = s0;
-        if (j >= k.n) {
-          vsrc[e] = (s.off_ce + j - k.n) | (1 << 30);
-          continue;
-        }
-        if (k.g_src[j] >= 0) terms.push_back(term(1, k.g_src[j], 0, 0));
-        for (int p = s.Ae.colptr[j]; p < s.Ae.colptr[j + 1]; ++p)
-          terms.push_back(term(2, s.off_Ae + p, s.Ae.rowidx[p], 0));
-        for (int p = s.Ai.colptr[j]; p < s.Ai.colptr[j + 1]; ++p)
-          terms.push_back(term(3, s.off_Ai + p, s.Ai.rowidx[p], s.off_ci + s.Ai.rowidx[p]));
-      } else {  // lhs entry s0 (kkt_kernels.h: kkt_assemble_body)
-        const int f = k.fast_src[s0];
-        if (f >= 0) {
-          vsrc[e] = f;
-          continue;
-        }
-        if (f != -2) continue;
-        for (int q = k.dptr[s0]; q < k.dptr[s0 + 1]; ++q) terms.push_back(term(0, k.dsrc[q], 0, 0));
-        for (int q = k.pptr[s0]; q < k.pptr[s0 + 1]; ++q) terms.push_back(term(4, k.pa[q], k.pr[q], k.pb[q]));
-      }
-      const size_t rel = first - block, cnt = terms.size() - first;
-      if (rel >= (1u << 20) || cnt >= (1u << 11)) {
-        ok = false;
-        break;
-      }
-      // (a sum of nothing — an x row with no gradient, no A_e, no A_i entry — is a zero)
-      vsrc[e] = cnt == 0 ? -1 : -static_cast<int32_t>(2 + (rel | (cnt << 20)));
-    }
-    while ((terms.size() - block) % 4 != 0) terms.push_back(KktTerm{0, 0, 0});  // 4 terms = 3 x 16 bytes
-    const uint32_t off16 = static_cast<uint32_t>(block * sizeof(KktTerm) / 16);
-    const uint32_t len16 = static_cast<uint32_t>((terms.size() - block) * sizeof(KktTerm) / 16);
-    task_terms[ti] = uint2{off16, len16};
-    widest = std::max(widest, len16);
-  }
-  // the staged terms and, behind them, one product per term (4 terms = 3 x 16 bytes)
-  m_factor_lds_inline = l.factor_lds_bytes + 16u + 16u * widest + 8u * (widest * 4u / 3u);
-  if (!ok || m_factor_lds_inline > 160u * 1024u) {
-    m_fuse_kkt = false;  // (the stand-alone assembly kernels then)
-    return;
-  }
-  if (terms.empty()) terms.push_back(KktTerm{0, 0, 0});
-  m_ent_vsrc.upload(vsrc);
-  m_kkt_terms.upload(terms);
-  m_task_terms.upload(task_terms);
-  m_h_vsrc = std::move(vsrc);
-  m_h_terms = std::move(terms);
-  m_h_task_terms = std::move(task_terms);
-}
-
-// The static side of BacksubFuse: every row of A_i goes to the task that owns the deepest of
-// its columns.
-void DeviceNlp::build_inline_backsub(const KktPlan& k, const LdltPlan& l) {
-  static_assert(sizeof(BsRow) == 8 && sizeof(BsTerm) == 8, "rows and terms are staged as 16-byte pairs");
-  const int dim = l.n;
-  std::vector<int32_t> inv_perm(dim, -1), task_of(dim, -1), local_of(dim, -1);
-  for (int pj = 0; pj < dim; ++pj) inv_perm[l.perm[pj]] = pj;
-  for (size_t ti = 0; ti < l.tasks.size(); ++ti)
-    for (uint32_t i = 0; i < l.tasks[ti].n_col; ++i) {
-      const uint32_t pj = l.col_perm[l.tasks[ti].col_off + i];
-      task_of[pj] = static_cast<int32_t>(ti);
-      local_of[pj] = static_cast<int32_t>(i);
-    }
-  std::vector<std::vector<int>> rows_of(l.tasks.size());
-  bool ok = true;
-  for (int r = 0; r < k.m_i && ok; ++r) {
-    int deepest = -1;
-    for (int q = k.ai_rowptr[r]; q < k.ai_rowptr[r + 1]; ++q) {
-      const int pj = inv_perm[k.ai_col[q]];
-      if (deepest < 0 || pj < deepest) deepest = pj;
-    }
-    if (deepest < 0) deepest = 0;  // an empty row: anybody
-    const int owner = task_of[deepest];
-    // what the scheme rests on: every other column is the owner's or an ancestor's (a later round's)
-    for (int q = k.ai_rowptr[r]; q < k.ai_rowptr[r + 1]; ++q) {
-      const int other = task_of[inv_perm[k.ai_col[q]]];
-      if (other != owner && l.tasks[other].round <= l.tasks[owner].round) ok = false;
-    }
-    rows_of[owner].push_back(r);
-  }
-  std::vector<BsRow> plan;  // BsRow and BsTerm are both two 32-bit words: one array
-  std::vector<uint4> task_plan(l.tasks.size(), uint4{0, 0, 0, 0});
-  uint32_t widest = 0;
-  for (size_t ti = 0; ti < l.tasks.size() && ok; ++ti) {
-    const size_t block = plan.size();
-    const std::vector<int>& rows = rows_of[ti];
-    const size_t n_rows = rows.size(), rows_padded = (n_rows + 1) / 2 * 2;
-    plan.resize(block + rows_padded, BsRow{0, 0});
-    uint32_t term = 0;
-    for (size_t j = 0; j < n_rows; ++j) {
-      const int r = rows[j];
-      const uint32_t cnt = static_cast<uint32_t>(k.ai_rowptr[r + 1] - k.ai_rowptr[r]);
-      if (term >= (1u << 20) || cnt >= (1u << 12)) ok = false;
-      plan[block + j] = BsRow{r, term | (cnt << 20)};
-      for (int q = k.ai_rowptr[r]; q < k.ai_rowptr[r + 1]; ++q) {
-        const int pj = inv_perm[k.ai_col[q]];
-        const uint32_t ref = task_of[pj] == static_cast<int32_t>(ti) ? static_cast<uint32_t>(local_of[pj])
-                                                                     : (0x80000000u | static_cast<uint32_t>(pj));
-        plan.push_back(BsRow{k.ai_src[q], ref});  // (a BsTerm)
-        ++term;
-      }
-    }
-    if ((plan.size() - block) % 2 != 0) plan.push_back(BsRow{0, 0});
-    const uint32_t len16 = static_cast<uint32_t>((plan.size() - block) / 2);
-    task_plan[ti] = uint4{static_cast<uint32_t>(block / 2), len16, static_cast<uint32_t>(n_rows),
-                          static_cast<uint32_t>(rows_padded / 2)};
-    widest = std::max(widest, len16);
-  }
-  m_solve_lds_inline = l.solve_lds_bytes + 16u + 16u * widest;
-  if (!ok || m_solve_lds_inline > 160u * 1024u) {
-    m_fuse_backsub = false;  // (the stand-alone back-substitution kernel then)
-    return;
-  }
-  if (plan.empty()) plan.push_back(BsRow{0, 0});
-  m_bs_plan.upload(plan);
-  m_bs_task_plan.upload(task_plan);
-  m_h_bs_plan = std::move(plan);
-  m_h_bs_task_plan = std::move(task_plan);
-}
-
 constexpr int kFactorThreadsSingle = 1024;
-// The multifrontal step (ldlt_mf_kernels.h): plan upload, LDS footprint, co-residency of every task's workgroup.
-void DeviceNlp::build_mf(const LdltPlan& l) {
-  if (const char* env = std::getenv("SLPX_LDLT_MF"))
-    if (env[0] == '0') return;
-  if (m_h_task_terms.size() != l.tasks.size() || m_h_bs_task_plan.size() != l.tasks.size()) return;
-  // Every task's static LDS content as ONE image in LDS order (mf_carve: from the tables to the KKT
-  // terms, then — behind the terms' products, which are not staged — its back-substitution rows):
-  // thirteen arrays staged one after the other were thirteen dependent waits on memory (4.5 us);
-  // one copy loop with every load in flight is a single trip.
-  uint32_t lds = 0;
-  std::vector<uint4> image, desc(l.tasks.size());
-  // sizes first (the slots are of one size: the largest image), then every task's image written straight into its
-  // slot, the tasks in chunks on the setup threads
-  std::vector<uint32_t> blob_bytes(l.tasks.size());
-  size_t stride16 = 1;
-  for (size_t ti = 0; ti < l.tasks.size(); ++ti) {
-    const MfCarve cv = mf_carve(l.tasks[ti], l.mf_tasks[ti]);
-    const uint32_t terms16 = m_h_task_terms[ti].y, bs16 = m_h_bs_task_plan[ti].y;
-    const uint32_t n_terms = terms16 * 4u / 3u;
-    const uint32_t end_terms = cv.o_terms + 16u * terms16;
-    lds = std::max(lds, mf_align16(end_terms + 8u * n_terms) + 16u * bs16);
-    blob_bytes[ti] = end_terms - cv.o_tab + 16u * bs16;
-    stride16 = std::max<size_t>(stride16, blob_bytes[ti] / 16u);
-    desc[ti] = uint4{0u, (end_terms - cv.o_tab) / 16u, bs16, terms16};
-  }
-  if (stride16 > kMfImageGroups) return;  // (a task image beyond what the staging loop requests)
-  // fixed-size slots (the kernel requests a task's image before it knows its length) + one round of padding
-  image.assign(stride16 * l.tasks.size() + kMfImageGroups, uint4{0, 0, 0, 0});
-  std::atomic<bool> out_of_bounds{false}, terms_do_not_fit{false};
-  parallel_chunks(l.tasks.size(), 8, [&](size_t t_begin, size_t t_end, unsigned) {
-    std::vector<uint8_t> fl;
-    std::vector<int32_t> vs;
-    for (size_t ti = t_begin; ti < t_end; ++ti) {
-      const LdltTask& t = l.tasks[ti];
-      const LdltMfTask& m = l.mf_tasks[ti];
-      const MfCarve cv = mf_carve(t, m);
-      const uint32_t terms16 = m_h_task_terms[ti].y, bs16 = m_h_bs_task_plan[ti].y;
-      const uint32_t end_terms = cv.o_terms + 16u * terms16;
-      unsigned char* blob = reinterpret_cast<unsigned char*>(image.data() + ti * stride16);
-      const size_t blob_size = blob_bytes[ti];
-      auto put = [&](uint32_t at, const void* src, size_t bytes) {
-        if (at < cv.o_tab || at - cv.o_tab + bytes > blob_size) {
-          out_of_bounds = true;
-          return;
-        }
-        if (bytes) std::memcpy(blob + (at - cv.o_tab), src, bytes);
-      };
-      put(cv.o_tab, l.mf_tab.data() + m.tab_off, 2u * m.n_tab);
-      put(cv.o_lvl, l.mf_lvl_ptr.data() + t.lvl_off, 4u * (t.n_lvl + 1));
-      put(cv.o_ext, l.mf_ext.data() + m.ext_off, 4u * m.n_ext);
-      {
-        // where an entry's value comes from; an entry that is a sum of terms says how many of each kind
-        // (kkt_terms_sum_grouped: the terms lie kind by kind)
-        vs.assign(m_h_vsrc.begin() + t.ent_off, m_h_vsrc.begin() + t.ent_off + t.n_ent);
-        const KktTerm* tt = m_h_terms.data() + static_cast<size_t>(m_h_task_terms[ti].x) * 4u / 3u;
-        for (uint32_t i = 0; i < t.n_ent; ++i) {
-          if (vs[i] >= -1) continue;
-          const uint32_t code = static_cast<uint32_t>(-(vs[i] + 2));
-          const uint32_t first = code & 0xfffffu, cnt = code >> 20;
-          uint32_t has_g = 0, n_a = 0, n_b = 0;
-          bool sorted = true;
-          int last = -1;
-          for (uint32_t q = first; q < first + cnt; ++q) {
-            const int kind = tt[q].b >> 28;
-            sorted = sorted && kind >= last;
-            last = kind;
-            if (kind == 1) ++has_g;
-            else if (kind == 0 || kind == 2) ++n_a;
-            else ++n_b;
-          }
-          if (!sorted || has_g > 1 || !mf_term_code_fits(first, n_a, n_b)) {
-            terms_do_not_fit = true;
-            break;
-          }
-          vs[i] = -static_cast<int32_t>(2u + mf_term_code(first, has_g, n_a, n_b));
-        }
-        put(cv.o_src, vs.data(), 4u * t.n_ent);
-      }
-      {
-        // (bit 5: the entry takes update slots)
-        fl.assign(l.ent_flags.begin() + t.ent_off, l.ent_flags.begin() + t.ent_off + t.n_ent);
-        for (uint32_t j = 0; j < m.n_cent; ++j) fl[l.mf_cent[m.cent_off + j]] |= 0x20;
-        put(cv.o_flags, fl.data(), t.n_ent);
-      }
-      put(cv.o_cent, l.mf_cent.data() + m.cent_off, 2u * m.n_cent);
-      put(cv.o_cptr, l.mf_contrib_ptr.data() + m.contrib_ptr_off, 4u * (m.n_cent + 1));
-      put(cv.o_cidx, l.mf_contrib_idx.data() + m.contrib_off, 4u * m.n_contrib_idx);
-      put(cv.o_cp, l.col_perm.data() + t.col_off, 4u * t.n_col);
-      put(cv.o_anc, l.mf_anc.data() + m.anc_off, 4u * m.n_anc);
-      put(cv.o_fr, l.mf_fronts.data() + m.front_off, sizeof(LdltFront) * m.n_front);
-      {
-        // the inertia counters start at zero, the smallest |d| at +inf
-        const unsigned long long inf = 0x7ff0000000000000ull;
-        put(cv.o_cnt + 16u, &inf, 8);
-      }
-      put(cv.o_terms, reinterpret_cast<const unsigned char*>(m_h_terms.data()) + 16u * static_cast<size_t>(m_h_task_terms[ti].x),
-          16u * terms16);
-      put(end_terms, reinterpret_cast<const unsigned char*>(m_h_bs_plan.data()) + 16u * static_cast<size_t>(m_h_bs_task_plan[ti].x),
-          16u * bs16);
-    }
-  });
-  if (out_of_bounds) throw std::runtime_error("slpx: task image layout out of bounds");
-  if (terms_do_not_fit) return;  // (an entry of hundreds of terms: the pair-list kernels' encoding holds 2047)
-  lds = mf_align16(lds) + 16u;
+// The multifrontal step (ldlt_mf_kernels.h) with the task images of build_mf_images: co-residency of every task's
+// workgroup, then the uploads.
+void DeviceNlp::upload_mf(const MfImages& im) {
+  if (im.declined != nullptr) return;
+  const LdltPlan& l = m_l_ref;
+  const uint32_t lds = im.lds;
   int per_cu = 0, cus = 0;
   hipFuncAttributes attr{};
   bool fits = false;
@@ -1374,13 +1158,13 @@ void DeviceNlp::build_mf(const LdltPlan& l) {
   }
   if (std::getenv("SLPX_LDLT_VERBOSE"))
     std::fprintf(stderr, "ldlt multifrontal step: %zu tasks, LDS %u bytes (static %zu), images %zu bytes, %d workgroup(s) of %d threads per CU x %d CUs%s\n",
-                 l.tasks.size(), lds, attr.sharedSizeBytes, 16 * image.size(), per_cu, m_mf_threads, cus, fits ? "" : ": NOT resident at once");
+                 l.tasks.size(), lds, attr.sharedSizeBytes, 16 * im.image.size(), per_cu, m_mf_threads, cus, fits ? "" : ": NOT resident at once");
   if (!fits) return;
   m_mf_tasks.upload(l.mf_tasks);
   m_mf_fronts.upload(l.mf_fronts);
-  m_mf_image.upload(image);
-  m_mf_image_stride16 = static_cast<uint32_t>(stride16);
-  m_mf_image_desc.upload(desc);
+  m_mf_image.upload(im.image);
+  m_mf_image_stride16 = im.stride16;
+  m_mf_image_desc.upload(im.desc);
   m_mf_contrib.upload(std::vector<double>(std::max<uint32_t>(1, l.mf_n_contrib), std::bit_cast<double>(kSlotEmpty)));
   if (m_exit_cnt.n == 0) m_exit_cnt.upload(std::vector<unsigned int>(1, 0u));
   m_mf_lds = lds;
@@ -1502,7 +1286,7 @@ void DeviceNlp::assemble_lsq() {
   hipLaunchKernelGGL(kkt_assemble_lsq_kernel, dim3(grid_for(m_kdev.nnz_lhs, 256), m_batch), dim3(256),
                      0, m_stream, m_kdev, m_V.p, m_s_ref.nV, m_s.p, m_lhs.p);
   hipLaunchKernelGGL(kkt_add_identity_kernel, dim3(grid_for(m_kdev.n, 256), m_batch), dim3(256), 0,
-                     m_stream, m_kdev, m_diag_pos.p, m_lhs.p);
+                     m_stream, m_kdev, m_kplan.diag_pos.p, m_lhs.p);
   SLPX_HIP_CHECK(hipGetLastError());
 }
 

@@ -8,6 +8,7 @@
 
 #include "coherent.h"
 #include "device.hpp"
+#include "device_layout.h"
 
 namespace slpx {
 
@@ -146,8 +147,8 @@ __device__ __forceinline__ double kkt_rhs_entry(const KktDev& K, const double* _
   return -g + aey + ait;
 }
 
-// Entries given as lists of terms in LDS (device.hpp: KktTerm; built by
-// DeviceNlp::build_inline_kkt from the same maps the functions above walk), evaluated by a whole
+// Entries given as lists of terms in LDS (device_layout.h: KktTerm; built by
+// build_inline_kkt of device_images.cpp from the same maps the functions above walk), evaluated by a whole
 // workgroup: ONE TERM PER LANE — a lone lane issues an instruction every 5-9 clocks, so walking a
 // ten-term row alone costs more than the trip to memory — then every sum adds up its own terms
 // from LDS in their order (kkt_terms_sum; same accumulators and order of summation as
@@ -190,22 +191,14 @@ __device__ __forceinline__ double kkt_terms_sum(const KktTerm* __restrict__ term
 }
 
 // The same sum for the step kernel of the fronts, whose image says how many terms of each kind an entry has
-// (kMfTerm*: DeviceNlp::build_mf re-encodes the entry's word; the terms of an entry are laid down kind by kind —
-// [g] [A_e^T y ...] [A_i^T ...] for a right-hand-side row, [direct ...] [products ...] for an entry of the matrix,
-// DeviceNlp::build_inline_kkt), so the kinds need not be read back and nothing branches on them: one trip to LDS
+// (kMfTerm*, mf_term_code of device_layout.h: build_mf_images re-encodes the entry's word; the terms of an entry are
+// laid down kind by kind — [g] [A_e^T y ...] [A_i^T ...] for a right-hand-side row, [direct ...] [products ...] for an
+// entry of the matrix, build_inline_kkt of device_images.cpp), so the kinds need not be read back and nothing branches on them: one trip to LDS
 // per four terms of both groups, one select and one add per term.  The loop above compiles to a chain of divergent
 // branches, ~100 instructions per term, and a lane's entry has up to a dozen terms (a right-hand-side row sums a
 // column of A_e^T y): 2 us of the step's critical path at cart-pole N=1000 by the kernel's own clocks.  Same
 // accumulators, same order, same bits: acc + 0.0 is acc for every acc but -0.0, which a sum that starts at +0.0
 // never is.
-constexpr uint32_t kMfTermFirstBits = 14, kMfTermABits = 8, kMfTermBBits = 7;  // + 1 bit: the row has a gradient term
-__host__ __device__ inline bool mf_term_code_fits(uint32_t first, uint32_t n_a, uint32_t n_b) {
-  return first < (1u << kMfTermFirstBits) && n_a < (1u << kMfTermABits) && n_b < (1u << kMfTermBBits);
-}
-__host__ __device__ inline uint32_t mf_term_code(uint32_t first, uint32_t has_g, uint32_t n_a, uint32_t n_b) {
-  return first | (n_a << kMfTermFirstBits) | (n_b << (kMfTermFirstBits + kMfTermABits)) |
-         (has_g << (kMfTermFirstBits + kMfTermABits + kMfTermBBits));
-}
 __device__ __forceinline__ double kkt_terms_sum_grouped(const double* __restrict__ prod, uint32_t code, bool is_rhs) {
   const uint32_t first = code & ((1u << kMfTermFirstBits) - 1u);
   const uint32_t n_a = (code >> kMfTermFirstBits) & ((1u << kMfTermABits) - 1u);

@@ -30,6 +30,7 @@
 
 #include "coherent.h"
 #include "device.hpp"
+#include "device_layout.h"
 #include "ldlt_kernels.h"  // round_wait, round_signal
 
 namespace slpx {
@@ -41,14 +42,13 @@ namespace slpx {
   g_ldlt_clocks[8 + (k)] = wall_clock64()
 
 constexpr int kIlLanes = 64;  // lanes of a wave
-constexpr int kIlWShift = 4;  // (measured: 8-wide rows 0.74 ms per factorization of 512 x N=1000, 16-wide 0.67)
-constexpr int kIlW = 1 << kIlWShift;  // problems per interleaved row
-constexpr int kIlRowsPerChunk = 64 / kIlW;  // rows groups covering a 64-problem chunk
+// The shape constants are in device_layout.h (pack_il_meta of device_images.cpp lays the refs out by them):
+//   kIlWShift = 4, kIlW = 16 problems per interleaved row (measured: 8-wide rows 0.74 ms per factorization of
+//   512 x N=1000, 16-wide 0.67), kIlRowsPerChunk row groups covering a 64-problem chunk;
+//   kIlFactorThreads = 512, kIlSlots = 32 entries of a level a factorization workgroup works on at a time:
 // a level has ~65-120 entries: with 32 of them in flight a task's level loop takes half the passes
 // of 16, and the same LDS per workgroup holds twice the waves to hide its latency (measured, ms per
 // factorization of 512 x N=1000: 256 threads 0.629, 512 threads 0.589, 1024 threads 0.809)
-constexpr int kIlFactorThreads = 512;
-constexpr int kIlSlots = kIlFactorThreads / kIlW;  // entries of a level a factorization workgroup works on at a time
 
 // number of 16-problem rows groups a batch occupies (padded to whole waves of 64 problems)
 __host__ __device__ inline int il_groups(int batch) { return kIlRowsPerChunk * ((batch + 63) / 64); }

@@ -21,6 +21,7 @@
 
 #include "coherent.h"
 #include "device.hpp"
+#include "device_layout.h"
 #include "kkt_kernels.h"
 #include "tape_kernels.h"  // stage16, q16
 
@@ -89,7 +90,7 @@ __device__ __forceinline__ void round_signal(unsigned int* cnt_base, int round, 
 // barrier and an atomic increment, and the consumer's separate trip for the data after the
 // counter moved.  A computed NaN never carries this payload (the hardware produces the
 // canonical quiet NaN), so a numerical breakdown cannot be mistaken for "not yet written".
-constexpr unsigned long long kSlotEmpty = 0x7ff8dead0badbeefull;
+// (kSlotEmpty, the pattern: device_layout.h — the host arms the slots with it)
 __device__ __forceinline__ bool slot_is_empty(double v) {
   return static_cast<unsigned long long>(__double_as_longlong(v)) == kSlotEmpty;
 }

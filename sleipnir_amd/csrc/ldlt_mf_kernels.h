@@ -31,6 +31,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "device_layout.h"
 #include "ldlt_kernels.h"
 #include "ipm_kernels.h"
 
@@ -43,7 +44,7 @@ using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 struct MfDev {
   const LdltMfTask* tasks = nullptr;
   const LdltFront* fronts = nullptr;
-  const uint4* image = nullptr;       // per task: its static LDS content in LDS order (DeviceNlp::build_mf), one fixed-size slot each
+  const uint4* image = nullptr;       // per task: its static LDS content in LDS order (build_mf_images of device_images.cpp), one fixed-size slot each
   uint32_t image_stride16 = 0;        // slot size in 16-byte groups
   const uint4* image_desc = nullptr;  // per task {first group, groups up to the end of the KKT terms, groups of back-substitution rows, terms groups}
   unsigned int n_tasks = 0;
@@ -150,17 +151,15 @@ constexpr int kMfNchAny = 3;
 // written out when the task is through.  A clock stored to memory where it is taken is waited for at the next barrier
 // (a workgroup barrier waits for the wave's outstanding stores): ~1 us of instrument per clock point, in a kernel
 // whose phases are one to five microseconds.  The ordinary build carries no clock code in this kernel.
+// (kMfClockBytes, their room in a task's LDS: device_layout.h)
 #ifdef SLPX_MF_CLOCKS
-constexpr uint32_t kMfClockBytes = 192;  // the 24 slots of g_ldlt_clocks
 constexpr uint32_t kMfClockTasks = 1024;
 __device__ unsigned long long g_mf_clocks[kMfClockTasks * 24];  // EVERY task's slots of the last launch (one timeline)
 #define SLPX_MF_CLOCK(k) \
   if (threadIdx.x == 0) s_clk[k] = wall_clock64()
 #else
-constexpr uint32_t kMfClockBytes = 0;
 #define SLPX_MF_CLOCK(k)
 #endif
-constexpr uint32_t kMfImageGroups = 6144;  // 16-byte groups of a task's image the staging loop requests: 96 KB
 
 // ---------------------------------------------------------------------------
 // The update block on the MATRIX CORES (fronts flagged by the plan: at least four pivot columns under
@@ -488,32 +487,8 @@ __device__ __forceinline__ void mf_solve_front(uint32_t xr, uint32_t u0, uint32_
 //   tables u16 | levels u32 | ext u32 | src i32 | flags u8 | entries with update slots u16 | their slot ranges u32 | slots u32 |
 //   colperm u32 | anc u32 | front descriptors 16 B | counters 32 B | KKT terms + products | back-substitution rows
 // ---------------------------------------------------------------------------
-struct MfCarve {
-  uint32_t o_arena, o_invd, o_x, o_tab, o_lvl, o_ext, o_src, o_flags, o_cent, o_cptr, o_cidx, o_cp, o_anc,
-      o_fr, o_cnt, o_terms;
-};
-__host__ __device__ inline uint32_t mf_align16(uint32_t v) { return (v + 15u) & ~15u; }
-__host__ __device__ inline MfCarve mf_carve(const LdltTask& t, const LdltMfTask& m) {
-  MfCarve c;
-  auto q = [](uint32_t count, uint32_t per16) { return 16u * ((count + per16 - 1u) / per16); };
-  c.o_arena = 8u * t.n_ent;
-  c.o_invd = c.o_arena + 8u * m.arena;
-  c.o_x = c.o_invd + 8u * t.n_col;
-  c.o_tab = mf_align16(c.o_x + 8u * (t.n_col + m.n_anc + 1u));
-  c.o_lvl = c.o_tab + q(m.n_tab, 8);
-  c.o_ext = c.o_lvl + q(t.n_lvl + 1u, 4);
-  c.o_src = c.o_ext + q(m.n_ext, 4);
-  c.o_flags = c.o_src + q(t.n_ent, 4);
-  c.o_cent = c.o_flags + q(t.n_ent, 16);
-  c.o_cptr = c.o_cent + q(m.n_cent, 8);
-  c.o_cidx = c.o_cptr + q(m.n_cent + 1u, 4);
-  c.o_cp = c.o_cidx + q(m.n_contrib_idx, 4);
-  c.o_anc = c.o_cp + q(t.n_col, 4);
-  c.o_fr = c.o_anc + q(m.n_anc, 4);
-  c.o_cnt = c.o_fr + 16u * m.n_front;
-  c.o_terms = c.o_cnt + 32u + kMfClockBytes;
-  return c;
-}
+// (MfCarve, mf_carve, mf_align16, kMfImageGroups: device_layout.h — build_mf_images of device_images.cpp writes every
+// task's image by the same offsets)
 
 // CHAINED: the variant of a chained step (DeviceNlp::sweep_full_for_step) — it waits for its sweep after
 // staging and counts its workgroups out; the other variant has none of that code.
@@ -581,7 +556,7 @@ __device__ __forceinline__ void mf_step_body(
   // ---- stage the plan: one image, one copy loop, every load in flight ----
   // (the image sits in a slot of fixed size, so its loads are requested before the task's own
   // descriptors — which say how much of the slot is image — have arrived: one trip to memory, not two)
-  constexpr int kInFlight = kMfImageGroups / THREADS;  // (DeviceNlp::build_mf: no image is longer than kMfImageGroups)
+  constexpr int kInFlight = kMfImageGroups / THREADS;  // (build_mf_images: no image is longer than kMfImageGroups)
   uint4 stage_v[kInFlight];
   const uint4* src16 = Mf.image + static_cast<size_t>(task_index) * Mf.image_stride16;
 #pragma unroll

@@ -442,6 +442,13 @@ extern "C" void hc_plan_hash(hc_handle* h, uint64_t* out) {
 extern "C" {
 void hc_destroy(hc_handle* h) { delete h; }
 
+// the plans themselves (NlpStructure, KktPlan, LdltPlan), for the support libraries that read them (imagecheck.cpp)
+void hc_plans(hc_handle* h, const void** out3) {
+  out3[0] = &h->s;
+  out3[1] = &h->k;
+  out3[2] = &h->l;
+}
+
 // Generates the run-time tape kernel of the full program and compiles it with hipRTC for
 // gfx950 (no device needed).  Returns the number of bodies compiled (0: the program has no
 // family worth one), -1 when hipRTC rejects the source (log on stderr).

@@ -53,6 +53,7 @@ def lib():
     sig("hc_create", vp, vp, vp, i32, i32, i32)
     sig("hc_destroy", None, vp)
     sig("hc_plan_hash", None, vp, vp)
+    sig("hc_plans", None, vp, vp)
     sig("hc_is_dense", i32, vp)
     sig("hc_mf_level_errors", i32, vp, d, d, vp, i32)
     sig("hc_tape_jit_compiles", i32, vp)
@@ -205,6 +206,12 @@ class HostCheck:
         if rows < 0:
             raise RuntimeError("no multifrontal plan (SLPX_LDLT_MF=1)")
         return out[:rows]
+
+    def plans(self):
+        """Addresses of the handle's NlpStructure, KktPlan and LdltPlan (for imagecheck)."""
+        out = (ctypes.c_void_p * 3)()
+        lib().hc_plans(self._h, out)
+        return [int(v) for v in out]
 
     def is_dense(self):
         """the system is factored as a dense matrix (no column of L fits a task of the sparse plan, or SLPX_DENSE=1)"""
