@@ -489,4 +489,92 @@ int orc_ldlt_factor_once(int n_total, int n, int m_e, const int* colptr, const i
   return info;
 }
 
+// The dense branch (dense_regularized_ldlt.hpp:59-136,167 — Eigen::LDLT's stand-in, DenseLDLT) on a caller-provided
+// lower-triangular CSC.  One factorization of lhs + diag(delta on the first n, -gamma on the rest): returns info;
+// D_out and trans_out (n_total each), inertia_out = (positive, negative, zero) of D, x_out = the solve of rhs
+// (optional; computed whatever info says, as DenseLDLT::solve does).
+int orc_dense_ldlt_factor_once(int n_total, int n, int m_e, const int* colptr, const int* rowidx, const double* val,
+                               double delta, double gamma, const double* rhs, double* D_out, int* trans_out,
+                               int* inertia_out, double* x_out) {
+  CSC lhs(n_total, n_total);
+  lhs.colptr.assign(colptr, colptr + n_total + 1);
+  lhs.rowidx.assign(rowidx, rowidx + colptr[n_total]);
+  lhs.val.assign(val, val + colptr[n_total]);
+  RegularizedLDLT helper(false, n, m_e, 0.0);
+  CSC a = add(lhs, helper.regularization(delta, gamma));
+  std::vector<double> dense(static_cast<size_t>(n_total) * n_total, 0.0);
+  for (int c = 0; c < n_total; ++c)
+    for (int p = a.colptr[c]; p < a.colptr[c + 1]; ++p) dense[static_cast<size_t>(c) * n_total + a.rowidx[p]] = a.val[p];
+  DenseLDLT s;
+  Info info = s.compute(std::move(dense), n_total);
+  Vec D = s.vectorD();
+  if (D_out) std::copy(D.begin(), D.end(), D_out);
+  if (trans_out) std::copy(s.transpositions().begin(), s.transpositions().end(), trans_out);
+  if (inertia_out) {
+    Inertia in(D);
+    inertia_out[0] = in.positive;
+    inertia_out[1] = in.negative;
+    inertia_out[2] = in.zero;
+  }
+  if (rhs && x_out) {
+    Vec x = s.solve(Vec(rhs, rhs + n_total));
+    std::copy(x.begin(), x.end(), x_out);
+  }
+  return info;
+}
+
+// The policy loop over the dense solver (RegularizedLDLT with use_sparse = false) from a fresh object: returns info;
+// delta_gamma_out = the regularization settled on, factorizations_out, D_out of the last factorization, x_out = the
+// solve of rhs where info is Success (both optional).
+int orc_dense_ldlt_solve(int n_total, int n, int m_e, const int* colptr, const int* rowidx, const double* val,
+                         const double* rhs, double gamma_min, double* x_out, double* D_out, double* delta_gamma_out,
+                         int* factorizations_out) {
+  CSC lhs(n_total, n_total);
+  lhs.colptr.assign(colptr, colptr + n_total + 1);
+  lhs.rowidx.assign(rowidx, rowidx + colptr[n_total]);
+  lhs.val.assign(val, val + colptr[n_total]);
+  RegularizedLDLT solver(false, n, m_e, gamma_min);
+  solver.compute(lhs);
+  if (delta_gamma_out) {
+    delta_gamma_out[0] = solver.hessian_regularization();
+    delta_gamma_out[1] = solver.constraint_jacobian_regularization();
+  }
+  if (factorizations_out) *factorizations_out = solver.factorizations();
+  Vec D = solver.vecD();
+  if (D_out) std::copy(D.begin(), D.end(), D_out);
+  if (solver.info() == Success && rhs && x_out) {
+    Vec x = solver.solve(Vec(rhs, rhs + n_total));
+    std::copy(x.begin(), x.end(), x_out);
+  }
+  return solver.info();
+}
+
+// What a test of a factorization A = L D Lᵀ needs and numpy is too slow for at order 1000: in long double, for
+// every i >= j, resid_out = A_ij - sum_k L_ik d_k L_jk and bound_out = sum_k |L_ik| |d_k| |L_jk| (k <= j; L unit
+// lower, its strictly lower part in `l`).  a, l, resid_out, bound_out: dense column-major n x n, lower triangle.
+void orc_ldlt_reconstruction(int n, const double* a, const double* l, const double* d, double* resid_out,
+                             double* bound_out) {
+  const size_t N = static_cast<size_t>(n);
+  std::vector<long double> rows(N * N, 0.0L);  // row-major L, the unit diagonal included
+  for (size_t i = 0; i < N; ++i) {
+    for (size_t k = 0; k < i; ++k) rows[i * N + k] = l[k * N + i];
+    rows[i * N + i] = 1.0L;
+  }
+  std::vector<long double> scaled(N);
+  for (size_t j = 0; j < N; ++j) {
+    for (size_t k = 0; k <= j; ++k) scaled[k] = rows[j * N + k] * static_cast<long double>(d[k]);
+    for (size_t i = j; i < N; ++i) {
+      long double s = 0.0L, b = 0.0L;
+      const long double* ri = rows.data() + i * N;
+      for (size_t k = 0; k <= j; ++k) {
+        const long double t = ri[k] * scaled[k];
+        s += t;
+        b += std::fabs(t);
+      }
+      resid_out[j * N + i] = static_cast<double>(static_cast<long double>(a[j * N + i]) - s);
+      bound_out[j * N + i] = static_cast<double>(b);
+    }
+  }
+}
+
 }  // extern "C"

@@ -239,7 +239,7 @@ class DenseLDLT {
     trans.assign(n, 0);
     bool ret = true;
     bool found_zero_pivot = false;
-    std::vector<double> temp(n);
+    std::vector<double> temp(n), sums;
     auto at = [&](int r, int c) -> double& { return m[static_cast<size_t>(c) * n + r]; };
     for (int k = 0; k < n; ++k) {
       int big = k;
@@ -260,14 +260,15 @@ class DenseLDLT {
       int rs = n - k - 1;
       if (k > 0) {
         for (int c = 0; c < k; ++c) temp[c] = at(c, c) * at(k, c);
-        double s = 0.0;
-        for (int c = 0; c < k; ++c) s += at(k, c) * temp[c];
-        at(k, k) -= s;
-        for (int r = 0; r < rs; ++r) {
-          double s2 = 0.0;
-          for (int c = 0; c < k; ++c) s2 += at(k + 1 + r, c) * temp[c];
-          at(k + 1 + r, k) -= s2;
+        // row k and the rows below it: every row's sum term by term in column order, the rows side by side (a
+        // column at a time: the order of each sum is the one above, the memory is walked contiguously)
+        sums.assign(rs + 1, 0.0);
+        for (int c = 0; c < k; ++c) {
+          const double t = temp[c];
+          const double* col = &at(k, c);
+          for (int r = 0; r <= rs; ++r) sums[r] += col[r] * t;
         }
+        for (int r = 0; r <= rs; ++r) at(k + r, k) -= sums[r];
       }
       double akk = at(k, k);
       bool pivot_is_valid = std::abs(akk) > 0.0;
@@ -314,6 +315,9 @@ class DenseLDLT {
     for (int k = n - 1; k >= 0; --k) std::swap(x[k], x[trans[k]]);
     return x;
   }
+
+  // transpositions(): step k exchanged k and trans[k] (identity on a zero matrix)
+  const std::vector<int>& transpositions() const { return trans; }
 
   int n = 0;
   Info info = Success;

@@ -97,7 +97,10 @@ __global__ __launch_bounds__(kDenseThreads) void ldlt_dense_factor_kernel(
 // triangle fills a quarter of it or more — the small problems of its unit tests, single shooting): Eigen::LDLT
 // (util/dense_regularized_ldlt.hpp:167), i.e. symmetric pivoting on the largest |diagonal| of the part not yet
 // factored, left-looking — the diagonal the pivot is chosen from is NOT yet updated, as in Eigen's unblocked kernel —
-// with Eigen's treatment of zero pivots (a zero pivot is an error only if something non-zero follows it).  The
+// with Eigen's treatment of zero pivots (a zero pivot is an error only if something non-zero follows it).  The pivot of
+// step k is the first index of the largest |diagonal| in [k, dim) as maxCoeff finds it, comparing with > from k on: k
+// itself when the entry at k is NaN or nothing compares greater (a NaN matrix), never a NaN entry after k — so
+// trans[k] is in [k, dim) whatever the input, non-finite included (such a matrix ends with n_bad = 1).  The
 // arithmetic is the textbook's, term by term in column order and without fused multiply-adds, so that D — and with it
 // every decision of the regularization policy — is what the reference's CPU path computes on the same matrix.
 // One workgroup per problem; `trans` (dim ints per problem): the transpositions.
@@ -139,7 +142,9 @@ __global__ __launch_bounds__(kDenseThreads) void ldlt_dense_pivoted_factor_kerne
   __syncthreads();
   const int lane = tid & 63, wave = tid >> 6;
   for (int k = 0; k < dim; ++k) {
-    // the largest |diagonal| of the rest, the first of equals (Eigen's maxCoeff)
+    // the largest |diagonal| of the rest, the first of equals (Eigen's maxCoeff: it starts at k and moves only on a
+    // strictly greater value, so a NaN at k keeps k and a NaN further on is never chosen).  bi == dim: this thread
+    // (wave, workgroup) has met nothing that compares — tid 0 turns that into k below, trans[k] is in [k, dim)
     {
       double best = -1.0;
       int bi = dim;
@@ -171,6 +176,7 @@ __global__ __launch_bounds__(kDenseThreads) void ldlt_dense_pivoted_factor_kerne
             bb = s_val[w];
             ii = s_idx[w];
           }
+        if (ii >= dim || isnan(at(k, k))) ii = k;
         s_flag[0] = ii;
         trans[k] = ii;
       }

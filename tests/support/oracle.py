@@ -90,6 +90,9 @@ def lib():
     sig("orc_eval_perm", None, i, vp)
     sig("orc_ldlt_solve", i, i, i, i, vp, vp, vp, vp, vp, i, d, d, vp, vp, vp, vp)
     sig("orc_ldlt_factor_once", i, i, i, i, vp, vp, vp, vp, i, d, d, vp, vp)
+    sig("orc_dense_ldlt_factor_once", i, i, i, i, vp, vp, vp, d, d, vp, vp, vp, vp, vp)
+    sig("orc_dense_ldlt_solve", i, i, i, i, vp, vp, vp, vp, d, vp, vp, vp, vp)
+    sig("orc_ldlt_reconstruction", None, i, vp, vp, vp, vp, vp)
     _lib = L
     return L
 
@@ -252,4 +255,45 @@ def ldlt_solve(n, m_e, colptr, rowidx, val, rhs, perm=None, gamma_min=1e-10):
                                 rhs.ctypes.data, None if p is None else p.ctypes.data,
                                 0 if p is None else len(p), gamma_min, 0.0, x.ctypes.data,
                                 D.ctypes.data, dg.ctypes.data, ctypes.addressof(nf))
+    return info, x, D, dg, nf.value
+
+
+def dense_ldlt_factor_once(n, m_e, colptr, rowidx, val, delta, gamma, rhs=None):
+    """One factorization of the oracle's dense branch (DenseLDLT, Eigen::LDLT's stand-in) of lhs + diag(delta, -gamma):
+    (info, D, trans, inertia = (positive, negative, zero), x) with x the solve of rhs, None without one."""
+    colptr, rowidx, val = _ia(colptr), _ia(rowidx), _fa(val)
+    nt = n + m_e
+    D, trans, inertia = np.zeros(nt), np.zeros(nt, dtype=np.int32), np.zeros(3, dtype=np.int32)
+    b = None if rhs is None else _fa(rhs)
+    x = None if rhs is None else np.zeros(nt)
+    info = lib().orc_dense_ldlt_factor_once(nt, n, m_e, colptr.ctypes.data, rowidx.ctypes.data, val.ctypes.data,
+                                            float(delta), float(gamma), None if b is None else b.ctypes.data,
+                                            D.ctypes.data, trans.ctypes.data, inertia.ctypes.data,
+                                            None if x is None else x.ctypes.data)
+    return info, D, trans, inertia, x
+
+
+def ldlt_reconstruction(A, L, D):
+    """(A - L D L^T, |L| |D| |L^T|) entry by entry in long double, rounded to double; lower triangles of dense
+    matrices (A symmetric, L unit lower: only its strictly lower part is read)."""
+    dim = len(D)
+    a = np.asfortranarray(A, dtype=np.float64)
+    l = np.asfortranarray(L, dtype=np.float64)
+    d = _fa(D)
+    resid, bound = np.zeros((dim, dim), order="F"), np.zeros((dim, dim), order="F")
+    lib().orc_ldlt_reconstruction(dim, a.ctypes.data, l.ctypes.data, d.ctypes.data, resid.ctypes.data, bound.ctypes.data)
+    return np.tril(resid), np.tril(bound)
+
+
+def dense_ldlt_solve(n, m_e, colptr, rowidx, val, rhs=None, gamma_min=1e-10):
+    """The policy loop over the oracle's dense branch (RegularizedLDLT with use_sparse = false) from a fresh object:
+    (info, x, D, (delta, gamma), factorizations); x stays zero without a rhs or where info is not Success."""
+    colptr, rowidx, val = _ia(colptr), _ia(rowidx), _fa(val)
+    nt = n + m_e
+    x, D, dg = np.zeros(nt), np.zeros(nt), np.zeros(2)
+    nf = ctypes.c_int()
+    b = None if rhs is None else _fa(rhs)
+    info = lib().orc_dense_ldlt_solve(nt, n, m_e, colptr.ctypes.data, rowidx.ctypes.data, val.ctypes.data,
+                                      None if b is None else b.ctypes.data, gamma_min, x.ctypes.data, D.ctypes.data,
+                                      dg.ctypes.data, ctypes.addressof(nf))
     return info, x, D, dg, nf.value

@@ -100,12 +100,23 @@ def test_linear_solver_seam_on_the_dense_branch(monkeypatch, batch):
     util/regularized_ldlt.hpp:45-87) on the dense kernels, single and batched (a workgroup per problem): a
     quasidefinite matrix needs no regularization, an indefinite Hessian is regularized to the ideal inertia — against
     dense numpy solves of the regularized matrices."""
+    _seam_on_the_dense_branch(monkeypatch, batch, 48, 20)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("batch", [1, 3])
+def test_linear_solver_seam_on_the_dense_branch_order_1025(monkeypatch, batch):
+    """The same at n + m_e = 1025: the smallest order at which a thread of the dense kernels' 1024 owns two entries
+    (the second pass of every `for (i = tid; i < dim; i += 1024)` of the factorization and of the solve)."""
+    _seam_on_the_dense_branch(monkeypatch, batch, 1005, 20)
+
+
+def _seam_on_the_dense_branch(monkeypatch, batch, n, m_e):
     import sleipnir_amd as sa
     from tests.test_linear_solver_gpu import _check_solution, _kkt
 
     monkeypatch.setenv("SLPX_DENSE", "1")
     rng = np.random.default_rng(31)
-    n, m_e = 48, 20
     for definite in (True, False):
         K, colptr, rowidx, vals = _kkt(rng, n, m_e, definite=definite, c22=1e-2 if definite else 0.0)
         scale = 1.0 + 0.1 * rng.random((batch, 1))
