@@ -305,6 +305,65 @@ int slpx_problem_solve_batch_warm(slpx_problem* p, int32_t batch, const double* 
                                   double* mu, double* cost, int32_t* iterations, int32_t* restorations, int32_t* repaired,
                                   slpx_report* report);
 
+/* ---- solution sensitivities ------------------------------------------------------------
+ * How the end iterate of the last slpx_problem_solve* moves when a parameter moves (no reference counterpart): the
+ * tangent predictor of an MPC loop — iterate + d(iterate)/dp dp as the warm start of the next solve — and the gradient
+ * of anything downstream of x* with respect to the parameters.  The entry points of this section are additions within
+ * ABI version 6, detected by the symbol's presence like slpx_problem_solve_batch.
+ *
+ * With L = f - y^T c_e - z^T c_i, Sigma = S^-1 Z and, for parameter q at the iterate (x, s, y, z) HELD FIXED,
+ *     r_x = d(grad_x L)/dp_q      r_e = dc_e/dp_q      r_i = dc_i/dp_q
+ * the KKT conditions differentiated, ds and dz eliminated as the Newton step eliminates p_s and p_z
+ * (interior_point.hpp:426-481), give
+ *     [H + A_i^T Sigma A_i  A_e^T] [ dx ]   [-r_x - A_i^T Sigma r_i]
+ *     [       A_e            0   ] [-dy ] = [        -r_e          ]       ds = A_i dx + r_i      dz = -Sigma ds
+ * — the matrix of the Newton step, assembled at the iterate and factored by the same inertia-correcting loop
+ * (slpx_ldlt_compute, from a cleared memory), every right-hand side solved on that factorization and refined twice
+ * (slpx_ldlt_refine).  The barrier parameter is held fixed: for an interior-point solve these are the sensitivities of
+ * the barrier problem's solution, which differ from those of the model's by O(mu).  Without inequality constraints,
+ * and without any constraints, the same equations with the blocks absent.
+ *
+ * UNITS: everything is in the USER'S units, those of slpx_problem_get_iterate (warm starts, above).  The model's own
+ * system is swept, assembled and factored at unit scales for the call; the scaling of the last solve is installed again
+ * before it returns.  ORDER: parameters as slpx_problem_parameters; outputs are parameter-major, row q = d(.)/dp_q.
+ *
+ * COST.  The first call compiles the model once more with the parameters as variables ("the extended structure":
+ * t_compile; kept with the problem, dropped when the model is compiled again — slpx_problem_compile_count does not
+ * count it).  The factorization is kept until the next slpx_problem_solve* / restoration call of the problem, the next
+ * slpx_problem_system, or a model change: calls in between report factorizations = 0.  A caller that drives the
+ * handle of slpx_problem_system itself between two calls asks for that handle again first.  The Jacobian takes n_p
+ * solves; the two products take ONE each, whatever n_p.  A following solve is not affected in any bit: the
+ * regularization memory, the scaling and the parameters of the problem's system are as they were.
+ *
+ * ERRORS: -100 + slpx_last_error() for a null problem, before any solve that ran a solver, for a model that reaches
+ * no parameter, when the parameters' values are no longer those of the solve the iterate came from
+ * (slpx_problem_set_parameters / slpx_expr_set_value with no new solve), without a HIP device, and when the system
+ * cannot be factored at all.  The status of that solve is NOT judged (solve_status reports it), and a regularization
+ * the factorization needed is no error: delta, gamma and the inertia are reported. */
+typedef struct slpx_sensitivity_info {
+  int32_t n_p, solves, factorizations, refine_steps;   /* of this call (solves: refinement's included) */
+  int32_t n_pos, n_neg, n_zero;                        /* inertia of what was factored */
+  double delta, gamma;                                 /* regularization it needed */
+  double berr_max;                                     /* largest componentwise backward error over the solves
+                                                          (slpx_ldlt_error_bounds: of the system as factored, delta and
+                                                          gamma in it; it reaches O(1) where a whole row of a right-hand
+                                                          side and its solution is at rounding level) */
+  int32_t solve_status;                                /* ExitStatus of the solve the iterate came from */
+  double t_compile, t_factor, t_total;                 /* seconds; t_compile > 0 on the first call only; t_total includes
+                                                          both */
+} slpx_sensitivity_info;
+/* The Jacobian: dx[n_p][n], ds[n_p][m_i], dy[n_p][m_e], dz[n_p][m_i].  Any output, and info, may be NULL. */
+int slpx_problem_sensitivity(slpx_problem* p, double* dx, double* ds, double* dy, double* dz, slpx_sensitivity_info* info);
+/* The Jacobian-vector product along dp[n_p]: dx[n], ds[m_i], dy[m_e], dz[m_i] — iterate + these is a valid
+ * slpx_warm_start of the model with parameters + dp (mu: that of the iterate). */
+int slpx_problem_sensitivity_jvp(slpx_problem* p, const double* dp, double* dx, double* ds, double* dy, double* dz,
+                                 slpx_sensitivity_info* info);
+/* The vector-Jacobian product for a cotangent vx[n] on x: grad_p[q] = sum_i vx[i] dx_i/dp_q, from ONE solve K w = [vx; 0]
+ * and grad_p[q] = w^T R[:, q], R the right-hand sides above (K is symmetric, also when regularized). */
+int slpx_problem_sensitivity_vjp(slpx_problem* p, const double* vx, double* grad_p, slpx_sensitivity_info* info);
+/* M[n_p][n + m_e + m_i]: r_x, r_e, r_i per parameter, at the iterate.  Neither factors nor solves. */
+int slpx_problem_sensitivity_rhs(slpx_problem* p, double* M);
+
 /* ---- compiled Newton system ------------------------------------------------------
  * One problem structure compiled for one GPU, `batch` independent value sets.
  * Replaces, per Newton step:

@@ -68,6 +68,15 @@ class WarmStart(ctypes.Structure):
     _fields_ = [("s", ctypes.c_void_p), ("y", ctypes.c_void_p), ("z", ctypes.c_void_p), ("mu", ctypes.c_double)]
 
 
+class SensitivityInfo(ctypes.Structure):
+    """slpx_sensitivity_info: what one sensitivity call did (include/slpx.h: solution sensitivities)."""
+    _fields_ = [("n_p", ctypes.c_int32), ("solves", ctypes.c_int32), ("factorizations", ctypes.c_int32),
+                ("refine_steps", ctypes.c_int32), ("n_pos", ctypes.c_int32), ("n_neg", ctypes.c_int32),
+                ("n_zero", ctypes.c_int32), ("delta", ctypes.c_double), ("gamma", ctypes.c_double),
+                ("berr_max", ctypes.c_double), ("solve_status", ctypes.c_int32), ("t_compile", ctypes.c_double),
+                ("t_factor", ctypes.c_double), ("t_total", ctypes.c_double)]
+
+
 def build(force: bool = False, verbose: bool = False) -> Path:
     """Compile libslpx.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     # (at most 16 jobs: a shared build host may count far more CPUs than one build may use)
@@ -202,6 +211,11 @@ def lib() -> ctypes.CDLL:
         sig("slpx_problem_warm_start_repaired", i32, vp)
         sig("slpx_problem_solve_batch_warm", ctypes.c_int, vp, i32, vp, vp, vp, vp, vp, vp, ctypes.POINTER(Options),
             ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(Report))
+    if hasattr(L, "slpx_problem_sensitivity"):
+        sig("slpx_problem_sensitivity", ctypes.c_int, vp, vp, vp, vp, vp, ctypes.POINTER(SensitivityInfo))
+        sig("slpx_problem_sensitivity_jvp", ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.POINTER(SensitivityInfo))
+        sig("slpx_problem_sensitivity_vjp", ctypes.c_int, vp, vp, vp, ctypes.POINTER(SensitivityInfo))
+        sig("slpx_problem_sensitivity_rhs", ctypes.c_int, vp, vp)
     _lib = L
     return L
 
@@ -327,6 +341,73 @@ class Problem:
     def warm_start_repaired(self) -> int:
         """Entries of its warm start the last solve's safeguard replaced or clamped (slpx_problem_warm_start_repaired)."""
         return int(lib().slpx_problem_warm_start_repaired(self._h))
+
+    # ---- solution sensitivities (include/slpx.h): everything in the user's units, rows in the order of parameters() ----
+    def _sensitivity_entry(self, name):
+        L = lib()
+        if not hasattr(L, name):
+            raise SlpxError(f"{LIB_PATH} has no {name}")
+        return getattr(L, name)
+
+    @staticmethod
+    def _sensitivity_info(info):
+        return {f[0]: getattr(info, f[0]) for f in SensitivityInfo._fields_}
+
+    def sensitivity(self):
+        """The Jacobian of the last solve's end iterate with respect to the parameters (slpx_problem_sensitivity):
+        dict(dx (n_p, n), ds (n_p, m_i), dy (n_p, m_e), dz (n_p, m_i), info)."""
+        fn = self._sensitivity_entry("slpx_problem_sensitivity")
+        n, me, mi = self.dims
+        # (the sizes come first, so an error of the call itself — no solve yet, no parameters — is the library's)
+        n_p = max(0, lib().slpx_problem_parameters(self._h, None, 0))
+        out = {"dx": np.zeros((n_p, n)), "ds": np.zeros((n_p, mi)), "dy": np.zeros((n_p, me)), "dz": np.zeros((n_p, mi))}
+        info = SensitivityInfo()
+        if fn(self._h, *(out[k].ctypes.data if out[k].size else None for k in ("dx", "ds", "dy", "dz")), ctypes.byref(info)) != 0:
+            raise SlpxError(lib().slpx_last_error().decode())
+        out["info"] = self._sensitivity_info(info)
+        return out
+
+    def sensitivity_jvp(self, dp):
+        """The directional derivative of the end iterate along dp (n_p) (slpx_problem_sensitivity_jvp):
+        dict(dx (n), ds (m_i), dy (m_e), dz (m_i), info).  iterate() + these is a warm start for parameters + dp."""
+        fn = self._sensitivity_entry("slpx_problem_sensitivity_jvp")
+        n, me, mi = self.dims
+        n_p = max(0, lib().slpx_problem_parameters(self._h, None, 0))
+        dp = np.ascontiguousarray(np.asarray(dp, dtype=np.float64).ravel())
+        if n_p and dp.shape[0] != n_p:
+            raise SlpxError(f"sensitivity_jvp: dp must have {n_p} entries, one per parameter")
+        out = {"dx": np.zeros(n), "ds": np.zeros(mi), "dy": np.zeros(me), "dz": np.zeros(mi)}
+        info = SensitivityInfo()
+        hold = dp if dp.size else np.zeros(1)
+        if fn(self._h, hold.ctypes.data, *(out[k].ctypes.data if out[k].size else None for k in ("dx", "ds", "dy", "dz")),
+              ctypes.byref(info)) != 0:
+            raise SlpxError(lib().slpx_last_error().decode())
+        out["info"] = self._sensitivity_info(info)
+        return out
+
+    def sensitivity_vjp(self, vx):
+        """(dx/dp)^T vx (n_p) for a cotangent vx (n) on x, from one solve (slpx_problem_sensitivity_vjp): (grad, info)."""
+        fn = self._sensitivity_entry("slpx_problem_sensitivity_vjp")
+        n = self.dims[0]
+        n_p = max(0, lib().slpx_problem_parameters(self._h, None, 0))
+        vx = np.ascontiguousarray(np.asarray(vx, dtype=np.float64).ravel())
+        if vx.shape[0] != n:
+            raise SlpxError(f"sensitivity_vjp: vx must have {n} entries, one per decision variable")
+        grad = np.zeros(max(1, n_p))
+        info = SensitivityInfo()
+        if fn(self._h, vx.ctypes.data if vx.size else None, grad.ctypes.data, ctypes.byref(info)) != 0:
+            raise SlpxError(lib().slpx_last_error().decode())
+        return grad[:n_p], self._sensitivity_info(info)
+
+    def sensitivity_rhs(self):
+        """M (n_p, n + m_e + m_i): per parameter r_x = d(grad_x L)/dp, r_e = dc_e/dp, r_i = dc_i/dp at the end iterate
+        (slpx_problem_sensitivity_rhs)."""
+        fn = self._sensitivity_entry("slpx_problem_sensitivity_rhs")
+        n_p = max(0, lib().slpx_problem_parameters(self._h, None, 0))
+        M = np.zeros((n_p, sum(self.dims)))
+        if fn(self._h, M.ctypes.data if M.size else None) != 0:
+            raise SlpxError(lib().slpx_last_error().decode())
+        return M
 
     RESTORATION_MODES = {"handoff": 0, "lockstep": 1}
 

@@ -231,6 +231,63 @@ int slpx_problem_get_iterate(const slpx_problem* p, double* x, double* sv, doubl
 int32_t slpx_problem_warm_start_repaired(const slpx_problem* p) { return p ? p->problem.warm_start_repaired() : -1; }
 
 namespace {
+void sensitivity_info_out(const slpx::SensitivityInfo& in, slpx_sensitivity_info* out) {
+  if (out == nullptr) return;
+  *out = slpx_sensitivity_info{in.n_p,   in.solves, in.factorizations, in.refine_steps, in.n_pos,     in.n_neg,    in.n_zero,
+                               in.delta, in.gamma,  in.berr_max,       in.solve_status, in.t_compile, in.t_factor, in.t_total};
+}
+void sensitivity_preconditions(const slpx_problem* p, const char* who) {
+  if (p == nullptr) throw std::runtime_error(std::string(who) + ": null problem");
+  if (slpx_device_count() < 1) throw std::runtime_error(std::string(who) + ": no HIP device");
+}
+}  // namespace
+
+int slpx_problem_sensitivity(slpx_problem* p, double* dx, double* ds, double* dy, double* dz, slpx_sensitivity_info* info) {
+  return guard([&] {
+    sensitivity_preconditions(p, "slpx_problem_sensitivity");
+    const auto r = p->problem.sensitivity();
+    if (dx) std::copy(r.dx.begin(), r.dx.end(), dx);
+    if (ds) std::copy(r.ds.begin(), r.ds.end(), ds);
+    if (dy) std::copy(r.dy.begin(), r.dy.end(), dy);
+    if (dz) std::copy(r.dz.begin(), r.dz.end(), dz);
+    sensitivity_info_out(r.info, info);
+  });
+}
+int slpx_problem_sensitivity_jvp(slpx_problem* p, const double* dp, double* dx, double* ds, double* dy, double* dz,
+                                 slpx_sensitivity_info* info) {
+  return guard([&] {
+    sensitivity_preconditions(p, "slpx_problem_sensitivity_jvp");
+    if (dp == nullptr) throw std::runtime_error("slpx_problem_sensitivity_jvp: dp is null");
+    // (the length of dp is the model's: asked for before the call that checks everything else, which needs no device)
+    const size_t n_p = p->problem.compiled() ? p->problem.compiled()->structure().parameter_nodes().size() : 0;
+    slpx::SensitivityInfo si;
+    const auto d = p->problem.sensitivity_jvp(std::span<const double>(dp, n_p), &si);
+    if (dx) std::copy(d.x.begin(), d.x.end(), dx);
+    if (ds) std::copy(d.s.begin(), d.s.end(), ds);
+    if (dy) std::copy(d.y.begin(), d.y.end(), dy);
+    if (dz) std::copy(d.z.begin(), d.z.end(), dz);
+    sensitivity_info_out(si, info);
+  });
+}
+int slpx_problem_sensitivity_vjp(slpx_problem* p, const double* vx, double* grad_p, slpx_sensitivity_info* info) {
+  return guard([&] {
+    sensitivity_preconditions(p, "slpx_problem_sensitivity_vjp");
+    if (vx == nullptr) throw std::runtime_error("slpx_problem_sensitivity_vjp: vx is null");
+    slpx::SensitivityInfo si;
+    const auto g = p->problem.sensitivity_vjp(std::span<const double>(vx, p->problem.decision_variables().size()), &si);
+    if (grad_p) std::copy(g.begin(), g.end(), grad_p);
+    sensitivity_info_out(si, info);
+  });
+}
+int slpx_problem_sensitivity_rhs(slpx_problem* p, double* M) {
+  return guard([&] {
+    sensitivity_preconditions(p, "slpx_problem_sensitivity_rhs");
+    const auto m = p->problem.sensitivity_rhs();
+    if (M) std::copy(m.begin(), m.end(), M);
+  });
+}
+
+namespace {
 int solve_batch_impl(slpx_problem* p, int32_t batch, const double* x0, const double* params, const slpx::BatchWarmStart* warm,
                      const slpx_options* o, int32_t* status, double* x, double* sv, double* y, double* z, double* mu,
                      double* cost, int32_t* iterations, int32_t* restorations, int32_t* repaired, slpx_report* report) {
@@ -391,6 +448,7 @@ slpx_system* slpx_problem_system(slpx_problem* p) {
     if (!p->borrowed) p->borrowed = std::make_unique<slpx_system>();
     p->borrowed->owner = &p->problem;
     p->borrowed->ref = &p->problem.compile();
+    p->problem.sensitivity_forget();  // (the caller may factor on it: a kept sensitivity factorization is not trusted)
   });
   return rc == 0 ? p->borrowed.get() : nullptr;
 }

@@ -1,0 +1,119 @@
+#include "sens_plan.hpp"
+
+#include <stdexcept>
+#include <string>
+#include <utility>
+
+#include "sens_rows.h"
+
+namespace slpx {
+
+SensPlan build_sens_plan(const NlpStructure& model, const NlpStructure& ext) {
+  SensPlan p;
+  p.n = model.n;
+  p.m_e = model.m_e;
+  p.m_i = model.m_i;
+  p.n_p = ext.n - model.n;
+  if (p.n_p <= 0) throw std::runtime_error("slpx: sensitivity plan: the extended structure has no parameter columns");
+  if (ext.m_e != model.m_e || ext.m_i != model.m_i)
+    throw std::runtime_error("slpx: sensitivity plan: the extended structure has other constraints than the model");
+  for (const CscPattern* pat : {&ext.Ae, &ext.Ai, &ext.Hf, &ext.Hc})
+    if (pat->cols != ext.n || static_cast<int>(pat->colptr.size()) != ext.n + 1)
+      throw std::runtime_error("slpx: sensitivity plan: a pattern of the extended structure is not over n + n_p columns");
+  p.dim = p.n + p.m_e;
+  p.dimM = p.n + p.m_e + p.m_i;
+  p.nV = model.nV;
+  p.nVx = ext.nV;
+  const int n = p.n, n_p = p.n_p, m_e = p.m_e, dimM = p.dimM;
+
+  // every source of M, Hessians first (H_f' before H_c'), as f(key = q * dimM + row, position in V')
+  auto for_each_source = [&](auto&& f) {
+    using Block = std::pair<const CscPattern*, int>;
+    for (const auto& [pat, off] : {Block{&ext.Hf, ext.off_Hf}, Block{&ext.Hc, ext.off_Hc}})
+      for (int c = 0; c < n; ++c)  // (columns >= n: the p-p block, which no sensitivity reads)
+        for (int32_t t = pat->colptr[c]; t < pat->colptr[c + 1]; ++t) {
+          const int r = pat->rowidx[t];
+          if (r < c) throw std::runtime_error("slpx: sensitivity plan: a Hessian entry above the diagonal");
+          if (r >= n) f(static_cast<int64_t>(r - n) * dimM + c, off + t);
+        }
+    for (int q = 0; q < n_p; ++q) {
+      for (int32_t t = ext.Ae.colptr[n + q]; t < ext.Ae.colptr[n + q + 1]; ++t)
+        f(static_cast<int64_t>(q) * dimM + n + ext.Ae.rowidx[t], ext.off_Ae + t);
+      for (int32_t t = ext.Ai.colptr[n + q]; t < ext.Ai.colptr[n + q + 1]; ++t)
+        f(static_cast<int64_t>(q) * dimM + n + m_e + ext.Ai.rowidx[t], ext.off_Ai + t);
+    }
+  };
+  const int64_t cells = static_cast<int64_t>(n_p) * dimM;
+  if (cells >= (int64_t{1} << 31)) throw std::runtime_error("slpx: sensitivity plan: n_p (n + m_e + m_i) does not fit 31 bits");
+  p.m_ptr.assign(static_cast<size_t>(cells) + 1, 0);
+  for_each_source([&](int64_t key, int32_t) { ++p.m_ptr[key + 1]; });
+  for (int64_t k = 0; k < cells; ++k) p.m_ptr[k + 1] += p.m_ptr[k];
+  p.m_src.assign(static_cast<size_t>(p.m_ptr[cells]), -1);
+  {
+    std::vector<int32_t> next(p.m_ptr.begin(), p.m_ptr.end() - 1);
+    for_each_source([&](int64_t key, int32_t src) { p.m_src[next[key]++] = src; });
+  }
+
+  // A_i of the model: by columns for the reduction (pattern order), by rows for the expansion (columns ascending)
+  const CscPattern& Ai = model.Ai;
+  p.red_ptr.assign(Ai.colptr.begin(), Ai.colptr.end());
+  if (static_cast<int>(p.red_ptr.size()) != n + 1) throw std::runtime_error("slpx: sensitivity plan: A_i is not over n columns");
+  p.red_src.resize(Ai.nnz());
+  p.red_row.assign(Ai.rowidx.begin(), Ai.rowidx.end());
+  for (int t = 0; t < Ai.nnz(); ++t) p.red_src[t] = model.off_Ai + t;
+  p.ai_rowptr.assign(p.m_i + 1, 0);
+  for (int32_t r : Ai.rowidx) ++p.ai_rowptr[r + 1];
+  for (int j = 0; j < p.m_i; ++j) p.ai_rowptr[j + 1] += p.ai_rowptr[j];
+  p.ai_col.resize(Ai.nnz());
+  p.ai_src.resize(Ai.nnz());
+  {
+    std::vector<int32_t> next(p.ai_rowptr.begin(), p.ai_rowptr.end() - 1);
+    for (int c = 0; c < n; ++c)
+      for (int32_t t = Ai.colptr[c]; t < Ai.colptr[c + 1]; ++t) {
+        const int32_t at = next[Ai.rowidx[t]]++;
+        p.ai_col[at] = c;
+        p.ai_src[at] = model.off_Ai + t;
+      }
+  }
+  return p;
+}
+
+void sens_host_rhs(const SensPlan& p, const double* Vx, const double* V, const double* s, const double* z, double* M, double* R) {
+  for (int q = 0; q < p.n_p; ++q)
+    for (int row = 0; row < p.dimM; ++row) {
+      const int64_t k = static_cast<int64_t>(q) * p.dimM + row;
+      const double m = sens_m_entry(p.m_ptr.data(), p.m_src.data(), Vx, k);
+      M[k] = m;
+      if (row < p.dim)
+        R[static_cast<int64_t>(q) * p.dim + row] =
+            sens_reduced_entry(p.n, p.m_e, p.dimM, p.m_ptr.data(), p.m_src.data(), p.red_ptr.data(), p.red_src.data(),
+                               p.red_row.data(), Vx, V, s, z, q, row, m);
+    }
+}
+
+void sens_host_combine(const SensPlan& p, const double* M, const double* R, const double* dp, double* rhs, double* r_i) {
+  for (int row = 0; row < p.dim; ++row) rhs[row] = sens_combine_entry(p.n_p, R, p.dim, 0, row, dp);
+  for (int j = 0; j < p.m_i; ++j) r_i[j] = sens_combine_entry(p.n_p, M, p.dimM, p.n + p.m_e, j, dp);
+}
+
+void sens_host_expand(const SensPlan& p, const double* V, const double* s, const double* z, const double* sol, const double* r_i,
+                      double* dx, double* ds, double* dy, double* dz) {
+  for (int i = 0; i < p.n; ++i) dx[i] = sol[i];
+  for (int j = 0; j < p.m_e; ++j) dy[j] = -sol[p.n + j];
+  for (int j = 0; j < p.m_i; ++j) {
+    ds[j] = sens_ds_entry(p.ai_rowptr.data(), p.ai_col.data(), p.ai_src.data(), V, sol, r_i, j);
+    dz[j] = sens_dz_entry(s[j], z[j], ds[j]);
+  }
+}
+
+void sens_host_vjp(const SensPlan& p, const double* R, const double* w, double* grad) {
+  for (int q = 0; q < p.n_p; ++q) {
+    double part[kSensVjpThreads];
+    for (int t = 0; t < kSensVjpThreads; ++t) part[t] = sens_vjp_partial(p.dim, R + static_cast<int64_t>(q) * p.dim, w, t);
+    for (int width = kSensVjpThreads / 2; width > 0; width >>= 1)
+      for (int t = 0; t < width; ++t) part[t] = part[t] + part[t + width];
+    grad[q] = part[0];
+  }
+}
+
+}  // namespace slpx

@@ -1,0 +1,109 @@
+// Solution sensitivities to the parameters (include/slpx.h: solution sensitivities): the derivative of the end
+// iterate (x, s, y, z) of a solve with respect to the model's parameters, as a Jacobian, a Jacobian-vector product
+// and a vector-Jacobian product.  sens_plan.hpp states the equations.
+//
+// What is new here is small: the derivative of the KKT residual with respect to the parameters — the EXTENDED
+// structure, the model compiled once more with x' = [x ; p], whose tape is swept at the iterate — and the kernels of
+// sensitivity.hip that gather it into right-hand sides and expand solutions.  Everything else is the model's own
+// batch-1 system as it stands: its sweep and assembly at the iterate, NewtonSystem::compute() (the ordinary
+// regularization policy loop), DeviceNlp::solve(), NewtonSystem::refine() and error_bounds().
+//
+// UNITS.  The model system is swept and assembled at UNIT scales with the iterate in the user's units (warm_start.h),
+// and so is the extended one: the system that is factored, the right-hand sides and every output are in the user's
+// units, whatever scaling the solve ran with.  The scaling the caller names is installed again afterwards.
+//
+// The extended system is a whole NewtonSystem (its KKT plan and symbolic factorization are made and never used: the
+// shortest route, and the measured cost is in profiles/sensitivity.txt); it lives as long as this object, which the
+// problem drops when the model is compiled again.
+#pragma once
+
+#include <memory>
+#include <vector>
+
+#include "device.hpp"
+#include "newton.hpp"
+#include "sens_plan.hpp"
+
+namespace slpx {
+
+// slpx_sensitivity_info (include/slpx.h), of one call
+struct SensitivityInfo {
+  int32_t n_p = 0, solves = 0, factorizations = 0, refine_steps = 0;
+  int32_t n_pos = 0, n_neg = 0, n_zero = 0;
+  double delta = 0.0, gamma = 0.0;
+  double berr_max = 0.0;
+  int32_t solve_status = 0;
+  double t_compile = 0.0, t_factor = 0.0, t_total = 0.0;
+};
+
+// the plan on the device: what the kernels of sensitivity.hip take (SensPlan's arrays by the same names)
+struct SensDev {
+  int n, n_p, m_e, m_i, dim, dimM;
+  const int32_t *m_ptr, *m_src, *red_ptr, *red_src, *red_row, *ai_rowptr, *ai_col, *ai_src;
+};
+
+class Sensitivity {
+ public:
+  // Where the derivatives are taken: the iterate in the user's units, the parameters' values (the order of
+  // NlpStructure::parameter_nodes()), and the scaling to leave on the model system.
+  struct Point {
+    const std::vector<double>*x, *s, *y, *z;
+    double mu = 0.0;
+    const std::vector<double>* parameters;
+    const std::vector<double>* scales_after;
+  };
+
+  // `model`: the problem's batch-1 system, with its device; `f`: the cost's root (kNull: none).  Compiles the extended
+  // structure for the model's device and builds and uploads the plan.  Throws where the model reaches no parameter.
+  Sensitivity(NewtonSystem& model, NodeId f);
+  ~Sensitivity();
+  Sensitivity(const Sensitivity&) = delete;
+  Sensitivity& operator=(const Sensitivity&) = delete;
+
+  const SensPlan& plan() const { return m_plan; }
+  const NewtonSystem& extended() const { return *m_ext; }
+  // seconds the constructor took; reported as t_compile by the first product and 0 afterwards
+  double take_compile_seconds() {
+    const double t = m_compile_seconds;
+    m_compile_seconds = 0.0;
+    return t;
+  }
+
+  // The model system was used by somebody else (a solve, a batch's hand-off, the caller's own handle), or the iterate
+  // is another one: the next product sweeps, assembles and factors again.  Until then a product reuses what the last
+  // one left — a Jacobian followed by a vjp factors once.
+  void forget() { m_evaluated = m_factored = false; }
+
+  // Any output may be null.  dx [n_p][n], ds [n_p][m_i], dy [n_p][m_e], dz [n_p][m_i]: one solve per parameter.
+  void jacobian(const Point& at, double* dx, double* ds, double* dy, double* dz, SensitivityInfo& info);
+  // The directional derivative along dp [n_p]: one solve.  dx [n], ds [m_i], dy [m_e], dz [m_i].
+  void jvp(const Point& at, const double* dp, double* dx, double* ds, double* dy, double* dz, SensitivityInfo& info);
+  // grad [n_p] = (dx/dp)^T vx for a cotangent vx [n] on x: one solve, K w = [vx; 0], then w^T R.
+  void vjp(const Point& at, const double* vx, double* grad, SensitivityInfo& info);
+  // M [n_p][n + m_e + m_i]: r_x, r_e, r_i per parameter.  No factorization.
+  void unreduced(const Point& at, double* M);
+
+ private:
+  void evaluate(const Point& at);
+  void factor(const Point& at, SensitivityInfo& info);
+  // rhs (device, dim) -> the refined solution into sol (device, dim)
+  void solve_one(const double* rhs, double* sol, SensitivityInfo& info);
+  void expand_and_download(int columns, const double* r_i, long long r_i_stride, double* dx, double* ds, double* dy, double* dz);
+  SensDev view() const;
+
+  NewtonSystem& m_model;
+  std::unique_ptr<NewtonSystem> m_ext;
+  SensPlan m_plan;
+  double m_compile_seconds = 0.0;
+  bool m_evaluated = false, m_factored = false;
+  // of the factorization in memory (reported by every product that reuses it)
+  int32_t m_n_pos = 0, m_n_neg = 0, m_n_zero = 0;
+  double m_delta = 0.0, m_gamma = 0.0;
+
+  DevBuf<int32_t> m_m_ptr, m_m_src, m_red_ptr, m_red_src, m_red_row, m_ai_rowptr, m_ai_col, m_ai_src;
+  // M, R; the model's V, s, z at the iterate (copies: the model system's own are its caller's again after a product)
+  DevBuf<double> m_M, m_R, m_V, m_s, m_z;
+  DevBuf<double> m_vec, m_rhs1, m_ri1, m_sol, m_out, m_grad;
+};
+
+}  // namespace slpx

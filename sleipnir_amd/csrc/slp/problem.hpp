@@ -29,6 +29,7 @@
 #include "../ipm_batch.hpp"
 #include "../ipm_host.hpp"
 #include "../newton.hpp"
+#include "../sensitivity.hpp"
 #include "../warm_start.h"
 #include "variable.hpp"
 
@@ -217,11 +218,101 @@ class ProblemF64 {
   // how many entries of the last solve's warm start the safeguard replaced or clamped (0 after a cold start)
   int warm_start_repaired() const { return m_warm_result.repaired; }
 
+  // ---- solution sensitivities (sensitivity.hpp; include/slpx.h: solution sensitivities) ----
+  // How the iterate() of the last solve() moves with the parameters (the order of parameters()), the iterate held as
+  // the solve left it, everything in the user's units: iterate() + sensitivity_jvp(dp) is a warm start for the model
+  // with parameters() + dp.  The first call compiles the extended structure (info.t_compile); calls between two solves
+  // share one factorization (info.factorizations == 0 from the second on).  Every one throws before any solve, for a
+  // model without parameters, after the parameters changed with no new solve, and without a device.  The status of
+  // the solve is not judged: info.solve_status reports it.
+  struct Sensitivities {
+    std::vector<double> dx, ds, dy, dz;  // [n_p][n], [n_p][m_i], [n_p][m_e], [n_p][m_i]: row q = d(.)/dp_q
+    slpx::SensitivityInfo info;
+  };
+  // every parameter's column: n_p solves
+  Sensitivities sensitivity() {
+    const slpx::Sensitivity::Point at = sensitivity_point();
+    const auto& st = m_sys->structure();
+    const size_t n_p = m_iterate_parameters.size();
+    Sensitivities out;
+    out.dx.resize(n_p * st.n);
+    out.ds.resize(n_p * st.m_i);
+    out.dy.resize(n_p * st.m_e);
+    out.dz.resize(n_p * st.m_i);
+    out.info.solve_status = m_iterate_status;
+    m_sens->jacobian(at, out.dx.data(), out.ds.data(), out.dy.data(), out.dz.data(), out.info);
+    return out;
+  }
+  // the tangent along dp [n_p], one solve: (dx, ds, dy, dz) as an Iterate with mu = 0
+  Iterate sensitivity_jvp(std::span<const double> dp, slpx::SensitivityInfo* info = nullptr) {
+    const slpx::Sensitivity::Point at = sensitivity_point();
+    if (dp.size() != m_iterate_parameters.size()) throw std::runtime_error("sensitivity_jvp: wrong number of values in dp");
+    const auto& st = m_sys->structure();
+    Iterate d;
+    d.x.resize(st.n);
+    d.s.resize(st.m_i);
+    d.y.resize(st.m_e);
+    d.z.resize(st.m_i);
+    slpx::SensitivityInfo local;
+    local.solve_status = m_iterate_status;
+    m_sens->jvp(at, dp.data(), d.x.data(), d.s.data(), d.y.data(), d.z.data(), local);
+    if (info) *info = local;
+    return d;
+  }
+  // (dx/dp)^T vx [n_p] for a cotangent vx [n] on x, one solve whatever n_p
+  std::vector<double> sensitivity_vjp(std::span<const double> vx, slpx::SensitivityInfo* info = nullptr) {
+    const slpx::Sensitivity::Point at = sensitivity_point();
+    if (vx.size() != static_cast<size_t>(m_sys->structure().n)) throw std::runtime_error("sensitivity_vjp: wrong number of values in vx");
+    std::vector<double> grad(m_iterate_parameters.size());
+    slpx::SensitivityInfo local;
+    local.solve_status = m_iterate_status;
+    m_sens->vjp(at, vx.data(), grad.data(), local);
+    if (info) *info = local;
+    return grad;
+  }
+  // M [n_p][n + m_e + m_i]: per parameter r_x = d(grad_x L)/dp_q, r_e = dc_e/dp_q, r_i = dc_i/dp_q at the iterate
+  std::vector<double> sensitivity_rhs() {
+    const slpx::Sensitivity::Point at = sensitivity_point();
+    const auto& st = m_sys->structure();
+    std::vector<double> M(m_iterate_parameters.size() * static_cast<size_t>(st.n + st.m_e + st.m_i));
+    m_sens->unreduced(at, M.data());
+    return M;
+  }
+  // Somebody else is about to use the problem's system (a caller's handle on it): the next sensitivity call evaluates
+  // and factors again.
+  void sensitivity_forget() {
+    if (m_sens) m_sens->forget();
+  }
+
  private:
+  // the checks every sensitivity call makes, and where it differentiates
+  slpx::Sensitivity::Point sensitivity_point() {
+    if (!m_has_iterate) throw std::runtime_error("sensitivity: the problem has not been solved");
+    if (!m_sys) throw std::runtime_error("sensitivity: the model was changed since the solve that produced the iterate");
+    const std::vector<NodeId> nodes = m_sys->structure().parameter_nodes();
+    if (nodes.empty()) throw std::runtime_error("sensitivity: the model reaches no parameter");
+    auto& g = detail::G();
+    for (size_t j = 0; j < nodes.size(); ++j)
+      if (j >= m_iterate_parameters.size() || g.val[nodes[j]] != m_iterate_parameters[j])
+        throw std::runtime_error("sensitivity: the parameters were changed since the solve that produced the iterate");
+    if (!m_sys->has_device()) throw std::runtime_error("sensitivity: no HIP device");
+    if (!m_sens) m_sens = std::make_unique<slpx::Sensitivity>(*m_sys, m_f ? m_f->expr : slpx::kNull);
+    m_sens_iterate = iterate();
+    return slpx::Sensitivity::Point{&m_sens_iterate.x, &m_sens_iterate.s, &m_sens_iterate.y, &m_sens_iterate.z, m_sens_iterate.mu,
+                                    &m_iterate_parameters, &m_scales};
+  }
+  void remember_iterate_for_sensitivity(ExitStatus status) {
+    m_iterate_status = static_cast<int>(status);
+    m_iterate_parameters.clear();
+    auto& g = detail::G();
+    for (NodeId node : m_sys->structure().parameter_nodes()) m_iterate_parameters.push_back(g.val[node]);
+  }
+
   ExitStatus solve_from(const Options& options, bool spy, const slpx::WarmStart* warm) {
     // (nothing given beside x: the cold start, as in a batch)
     if (warm && warm->s.empty() && warm->y.empty() && warm->z.empty() && warm->mu <= 0.0) warm = nullptr;
     m_has_iterate = false;
+    sensitivity_forget();
     m_warm_result = slpx::WarmStartResult{};
     auto& g = detail::G();
     std::vector<double> x(m_decision_variables.size());
@@ -293,6 +384,7 @@ class ProblemF64 {
     for (size_t i = 0; i < x.size(); ++i) g.val[m_decision_variables[i].expr] = x[i];
     m_iterate_x = x;
     m_has_iterate = true;
+    remember_iterate_for_sensitivity(status);
     return status;
   }
 
@@ -318,6 +410,7 @@ class ProblemF64 {
     if (batch <= 0) throw std::runtime_error("solve_batch: batch must be positive");
     if (x0 == nullptr) throw std::runtime_error("solve_batch: x0 is null");
     if (has_callbacks()) throw std::runtime_error("solve_batch: the problem has callbacks registered");
+    sensitivity_forget();  // (restoration hand-offs run on the batch-1 system)
     auto& g = detail::G();
     const size_t B = static_cast<size_t>(batch), n = m_decision_variables.size(), m_e = m_equality_constraints.size(),
                  m_i = m_inequality_constraints.size();
@@ -428,6 +521,7 @@ class ProblemF64 {
   ExitStatus restoration_steps(const Options& options, std::vector<double>& x, std::vector<double>& s,
                                std::vector<double>& y, std::vector<double>& z, double mu, int steps) {
     auto& g = detail::G();
+    sensitivity_forget();
     compile();
     std::vector<double> x0(m_decision_variables.size());
     for (size_t i = 0; i < x0.size(); ++i) x0[i] = g.val[m_decision_variables[i].expr];
@@ -462,6 +556,7 @@ class ProblemF64 {
                                                   const std::vector<double>& mu, int steps, slpx::BatchRestorationStats& stats) {
     if (batch <= 0) throw std::runtime_error("restoration_steps_batch: batch must be positive");
     if (has_callbacks()) throw std::runtime_error("restoration_steps_batch: the problem has callbacks registered");
+    sensitivity_forget();
     auto& g = detail::G();
     compile();
     const auto& st = m_sys->structure();
@@ -641,6 +736,7 @@ class ProblemF64 {
   }
 
   void invalidate() {
+    m_sens.reset();  // (it refers to m_sys)
     m_batch_sys.clear();
     m_sys.reset();
     m_param_snapshot.clear();
@@ -728,6 +824,12 @@ class ProblemF64 {
   std::vector<double> m_iterate_x;
   slpx::WarmStartResult m_warm_result;
   bool m_has_iterate = false;
+  // sensitivities: the extended system and its plan (made by the first call, dropped with m_sys), the parameters'
+  // values and the status of the solve the iterate came from, and the iterate as a sensitivity call handed it down
+  std::unique_ptr<slpx::Sensitivity> m_sens;
+  std::vector<double> m_iterate_parameters;
+  int m_iterate_status = 0;
+  Iterate m_sens_iterate;
   SolveReport m_report;
 };
 

@@ -22,7 +22,7 @@ from sleipnir_amd.autodiff import (EqualityConstraints, ExpressionType, Inequali
 
 __all__ = ["ExitStatus", "Problem", "OCP", "DynamicsType", "TimestepMethod", "TranscriptionMethod",
            "EqualityConstraints", "InequalityConstraints", "IterationInfo", "bounds", "multistart",
-           "Iterate", "BatchIterate", "BatchResult"]
+           "Iterate", "BatchIterate", "BatchResult", "Sensitivity"]
 
 
 class ExitStatus(enum.IntEnum):
@@ -109,6 +109,30 @@ class Iterate:
     def _blocks(self):
         return {k: getattr(self, k) for k in ("s", "y", "z", "mu") if getattr(self, k) is not None}
 
+    def __add__(self, delta):
+        """iterate + delta, block by block (a block absent on either side stays this side's): the tangent predictor
+        problem.iterate() + problem.sensitivity_jvp(dp)."""
+        if not isinstance(delta, Iterate):
+            return NotImplemented
+
+        def add(a, b):
+            return a if b is None else b if a is None else np.asarray(a, dtype=np.float64) + np.asarray(b, dtype=np.float64)
+
+        mu = self.mu if not delta.mu else delta.mu if self.mu is None else self.mu + delta.mu
+        return type(self)(x=add(self.x, delta.x), s=add(self.s, delta.s), y=add(self.y, delta.y), z=add(self.z, delta.z), mu=mu)
+
+
+@dataclasses.dataclass
+class Sensitivity:
+    """What Problem.sensitivity() returns: the derivatives of the end iterate with respect to the parameters, in the
+    user's units — dx (n_p, n), ds (n_p, m_i), dy (n_p, m_e), dz (n_p, m_i) — and `info`, a dict of
+    slpx_sensitivity_info's members."""
+    dx: np.ndarray
+    ds: np.ndarray
+    dy: np.ndarray
+    dz: np.ndarray
+    info: dict
+
 
 @dataclasses.dataclass
 class BatchIterate(Iterate):
@@ -152,6 +176,7 @@ class Problem:
         self._decision_variables: list[Variable] = []
         self._pattern_cache = None
         self.report = None  # counters and phase times of the last solve() that ran an iteration
+        self.sensitivity_info = None  # slpx_sensitivity_info of the last sensitivity_jvp() / sensitivity_vjp()
 
     # ---- model ----
     def decision_variable(self, rows=None, cols=1):
@@ -296,6 +321,35 @@ class Problem:
                 problem.solve(warm_start=problem.iterate())
         """
         self._p.set_parameters(values)
+
+    # ---- solution sensitivities (include/slpx.h): how iterate() moves with parameters(), in the user's units ----
+    def sensitivity(self) -> "Sensitivity":
+        """The Jacobian of the last solve's end iterate with respect to parameters(): dx (n_p, n), ds (n_p, m_i),
+        dy (n_p, m_e), dz (n_p, m_i), row q the derivative with respect to parameter q, and `info` (what the call did:
+        solves, factorizations, the inertia and regularization of what was factored, the largest backward error, the
+        status of the solve the iterate came from).  n_p solves on one factorization."""
+        r = self._p.sensitivity()
+        return Sensitivity(dx=r["dx"], ds=r["ds"], dy=r["dy"], dz=r["dz"], info=r["info"])
+
+    def sensitivity_jvp(self, dp) -> "Iterate":
+        """The tangent of the end iterate along a parameter change dp (n_p), from one solve: an Iterate-shaped delta
+        with mu = 0.  The predictor of an MPC loop:
+
+            problem.solve()
+            for p_now in measurements:
+                it = problem.iterate() + problem.sensitivity_jvp(p_now - p_last)
+                problem.set_parameters(p_now)
+                problem.solve(warm_start=it)
+        """
+        r = self._p.sensitivity_jvp(dp)
+        self.sensitivity_info = r["info"]
+        return Iterate(x=r["dx"], s=r["ds"], y=r["dy"], z=r["dz"], mu=0.0)
+
+    def sensitivity_vjp(self, v) -> np.ndarray:
+        """(d x*/d p)^T v (n_p) for a cotangent v (n) on x: the gradient of l(x*(p)) with v = dl/dx, from ONE solve
+        whatever n_p."""
+        grad, self.sensitivity_info = self._p.sensitivity_vjp(v)
+        return grad
 
     def restoration_steps_batch(self, x, s, y, z, mu, steps, **kwargs):
         """`steps` iterations of feasibility restoration from each of B iterates (rows of x, s, y, z; mu of length B), in
