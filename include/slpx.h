@@ -364,6 +364,58 @@ int slpx_problem_sensitivity_vjp(slpx_problem* p, const double* vx, double* grad
 /* M[n_p][n + m_e + m_i]: r_x, r_e, r_i per parameter, at the iterate.  Neither factors nor solves. */
 int slpx_problem_sensitivity_rhs(slpx_problem* p, double* M);
 
+/* ---- batched sensitivities ----------------------------------------------------------------
+ * The same derivatives for B iterates at once, instance b with respect to ITS parameter row — additions within ABI
+ * version 6, detected by the symbol's presence.  slpx_problem_solve_batch* leaves no state in the problem, so these are
+ * functions of the rows they are given, everything in the user's units:
+ *     x[B][n], s[B][m_i], y[B][m_e], z[B][m_i], mu[B]   the end iterates, exactly what slpx_problem_solve_batch_warm
+ *                                                       returns (and slpx_problem_get_iterate for one problem)
+ *     params[B][n_p]                                    the parameter rows, the order of slpx_problem_parameters
+ * s, y, z may be NULL where the model has no such rows.  Equations, units and policy are those of the section above:
+ * unit scales, every instance factored from a cleared regularization memory, every right-hand side solved and refined
+ * twice, the componentwise backward error reported.
+ *
+ * status[B] reports each instance instead of an error for the call:
+ *     0  computed
+ *     1  skipped: a NaN or an Inf in its iterate, its parameter row, dp or vx, or an s_j <= 0 with m_i > 0
+ *     2  the KKT system at its iterate could not be factored
+ * Every output row of an instance whose status is not 0 is NaN; the other instances do not notice it (it is left out of
+ * the factorization, the refinement and the error bounds), and their bits depend neither on B nor on their position
+ * nor on their neighbours.  info[B] is per instance: inertia (of a computed instance: what the policy accepts,
+ * (n, m_e, 0), stated as such and not read back from the counters, which are those of the call's LAST factorization
+ * launch), delta, gamma, solves, refine_steps, berr_max;
+ * factorizations is the count of factorization launches of the call (0 for a skipped instance), solve_status is 0 (the
+ * call is not told it), the times are the call's, repeated in every row.
+ *
+ * STATE.  A call runs on the batch system of size B (the one slpx_problem_solve_batch uses) and on an extended system
+ * compiled for that B on the first call (t_compile; kept with the problem).  It changes neither the variables nor the
+ * parameters, neither the scaling nor the regularization memory of the problem's own system, nor a kept single-problem
+ * sensitivity factorization; the batch system has its shared parameter pool and its regularization memory back on
+ * return, so a following slpx_problem_solve_batch* keeps every bit.  The factorization is kept: a call with the same B
+ * and the same bits in every iterate and parameter row reports factorizations = 0, until the next
+ * slpx_problem_solve_batch* or slpx_problem_restoration_steps_batch of that B or a model change.  The Jacobian takes n_p
+ * rounds of solves, round q carrying column q of all B instances; the two products take ONE round.
+ *
+ * ERRORS: -100 + slpx_last_error() for a null problem, B <= 0 or B > 65535 (one grid slice per instance), a NULL
+ * required input, a model that reaches no parameter, and without a HIP device.  Any output, status and info may be
+ * NULL. */
+/* The Jacobians: dx[B][n_p][n], ds[B][n_p][m_i], dy[B][n_p][m_e], dz[B][n_p][m_i]. */
+int slpx_problem_sensitivity_batch(slpx_problem* p, int32_t B, const double* x, const double* s, const double* y, const double* z,
+                                   const double* mu, const double* params, double* dx, double* ds, double* dy, double* dz,
+                                   int32_t* status, slpx_sensitivity_info* info);
+/* Along dp[B][n_p]: dx[B][n], ds[B][m_i], dy[B][m_e], dz[B][m_i] — iterate + these is the warm start of the next batch
+ * with params + dp. */
+int slpx_problem_sensitivity_batch_jvp(slpx_problem* p, int32_t B, const double* x, const double* s, const double* y,
+                                       const double* z, const double* mu, const double* params, const double* dp, double* dx,
+                                       double* ds, double* dy, double* dz, int32_t* status, slpx_sensitivity_info* info);
+/* For cotangents vx[B][n] on x: grad_p[B][n_p]. */
+int slpx_problem_sensitivity_batch_vjp(slpx_problem* p, int32_t B, const double* x, const double* s, const double* y,
+                                       const double* z, const double* mu, const double* params, const double* vx, double* grad_p,
+                                       int32_t* status, slpx_sensitivity_info* info);
+/* M[B][n_p][n + m_e + m_i]: r_x, r_e, r_i per instance and parameter.  Neither factors nor solves. */
+int slpx_problem_sensitivity_batch_rhs(slpx_problem* p, int32_t B, const double* x, const double* s, const double* y,
+                                       const double* z, const double* mu, const double* params, double* M, int32_t* status);
+
 /* ---- compiled Newton system ------------------------------------------------------
  * One problem structure compiled for one GPU, `batch` independent value sets.
  * Replaces, per Newton step:

@@ -216,6 +216,12 @@ def lib() -> ctypes.CDLL:
         sig("slpx_problem_sensitivity_jvp", ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.POINTER(SensitivityInfo))
         sig("slpx_problem_sensitivity_vjp", ctypes.c_int, vp, vp, vp, ctypes.POINTER(SensitivityInfo))
         sig("slpx_problem_sensitivity_rhs", ctypes.c_int, vp, vp)
+    if hasattr(L, "slpx_problem_sensitivity_batch"):
+        rows = (vp, i32, vp, vp, vp, vp, vp, vp)  # problem, B, x, s, y, z, mu, params
+        sig("slpx_problem_sensitivity_batch", ctypes.c_int, *rows, vp, vp, vp, vp, vp, vp)
+        sig("slpx_problem_sensitivity_batch_jvp", ctypes.c_int, *rows, vp, vp, vp, vp, vp, vp, vp)
+        sig("slpx_problem_sensitivity_batch_vjp", ctypes.c_int, *rows, vp, vp, vp, vp)
+        sig("slpx_problem_sensitivity_batch_rhs", ctypes.c_int, *rows, vp, vp)
     _lib = L
     return L
 
@@ -408,6 +414,99 @@ class Problem:
         if fn(self._h, M.ctypes.data if M.size else None) != 0:
             raise SlpxError(lib().slpx_last_error().decode())
         return M
+
+    # ---- batched sensitivities (include/slpx.h): functions of the rows they are given, not of the problem's state ----
+    def _batch_rows(self, iterate, parameters, who):
+        """(B, n_p, [x, s, y, z, mu, params] as contiguous arrays, their pointers): `iterate` is anything with x, s, y, z,
+        mu rows — the dict solve_batch(..., warm_start={}) returns as it is, or an object with those attributes."""
+        get = iterate.get if hasattr(iterate, "get") else lambda k: getattr(iterate, k, None)
+        n, me, mi = self.dims
+        n_p = max(0, lib().slpx_problem_parameters(self._h, None, 0))
+        x = get("x")
+        if x is None:
+            raise ValueError(f"{who}: the iterate has no x")
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+        if x.ndim != 2 or x.shape[1] != n:
+            raise ValueError(f"{who}: x must have shape (B, {n})")
+        B = x.shape[0]
+        hold = [x]
+        for k, count in (("s", mi), ("y", me), ("z", mi), ("mu", 1)):
+            v = get(k)
+            if v is None:
+                if count:
+                    raise ValueError(f"{who}: the iterate has no {k}")
+                v = np.zeros((B, 0))
+            v = np.asarray(v, dtype=np.float64)
+            if v.size != B * count or (v.ndim == 2 and v.shape != (B, count)):
+                raise ValueError(f"{who}: {k} must have shape ({B}, {count})")
+            hold.append(np.ascontiguousarray(v.reshape(B, count)))
+        rows = np.ascontiguousarray(np.asarray(parameters, dtype=np.float64))
+        if rows.ndim != 2 or rows.shape != (B, n_p):
+            raise ValueError(f"{who}: parameters must have shape ({B}, {n_p}): one row per instance")
+        hold.append(rows)
+        return B, n_p, hold, [a.ctypes.data if a.size else None for a in hold]
+
+    def _batch_info(self, info):
+        return [self._sensitivity_info(i) for i in info]
+
+    def sensitivity_batch(self, iterate, parameters):
+        """The Jacobians of B end iterates with respect to their parameter rows (slpx_problem_sensitivity_batch):
+        dict(dx (B, n_p, n), ds (B, n_p, m_i), dy (B, n_p, m_e), dz (B, n_p, m_i), status (B), info: list of B dicts).
+        status: 0 computed, 1 skipped (not finite, or s <= 0), 2 not factored; rows of the latter two are NaN."""
+        fn = self._sensitivity_entry("slpx_problem_sensitivity_batch")
+        B, n_p, hold, ptrs = self._batch_rows(iterate, parameters, "sensitivity_batch")
+        n, me, mi = self.dims
+        out = {"dx": np.zeros((B, n_p, n)), "ds": np.zeros((B, n_p, mi)), "dy": np.zeros((B, n_p, me)), "dz": np.zeros((B, n_p, mi)),
+               "status": np.zeros(B, dtype=np.int32)}
+        info = (SensitivityInfo * max(1, B))()
+        if fn(self._h, B, *ptrs, *(out[k].ctypes.data if out[k].size else None for k in ("dx", "ds", "dy", "dz", "status")), info) != 0:
+            raise SlpxError(lib().slpx_last_error().decode())
+        out["info"] = self._batch_info(info[:B])
+        return out
+
+    def sensitivity_batch_jvp(self, iterate, parameters, dp):
+        """Along dp (B, n_p), one round of solves (slpx_problem_sensitivity_batch_jvp): dict(dx (B, n), ds (B, m_i),
+        dy (B, m_e), dz (B, m_i), status, info).  iterate + these is the warm start of the batch with parameters + dp."""
+        fn = self._sensitivity_entry("slpx_problem_sensitivity_batch_jvp")
+        B, n_p, hold, ptrs = self._batch_rows(iterate, parameters, "sensitivity_batch_jvp")
+        dp = np.ascontiguousarray(np.asarray(dp, dtype=np.float64))
+        if dp.shape != (B, n_p):
+            raise ValueError(f"sensitivity_batch_jvp: dp must have shape ({B}, {n_p})")
+        n, me, mi = self.dims
+        out = {"dx": np.zeros((B, n)), "ds": np.zeros((B, mi)), "dy": np.zeros((B, me)), "dz": np.zeros((B, mi)),
+               "status": np.zeros(B, dtype=np.int32)}
+        info = (SensitivityInfo * max(1, B))()
+        if fn(self._h, B, *ptrs, dp.ctypes.data if dp.size else None,
+              *(out[k].ctypes.data if out[k].size else None for k in ("dx", "ds", "dy", "dz", "status")), info) != 0:
+            raise SlpxError(lib().slpx_last_error().decode())
+        out["info"] = self._batch_info(info[:B])
+        return out
+
+    def sensitivity_batch_vjp(self, iterate, parameters, vx):
+        """(dx/dp)^T vx per instance for cotangents vx (B, n), one round of solves (slpx_problem_sensitivity_batch_vjp):
+        dict(grad (B, n_p), status, info)."""
+        fn = self._sensitivity_entry("slpx_problem_sensitivity_batch_vjp")
+        B, n_p, hold, ptrs = self._batch_rows(iterate, parameters, "sensitivity_batch_vjp")
+        vx = np.ascontiguousarray(np.asarray(vx, dtype=np.float64))
+        if vx.shape != (B, self.dims[0]):
+            raise ValueError(f"sensitivity_batch_vjp: vx must have shape ({B}, {self.dims[0]})")
+        out = {"grad": np.zeros((B, n_p)), "status": np.zeros(B, dtype=np.int32)}
+        info = (SensitivityInfo * max(1, B))()
+        if fn(self._h, B, *ptrs, vx.ctypes.data if vx.size else None, out["grad"].ctypes.data if out["grad"].size else None,
+              out["status"].ctypes.data if B else None, info) != 0:
+            raise SlpxError(lib().slpx_last_error().decode())
+        out["info"] = self._batch_info(info[:B])
+        return out
+
+    def sensitivity_batch_rhs(self, iterate, parameters):
+        """M (B, n_p, n + m_e + m_i): per instance and parameter r_x, r_e, r_i at its iterate; neither factors nor solves
+        (slpx_problem_sensitivity_batch_rhs): dict(M, status)."""
+        fn = self._sensitivity_entry("slpx_problem_sensitivity_batch_rhs")
+        B, n_p, hold, ptrs = self._batch_rows(iterate, parameters, "sensitivity_batch_rhs")
+        out = {"M": np.zeros((B, n_p, sum(self.dims))), "status": np.zeros(B, dtype=np.int32)}
+        if fn(self._h, B, *ptrs, out["M"].ctypes.data if out["M"].size else None, out["status"].ctypes.data if B else None) != 0:
+            raise SlpxError(lib().slpx_last_error().decode())
+        return out
 
     RESTORATION_MODES = {"handoff": 0, "lockstep": 1}
 

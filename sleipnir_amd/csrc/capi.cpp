@@ -288,6 +288,87 @@ int slpx_problem_sensitivity_rhs(slpx_problem* p, double* M) {
 }
 
 namespace {
+// what the four batched entry points check alike, and their rows as the problem takes them
+struct BatchSensitivityArgs {
+  slp::ProblemF64::BatchIterate it;
+  std::span<const double> params;
+  size_t B = 0, n = 0, m_e = 0, m_i = 0, n_p = 0;
+};
+void batch_sensitivity_args(BatchSensitivityArgs& a, slpx_problem* p, int32_t B, const double* x, const double* s, const double* y,
+                            const double* z, const double* mu, const double* params, const char* who) {
+  const std::string name(who);
+  if (p == nullptr) throw std::runtime_error(name + ": null problem");
+  if (B <= 0 || B > 65535) throw std::runtime_error(name + ": B must be in 1 .. 65535 (one grid slice per instance)");
+  a.B = static_cast<size_t>(B);
+  a.n = p->problem.decision_variables().size();
+  a.m_e = p->problem.equality_constraints().size();
+  a.m_i = p->problem.inequality_constraints().size();
+  if (x == nullptr || mu == nullptr || params == nullptr || (a.m_i && (s == nullptr || z == nullptr)) || (a.m_e && y == nullptr))
+    throw std::runtime_error(name + ": a required input is null (x, mu, params; s, y, z where the model has such rows)");
+  a.n_p = slpx::problem_parameter_nodes(*p, nullptr).size();  // (from the host graph: no device needed)
+  if (a.n_p == 0) throw std::runtime_error(name + ": the model reaches no parameter");
+  if (slpx_device_count() < 1) throw std::runtime_error(name + ": no HIP device");
+  a.it = slp::ProblemF64::BatchIterate{std::span<const double>(x, a.B * a.n), std::span<const double>(s, a.m_i ? a.B * a.m_i : 0),
+                                       std::span<const double>(y, a.m_e ? a.B * a.m_e : 0),
+                                       std::span<const double>(z, a.m_i ? a.B * a.m_i : 0), std::span<const double>(mu, a.B)};
+  a.params = std::span<const double>(params, a.B * a.n_p);
+}
+void batch_sensitivity_out(const slp::ProblemF64::BatchSensitivities& r, double* dx, double* ds, double* dy, double* dz, int32_t* status,
+                           slpx_sensitivity_info* info) {
+  if (dx) std::copy(r.dx.begin(), r.dx.end(), dx);
+  if (ds) std::copy(r.ds.begin(), r.ds.end(), ds);
+  if (dy) std::copy(r.dy.begin(), r.dy.end(), dy);
+  if (dz) std::copy(r.dz.begin(), r.dz.end(), dz);
+  if (status) std::copy(r.status.begin(), r.status.end(), status);
+  if (info)
+    for (size_t b = 0; b < r.info.size(); ++b) sensitivity_info_out(r.info[b], info + b);
+}
+}  // namespace
+
+int slpx_problem_sensitivity_batch(slpx_problem* p, int32_t B, const double* x, const double* s, const double* y, const double* z,
+                                   const double* mu, const double* params, double* dx, double* ds, double* dy, double* dz, int32_t* status,
+                                   slpx_sensitivity_info* info) {
+  return guard([&] {
+    BatchSensitivityArgs a;
+    batch_sensitivity_args(a, p, B, x, s, y, z, mu, params, "slpx_problem_sensitivity_batch");
+    batch_sensitivity_out(p->problem.sensitivity_batch(B, a.it, a.params), dx, ds, dy, dz, status, info);
+  });
+}
+int slpx_problem_sensitivity_batch_jvp(slpx_problem* p, int32_t B, const double* x, const double* s, const double* y, const double* z,
+                                       const double* mu, const double* params, const double* dp, double* dx, double* ds, double* dy,
+                                       double* dz, int32_t* status, slpx_sensitivity_info* info) {
+  return guard([&] {
+    BatchSensitivityArgs a;
+    batch_sensitivity_args(a, p, B, x, s, y, z, mu, params, "slpx_problem_sensitivity_batch_jvp");
+    if (dp == nullptr) throw std::runtime_error("slpx_problem_sensitivity_batch_jvp: dp is null");
+    batch_sensitivity_out(p->problem.sensitivity_batch_jvp(B, a.it, a.params, std::span<const double>(dp, a.B * a.n_p)), dx, ds, dy, dz,
+                          status, info);
+  });
+}
+int slpx_problem_sensitivity_batch_vjp(slpx_problem* p, int32_t B, const double* x, const double* s, const double* y, const double* z,
+                                       const double* mu, const double* params, const double* vx, double* grad_p, int32_t* status,
+                                       slpx_sensitivity_info* info) {
+  return guard([&] {
+    BatchSensitivityArgs a;
+    batch_sensitivity_args(a, p, B, x, s, y, z, mu, params, "slpx_problem_sensitivity_batch_vjp");
+    if (vx == nullptr) throw std::runtime_error("slpx_problem_sensitivity_batch_vjp: vx is null");
+    const auto r = p->problem.sensitivity_batch_vjp(B, a.it, a.params, std::span<const double>(vx, a.B * a.n));
+    if (grad_p) std::copy(r.grad.begin(), r.grad.end(), grad_p);
+    batch_sensitivity_out(r, nullptr, nullptr, nullptr, nullptr, status, info);
+  });
+}
+int slpx_problem_sensitivity_batch_rhs(slpx_problem* p, int32_t B, const double* x, const double* s, const double* y, const double* z,
+                                       const double* mu, const double* params, double* M, int32_t* status) {
+  return guard([&] {
+    BatchSensitivityArgs a;
+    batch_sensitivity_args(a, p, B, x, s, y, z, mu, params, "slpx_problem_sensitivity_batch_rhs");
+    const auto r = p->problem.sensitivity_batch_rhs(B, a.it, a.params);
+    if (M) std::copy(r.M.begin(), r.M.end(), M);
+    if (status) std::copy(r.status.begin(), r.status.end(), status);
+  });
+}
+
+namespace {
 int solve_batch_impl(slpx_problem* p, int32_t batch, const double* x0, const double* params, const slpx::BatchWarmStart* warm,
                      const slpx_options* o, int32_t* status, double* x, double* sv, double* y, double* z, double* mu,
                      double* cost, int32_t* iterations, int32_t* restorations, int32_t* repaired, slpx_report* report) {

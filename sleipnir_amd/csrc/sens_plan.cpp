@@ -116,4 +116,25 @@ void sens_host_vjp(const SensPlan& p, const double* R, const double* w, double* 
   }
 }
 
+void sens_classify_instances(int B, int n, int m_e, int m_i, int n_p, const double* x, const double* s, const double* y,
+                             const double* z, const double* mu, const double* params, const double* extra, int n_extra,
+                             int32_t* status) {
+  // (x - x is 0 for a finite x and NaN for a NaN or an Inf)
+  const auto finite_row = [](const double* a, int b, int count) {
+    if (a == nullptr) return true;
+    const double* row = a + static_cast<int64_t>(b) * count;
+    for (int i = 0; i < count; ++i)
+      if (!(row[i] - row[i] == 0.0)) return false;
+    return true;
+  };
+  for (int b = 0; b < B; ++b) {
+    bool ok = finite_row(x, b, n) && finite_row(s, b, m_i) && finite_row(y, b, m_e) && finite_row(z, b, m_i) && finite_row(mu, b, 1) &&
+              finite_row(params, b, n_p) && finite_row(extra, b, n_extra);
+    if (ok && s != nullptr)
+      for (int j = 0; j < m_i; ++j)
+        if (!(s[static_cast<int64_t>(b) * m_i + j] > 0.0)) ok = false;
+    status[b] = ok ? kSensComputed : kSensSkipped;
+  }
+}
+
 }  // namespace slpx

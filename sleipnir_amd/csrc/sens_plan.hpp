@@ -62,4 +62,16 @@ void sens_host_expand(const SensPlan& p, const double* V, const double* s, const
 // grad [n_p]: grad[q] = wᵀ R[:, q], w [dim]
 void sens_host_vjp(const SensPlan& p, const double* R, const double* w, double* grad);
 
+// ---- batched calls: which instances are differentiated at all (include/slpx.h: batched sensitivities) ----
+// The per-instance outcome of a batched sensitivity call (slpx.h: status[B]).
+constexpr int32_t kSensComputed = 0;     // differentiated
+constexpr int32_t kSensSkipped = 1;      // a NaN or an Inf among its inputs, or an s_j <= 0 (Sigma = z / s would not be finite)
+constexpr int32_t kSensNotFactored = 2;  // the KKT system at its iterate could not be factored (set by the driver)
+// status[b] = kSensSkipped where a row of instance b — x [B][n], s [B][m_i], y [B][m_e], z [B][m_i], mu [B],
+// params [B][n_p], extra [B][n_extra] (dp or vx; null: none) — holds a value that is not finite, or s an entry <= 0;
+// kSensComputed otherwise.  An array whose row has no entries may be null.  A pure function: no device, no model.
+void sens_classify_instances(int B, int n, int m_e, int m_i, int n_p, const double* x, const double* s, const double* y,
+                             const double* z, const double* mu, const double* params, const double* extra, int n_extra,
+                             int32_t* status);
+
 }  // namespace slpx

@@ -1,89 +1,115 @@
-// The kernels of the solution sensitivities and their driver (sensitivity.hpp).  Opt-in: nothing on the path of a
-// solve comes here.
+// The kernels of the solution sensitivities and their drivers (sensitivity.hpp): one problem (Sensitivity) and B
+// instances at once (BatchSensitivity).  Opt-in: nothing on the path of a solve comes here.
 //
 // Four kernels, all row-local gathers — one lane computes one output entry with the row formulas of sens_rows.h, the
-// bodies the host executor (sens_plan.cpp) runs — so an entry's bits do not depend on the launch geometry:
-//   sens_rhs_kernel      V' (extended sweep), V, s, z -> every column of M and of R in one launch, grid (rows, n_p)
+// bodies the host executor (sens_plan.cpp) runs — so an entry's bits do not depend on the launch geometry, on the batch
+// size, on the instance's position or on its neighbours:
+//   sens_rhs_kernel      V' (extended sweep), V, s, z -> every column of M and of R in one launch
 //   sens_combine_kernel  R dp and (dc_i/dp) dp for the jvp
-//   sens_expand_kernel   [dx; -dy] -> dx, ds = A_i dx + r_i, dy, dz = -Sigma ds, grid (entries, columns)
+//   sens_expand_kernel   [dx; -dy] -> dx, ds = A_i dx + r_i, dy, dz = -Sigma ds, straight into the caller's layout
 //   sens_vjp_kernel      w^T R[:, q], one workgroup per parameter, lanes and fold in the fixed order of sens_rows.h
-// Plain vector loads and stores only.
+// THE GRID.  blockIdx.y is the instance (at most 65535 of them: one grid slice each) and every buffer has an instance
+// stride, 0 or unused for one problem.  blockIdx.x runs over the entries of ONE instance with the columns folded in —
+// (parameter, row) for rhs and expand.  A batched launch uses workgroups of one wave (kSensBatchThreads): the models
+// the batch serves have n_p * dimM of a few dozen to a few thousand, so a 256-lane workgroup per (instance, column)
+// would be mostly idle lanes, and it is the instance axis that fills the machine.  The single-slice launches of one
+// problem keep 256 lanes (kSensThreads), the geometry profiles/sensitivity.txt was measured with; the kernels take the
+// workgroup size from the launch.  Plain vector loads and stores only; no LDS beyond the fold of the vjp.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstring>
+#include <limits>
 
 #include "sens_rows.h"
 #include "sensitivity.hpp"
 
 namespace slpx {
 
-constexpr int kSensThreads = 256;
+constexpr int kSensThreads = 256;      // one problem
+constexpr int kSensBatchThreads = 64;  // B instances: one wave
 
-__global__ __launch_bounds__(kSensThreads) void sens_rhs_kernel(SensDev d, const double* __restrict__ Vx, const double* __restrict__ V,
+// entry e = q * dimM + row of instance blockIdx.y
+__global__ __launch_bounds__(kSensThreads) void sens_rhs_kernel(SensDev d, const double* __restrict__ Vx, long long Vx_stride,
+                                                               const double* __restrict__ V, long long V_stride,
                                                                const double* __restrict__ s, const double* __restrict__ z,
-                                                               double* __restrict__ M, double* __restrict__ R) {
-  const int row = static_cast<int>(blockIdx.x) * kSensThreads + static_cast<int>(threadIdx.x);
-  const int q = static_cast<int>(blockIdx.y);
-  if (row >= d.dimM || q >= d.n_p) return;
-  const int64_t k = static_cast<int64_t>(q) * d.dimM + row;
-  const double m = sens_m_entry(d.m_ptr, d.m_src, Vx, k);
-  M[k] = m;
+                                                               long long sz_stride, double* __restrict__ M, double* __restrict__ R) {
+  const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (e >= static_cast<int64_t>(d.n_p) * d.dimM) return;
+  const int64_t b = blockIdx.y;
+  const int q = static_cast<int>(e / d.dimM), row = static_cast<int>(e - static_cast<int64_t>(q) * d.dimM);
+  Vx += b * Vx_stride;
+  const double m = sens_m_entry(d.m_ptr, d.m_src, Vx, e);
+  M[b * d.n_p * d.dimM + e] = m;
   if (row < d.dim)
-    R[static_cast<int64_t>(q) * d.dim + row] =
-        sens_reduced_entry(d.n, d.m_e, d.dimM, d.m_ptr, d.m_src, d.red_ptr, d.red_src, d.red_row, Vx, V, s, z, q, row, m);
+    R[b * d.n_p * d.dim + static_cast<int64_t>(q) * d.dim + row] =
+        sens_reduced_entry(d.n, d.m_e, d.dimM, d.m_ptr, d.m_src, d.red_ptr, d.red_src, d.red_row, Vx, V + b * V_stride, s + b * sz_stride,
+                           z + b * sz_stride, q, row, m);
 }
 
+// instance blockIdx.y: M [n_p][dimM], R [n_p][dim], dp [n_p] -> rhs [dim], r_i [m_i], every one dense per instance
 __global__ __launch_bounds__(kSensThreads) void sens_combine_kernel(SensDev d, const double* __restrict__ M, const double* __restrict__ R,
                                                                    const double* __restrict__ dp, double* __restrict__ rhs,
                                                                    double* __restrict__ r_i) {
-  const int row = static_cast<int>(blockIdx.x) * kSensThreads + static_cast<int>(threadIdx.x);
+  const int row = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
   if (row >= d.dimM) return;
-  if (row < d.dim) rhs[row] = sens_combine_entry(d.n_p, R, d.dim, 0, row, dp);
-  else r_i[row - d.dim] = sens_combine_entry(d.n_p, M, d.dimM, d.dim, row - d.dim, dp);
+  const int64_t b = blockIdx.y;
+  M += b * d.n_p * d.dimM;
+  R += b * d.n_p * d.dim;
+  dp += b * d.n_p;
+  if (row < d.dim) rhs[b * d.dim + row] = sens_combine_entry(d.n_p, R, d.dim, 0, row, dp);
+  else r_i[b * d.m_i + row - d.dim] = sens_combine_entry(d.n_p, M, d.dimM, d.dim, row - d.dim, dp);
 }
 
-// column c: sol + c * dim -> out + c * dimOut, laid out [dx (n) | ds (m_i) | dy (m_e) | dz (m_i)]; r_i of the column at
-// r_i + c * r_i_stride
-__global__ __launch_bounds__(kSensThreads) void sens_expand_kernel(SensDev d, int columns, const double* __restrict__ V,
+// entry e = c * dimM + i of instance b = blockIdx.y: column c of its `columns` solutions, sol + (b * columns + c) * dim,
+// into row b * columns + c of dx [.][n], ds [.][m_i], dy [.][m_e], dz [.][m_i]; r_i of the column at
+// r_i + b * r_i_instance + c * r_i_column
+__global__ __launch_bounds__(kSensThreads) void sens_expand_kernel(SensDev d, int columns, const double* __restrict__ V, long long V_stride,
                                                                   const double* __restrict__ s, const double* __restrict__ z,
-                                                                  const double* __restrict__ sol, const double* __restrict__ r_i,
-                                                                  long long r_i_stride, double* __restrict__ out) {
-  const int e = static_cast<int>(blockIdx.x) * kSensThreads + static_cast<int>(threadIdx.x);
-  const int c = static_cast<int>(blockIdx.y);
-  if (e >= d.dimM || c >= columns) return;
-  const double* p = sol + static_cast<int64_t>(c) * d.dim;
-  double* o = out + static_cast<int64_t>(c) * (d.dimM + d.m_i);
-  if (e < d.n) {
-    o[e] = p[e];
-  } else if (e < d.dim) {
-    o[d.n + d.m_i + (e - d.n)] = -p[e];
+                                                                  long long sz_stride, const double* __restrict__ sol,
+                                                                  const double* __restrict__ r_i, long long r_i_column,
+                                                                  long long r_i_instance, double* __restrict__ dx, double* __restrict__ ds,
+                                                                  double* __restrict__ dy, double* __restrict__ dz) {
+  const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (e >= static_cast<int64_t>(columns) * d.dimM) return;
+  const int64_t b = blockIdx.y;
+  const int c = static_cast<int>(e / d.dimM), i = static_cast<int>(e - static_cast<int64_t>(c) * d.dimM);
+  const int64_t out = b * columns + c;
+  const double* p = sol + out * d.dim;
+  if (i < d.n) {
+    dx[out * d.n + i] = p[i];
+  } else if (i < d.dim) {
+    dy[out * d.m_e + (i - d.n)] = -p[i];
   } else {
-    const int j = e - d.dim;
-    const double ds = sens_ds_entry(d.ai_rowptr, d.ai_col, d.ai_src, V, p, r_i + static_cast<int64_t>(c) * r_i_stride, j);
-    o[d.n + j] = ds;
-    o[d.n + d.m_i + d.m_e + j] = sens_dz_entry(s[j], z[j], ds);
+    const int j = i - d.dim;
+    const double v = sens_ds_entry(d.ai_rowptr, d.ai_col, d.ai_src, V + b * V_stride, p, r_i + b * r_i_instance + c * r_i_column, j);
+    ds[out * d.m_i + j] = v;
+    dz[out * d.m_i + j] = sens_dz_entry(s[b * sz_stride + j], z[b * sz_stride + j], v);
   }
 }
 
+// workgroup (q, b): grad [b][q] = w[b]^T R[b][:, q]
 __global__ __launch_bounds__(kSensVjpThreads) void sens_vjp_kernel(SensDev d, const double* __restrict__ R, const double* __restrict__ w,
                                                                   double* __restrict__ grad) {
   __shared__ double part[kSensVjpThreads];
   const int q = static_cast<int>(blockIdx.x);
+  const int64_t b = blockIdx.y;
   const int t = static_cast<int>(threadIdx.x);
-  part[t] = sens_vjp_partial(d.dim, R + static_cast<int64_t>(q) * d.dim, w, t);
+  part[t] = sens_vjp_partial(d.dim, R + (b * d.n_p + q) * d.dim, w + b * d.dim, t);
   __syncthreads();
   for (int width = kSensVjpThreads / 2; width > 0; width >>= 1) {
     if (t < width) part[t] = part[t] + part[t + width];
     __syncthreads();
   }
-  if (t == 0) grad[q] = part[0];
+  if (t == 0) grad[b * d.n_p + q] = part[0];
 }
 
 namespace {
 using clk = std::chrono::steady_clock;
 double seconds_since(clk::time_point t0) { return std::chrono::duration<double>(clk::now() - t0).count(); }
-int blocks_for(int count) { return std::max(1, (count + kSensThreads - 1) / kSensThreads); }
+unsigned blocks_for(int64_t count, int threads = kSensThreads) { return static_cast<unsigned>(std::max<int64_t>(1, (count + threads - 1) / threads)); }
 }  // namespace
 
 Sensitivity::Sensitivity(NewtonSystem& model, NodeId f) : m_model(model) {
@@ -92,7 +118,6 @@ Sensitivity::Sensitivity(NewtonSystem& model, NodeId f) : m_model(model) {
   if (model.batch() != 1) throw std::runtime_error("slpx: sensitivity: the model's system must be a single problem");
   const std::vector<NodeId> params = model.structure().parameter_nodes();
   if (params.empty()) throw std::runtime_error("slpx: sensitivity: the model reaches no parameter");
-  if (params.size() > 65535) throw std::runtime_error("slpx: sensitivity: more than 65535 parameters (one grid row each)");
   // x' = [x ; p]: the parameters behind the decision variables, in the order of every parameter vector
   std::vector<NodeId> xp = model.x_nodes();
   xp.insert(xp.end(), params.begin(), params.end());
@@ -121,7 +146,10 @@ Sensitivity::Sensitivity(NewtonSystem& model, NodeId f) : m_model(model) {
   m_rhs1.alloc(static_cast<size_t>(p.dim));
   m_ri1.alloc(static_cast<size_t>(std::max(1, p.m_i)));
   m_sol.alloc(n_p * p.dim);
-  m_out.alloc(n_p * (static_cast<size_t>(p.dimM) + p.m_i));
+  m_dx.alloc(std::max<size_t>(1, n_p * p.n));
+  m_ds.alloc(std::max<size_t>(1, n_p * p.m_i));
+  m_dy.alloc(std::max<size_t>(1, n_p * p.m_e));
+  m_dz.alloc(std::max<size_t>(1, n_p * p.m_i));
   m_grad.alloc(n_p);
   m_compile_seconds = seconds_since(t0);
 }
@@ -168,8 +196,8 @@ void Sensitivity::evaluate(const Point& at) {
     SLPX_HIP_CHECK(hipMemcpyAsync(m_s.p, dev.d_s(), m_i * sizeof(double), hipMemcpyDeviceToDevice, st));
     SLPX_HIP_CHECK(hipMemcpyAsync(m_z.p, dev.d_z(), m_i * sizeof(double), hipMemcpyDeviceToDevice, st));
   }
-  hipLaunchKernelGGL(sens_rhs_kernel, dim3(blocks_for(p.dimM), p.n_p), dim3(kSensThreads), 0, st, view(), ext.d_V(), m_V.p, m_s.p, m_z.p,
-                     m_M.p, m_R.p);
+  hipLaunchKernelGGL(sens_rhs_kernel, dim3(blocks_for(static_cast<int64_t>(p.n_p) * p.dimM)), dim3(kSensThreads), 0, st, view(), ext.d_V(), 0LL,
+                     m_V.p, 0LL, m_s.p, m_z.p, 0LL, m_M.p, m_R.p);
   SLPX_HIP_CHECK(hipGetLastError());
   dev.assemble();
   dev.build_rhs();
@@ -241,19 +269,19 @@ void Sensitivity::expand_and_download(int columns, const double* r_i, long long 
   const SensPlan& p = m_plan;
   DeviceNlp& dev = m_model.device();
   const hipStream_t st = dev.stream();
-  hipLaunchKernelGGL(sens_expand_kernel, dim3(blocks_for(p.dimM), columns), dim3(kSensThreads), 0, st, view(), columns, m_V.p, m_s.p, m_z.p,
-                     m_sol.p, r_i, r_i_stride, m_out.p);
+  hipLaunchKernelGGL(sens_expand_kernel, dim3(blocks_for(static_cast<int64_t>(columns) * p.dimM)), dim3(kSensThreads), 0, st, view(), columns,
+                     m_V.p, 0LL, m_s.p, m_z.p, 0LL, m_sol.p, r_i, r_i_stride, 0LL, m_dx.p, m_ds.p, m_dy.p, m_dz.p);
   SLPX_HIP_CHECK(hipGetLastError());
-  const size_t stride = static_cast<size_t>(p.dimM) + p.m_i;
-  std::vector<double> out(static_cast<size_t>(columns) * stride);
-  dev.download(m_out.p, out.data(), out.size());
-  for (int c = 0; c < columns; ++c) {
-    const double* o = out.data() + c * stride;
-    if (dx) std::copy(o, o + p.n, dx + static_cast<size_t>(c) * p.n);
-    if (ds) std::copy(o + p.n, o + p.n + p.m_i, ds + static_cast<size_t>(c) * p.m_i);
-    if (dy) std::copy(o + p.n + p.m_i, o + p.n + p.m_i + p.m_e, dy + static_cast<size_t>(c) * p.m_e);
-    if (dz) std::copy(o + p.n + p.m_i + p.m_e, o + stride, dz + static_cast<size_t>(c) * p.m_i);
-  }
+  // (the kernel wrote the caller's layout: one copy per output array, one wait for all)
+  const auto fetch = [&](const DevBuf<double>& from, double* to, int width) {
+    const size_t count = static_cast<size_t>(columns) * width;
+    if (to != nullptr && count) SLPX_HIP_CHECK(hipMemcpyAsync(to, from.p, count * sizeof(double), hipMemcpyDeviceToHost, st));
+  };
+  fetch(m_dx, dx, p.n);
+  fetch(m_ds, ds, p.m_i);
+  fetch(m_dy, dy, p.m_e);
+  fetch(m_dz, dz, p.m_i);
+  SLPX_HIP_CHECK(hipStreamSynchronize(st));
 }
 
 void Sensitivity::jacobian(const Point& at, double* dx, double* ds, double* dy, double* dz, SensitivityInfo& info) {
@@ -300,7 +328,7 @@ void Sensitivity::vjp(const Point& at, const double* vx, double* grad, Sensitivi
   SLPX_HIP_CHECK(hipMemcpyAsync(m_rhs1.p, rhs.data(), rhs.size() * sizeof(double), hipMemcpyHostToDevice, st));
   SLPX_HIP_CHECK(hipStreamSynchronize(st));
   solve_one(m_rhs1.p, m_sol.p, info);
-  hipLaunchKernelGGL(sens_vjp_kernel, dim3(p.n_p), dim3(kSensVjpThreads), 0, st, view(), m_R.p, m_sol.p, m_grad.p);
+  hipLaunchKernelGGL(sens_vjp_kernel, dim3(p.n_p, 1), dim3(kSensVjpThreads), 0, st, view(), m_R.p, m_sol.p, m_grad.p);
   SLPX_HIP_CHECK(hipGetLastError());
   std::vector<double> g(static_cast<size_t>(p.n_p));
   dev.download(m_grad.p, g.data(), g.size());
@@ -314,6 +342,448 @@ void Sensitivity::unreduced(const Point& at, double* M) {
   if (at.scales_after != nullptr && static_cast<int>(at.scales_after->size()) == m_model.structure().n_scales() && !m_factored)
     m_model.device().set_scaling(*at.scales_after);
   if (M) m_model.device().download(m_M.p, M, static_cast<size_t>(m_plan.n_p) * m_plan.dimM);
+}
+
+// ---- B instances at once ----
+
+// One call's bookkeeping.  status: the outcome of every instance IN THIS CALL — that of its rows (PerBatch::base_status),
+// or skipped for a dp / vx that is not finite; mask: the instances the solves of this call are for.
+struct BatchSensitivity::Call {
+  PerBatch* pb = nullptr;
+  NewtonSystem* model = nullptr;
+  Rows at;
+  clk::time_point t0;
+  std::vector<int32_t> status;
+  std::vector<uint8_t> extra_bad, mask;
+  std::vector<SensitivityInfo> info;
+  std::vector<double> extra;  // dp / vx, zeros in the rows of the instances left out: no kernel reads a NaN
+  double t_compile = 0.0, t_factor = 0.0;
+  int factorizations = 0;
+
+  void settle() {
+    const int B = pb->B;
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+      status[b] = pb->base_status[b] != kSensComputed ? pb->base_status[b] : extra_bad[b] ? kSensSkipped : kSensComputed;
+      mask[b] = status[b] == kSensComputed ? 1 : 0;
+      any = any || mask[b];
+    }
+    any_computed = any;
+  }
+  bool any_computed = false;
+};
+
+SensDev BatchSensitivity::view() const {
+  const SensPlan& p = m_plan;
+  return SensDev{p.n, p.n_p, p.m_e, p.m_i, p.dim, p.dimM, m_m_ptr.p, m_m_src.p, m_red_ptr.p, m_red_src.p, m_red_row.p,
+                 m_ai_rowptr.p, m_ai_col.p, m_ai_src.p};
+}
+
+void BatchSensitivity::forget(int batch) {
+  const auto it = m_per_batch.find(batch);
+  if (it != m_per_batch.end()) it->second.evaluated = it->second.factored = false;
+}
+void BatchSensitivity::forget_all() {
+  for (auto& [batch, pb] : m_per_batch) pb.evaluated = pb.factored = false;
+}
+
+// The extended system of this batch size (made on the first call for it) and, on the very first call, the plan.
+BatchSensitivity::PerBatch& BatchSensitivity::per_batch(NewtonSystem& model, NodeId f) {
+  const int B = model.batch();
+  PerBatch& pb = m_per_batch[B];
+  if (pb.ext) return pb;
+  const auto t0 = clk::now();
+  if (!model.has_device()) throw std::runtime_error("slpx: batched sensitivity: no HIP device");
+  const std::vector<NodeId> params = model.structure().parameter_nodes();
+  if (params.empty()) throw std::runtime_error("slpx: batched sensitivity: the model reaches no parameter");
+  std::vector<NodeId> xp = model.x_nodes();
+  xp.insert(xp.end(), params.begin(), params.end());
+  NewtonOptions opt;
+  opt.tape = model.options().tape;
+  opt.device = model.options().device;
+  opt.batch = B;
+  auto ext = std::make_unique<NewtonSystem>(model.graph(), xp, f, model.c_e_nodes(), model.c_i_nodes(), opt);
+  ext->device().set_scaling(std::vector<double>(ext->structure().n_scales(), 1.0));
+  if (!m_have_plan) {
+    m_plan = build_sens_plan(model.structure(), ext->structure());
+    m_m_ptr.upload(m_plan.m_ptr);
+    m_m_src.upload(m_plan.m_src);
+    m_red_ptr.upload(m_plan.red_ptr);
+    m_red_src.upload(m_plan.red_src);
+    m_red_row.upload(m_plan.red_row);
+    m_ai_rowptr.upload(m_plan.ai_rowptr);
+    m_ai_col.upload(m_plan.ai_col);
+    m_ai_src.upload(m_plan.ai_src);
+    m_have_plan = true;
+  }
+  const SensPlan& p = m_plan;
+  if (ext->structure().nV != p.nVx || model.structure().nV != p.nV || model.kkt().dim != p.dim)
+    throw std::runtime_error("slpx: batched sensitivity: the batch system does not belong to the plan");
+  const size_t Bz = static_cast<size_t>(B), n_p = static_cast<size_t>(p.n_p);
+  pb.B = B;
+  pb.M.alloc(Bz * n_p * p.dimM);
+  pb.R.alloc(Bz * n_p * p.dim);
+  pb.V.alloc(Bz * p.nV);
+  pb.s.alloc(Bz * std::max(1, p.m_i));
+  pb.z.alloc(Bz * std::max(1, p.m_i));
+  pb.vec.alloc(Bz * n_p);
+  pb.rhs1.alloc(Bz * p.dim);
+  pb.ri1.alloc(Bz * std::max(1, p.m_i));
+  pb.grad.alloc(Bz * n_p);
+  pb.base_status.assign(Bz, kSensSkipped);
+  pb.fact.assign(Bz, SensitivityInfo{});
+  pb.ext = std::move(ext);
+  pb.compile_seconds = seconds_since(t0);
+  return pb;
+}
+
+// room for `columns` solutions per instance and their expansion
+void BatchSensitivity::ensure_columns(PerBatch& pb, int columns) {
+  if (pb.sol_columns >= columns) return;
+  const SensPlan& p = m_plan;
+  const size_t rows = static_cast<size_t>(pb.B) * columns;
+  pb.sol.alloc(rows * p.dim);
+  pb.dx.alloc(std::max<size_t>(1, rows * p.n));
+  pb.ds.alloc(std::max<size_t>(1, rows * p.m_i));
+  pb.dy.alloc(std::max<size_t>(1, rows * p.m_e));
+  pb.dz.alloc(std::max<size_t>(1, rows * p.m_i));
+  pb.sol_columns = columns;
+}
+
+// The checks every call makes, the classification of its instances, and whether what the last call of this batch size
+// left in memory is still the system of these rows.
+void BatchSensitivity::begin(Call& c, NewtonSystem& model, NodeId f, const Rows& at, const double* extra, int n_extra) {
+  c.t0 = clk::now();
+  c.model = &model;
+  c.at = at;
+  const int B = at.B;
+  if (B <= 0 || B > 65535) throw std::runtime_error("slpx: batched sensitivity: B must be in 1 .. 65535 (one grid slice per instance)");
+  if (model.batch() != B) throw std::runtime_error("slpx: batched sensitivity: the batch system is of another size");
+  PerBatch& pb = per_batch(model, f);
+  c.pb = &pb;
+  c.t_compile = pb.compile_seconds;
+  pb.compile_seconds = 0.0;
+  const SensPlan& p = m_plan;
+  if (at.x == nullptr || at.mu == nullptr || at.params == nullptr || (p.m_i && (at.s == nullptr || at.z == nullptr)) ||
+      (p.m_e && at.y == nullptr))
+    throw std::runtime_error("slpx: batched sensitivity: a required input is null");
+  const size_t Bz = static_cast<size_t>(B);
+  // the rows as one vector: what the kept factorization is the factorization OF
+  std::vector<double> key;
+  key.reserve(Bz * (p.n + 2 * p.m_i + p.m_e + 1 + p.n_p));
+  key.insert(key.end(), at.x, at.x + Bz * p.n);
+  if (p.m_i) key.insert(key.end(), at.s, at.s + Bz * p.m_i);
+  if (p.m_e) key.insert(key.end(), at.y, at.y + Bz * p.m_e);
+  if (p.m_i) key.insert(key.end(), at.z, at.z + Bz * p.m_i);
+  key.insert(key.end(), at.mu, at.mu + Bz);
+  key.insert(key.end(), at.params, at.params + Bz * p.n_p);
+  const bool same = pb.evaluated && key.size() == pb.key.size() && std::memcmp(key.data(), pb.key.data(), key.size() * sizeof(double)) == 0;
+  if (!same) {
+    pb.evaluated = pb.factored = false;
+    pb.key = std::move(key);
+    sens_classify_instances(B, p.n, p.m_e, p.m_i, p.n_p, at.x, at.s, at.y, at.z, at.mu, at.params, nullptr, 0, pb.base_status.data());
+    pb.fact.assign(Bz, SensitivityInfo{});
+  }
+  c.status.assign(Bz, kSensComputed);
+  c.extra_bad.assign(Bz, 0);
+  c.mask.assign(Bz, 0);
+  c.info.assign(Bz, SensitivityInfo{});
+  if (extra != nullptr) {
+    std::vector<int32_t> st(Bz);
+    sens_classify_instances(B, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, extra, n_extra, st.data());
+    c.extra.assign(extra, extra + Bz * n_extra);
+    for (size_t b = 0; b < Bz; ++b)
+      if (st[b] != kSensComputed) {
+        c.extra_bad[b] = 1;
+        std::fill(c.extra.begin() + b * n_extra, c.extra.begin() + (b + 1) * n_extra, 0.0);
+      }
+  }
+  c.settle();
+}
+
+// Both batch systems at the rows, unit scales, the user's units: V' and V swept, M and R written, the model's lhs
+// assembled (and a right-hand side of its own built: the factorization carries one along).  An instance that is left
+// out stands in with the rows of the first one that is not: nothing reads a NaN, and nobody reads its results.
+void BatchSensitivity::evaluate(Call& c) {
+  PerBatch& pb = *c.pb;
+  if (pb.evaluated) return;
+  const SensPlan& p = m_plan;
+  const Rows& at = c.at;
+  const size_t B = static_cast<size_t>(pb.B), n = p.n, n_p = p.n_p, m_e = p.m_e, m_i = p.m_i;
+  pb.factored = false;
+  size_t h = B;
+  for (size_t b = 0; b < B && h == B; ++b)
+    if (pb.base_status[b] == kSensComputed) h = b;
+  if (h == B) {  // (nothing to differentiate: every output row is NaN)
+    pb.evaluated = true;
+    return;
+  }
+  std::vector<double> xp(B * (n + n_p)), x(B * n), s(B * std::max<size_t>(1, m_i), 1.0), y(B * std::max<size_t>(1, m_e), 0.0),
+      z(B * std::max<size_t>(1, m_i), 1.0), mu(B), rows(B * n_p);
+  for (size_t b = 0; b < B; ++b) {
+    const size_t from = pb.base_status[b] == kSensComputed ? b : h;
+    std::copy(at.x + from * n, at.x + (from + 1) * n, x.begin() + b * n);
+    std::copy(at.x + from * n, at.x + (from + 1) * n, xp.begin() + b * (n + n_p));
+    std::copy(at.params + from * n_p, at.params + (from + 1) * n_p, xp.begin() + b * (n + n_p) + n);
+    std::copy(at.params + from * n_p, at.params + (from + 1) * n_p, rows.begin() + b * n_p);
+    if (m_i) {
+      std::copy(at.s + from * m_i, at.s + (from + 1) * m_i, s.begin() + b * m_i);
+      std::copy(at.z + from * m_i, at.z + (from + 1) * m_i, z.begin() + b * m_i);
+    }
+    if (m_e) std::copy(at.y + from * m_e, at.y + (from + 1) * m_e, y.begin() + b * m_e);
+    mu[b] = at.mu[from];
+  }
+  DeviceNlp& dev = c.model->device();
+  DeviceNlp& ext = pb.ext->device();
+  ext.upload_x(xp.data());
+  ext.upload_duals(s.data(), y.data(), z.data());
+  ext.sweep_full();
+  SLPX_HIP_CHECK(hipStreamSynchronize(ext.stream()));  // (the two systems may run on different streams)
+  // instance b's parameter row in a pool of its own on the model's batch system for the sweep; however this ends, the
+  // shared pool with the parameters' current values is in force again
+  struct SharedPoolAgain {
+    NewtonSystem* sys;
+    void now() {
+      NewtonSystem* s = sys;
+      sys = nullptr;
+      if (s != nullptr) s->device().refresh_params(s->graph());
+    }
+    ~SharedPoolAgain() {
+      try {
+        now();
+      } catch (...) {
+      }
+    }
+  } shared_pool_again{c.model};
+  dev.set_parameters(rows.data(), /*per_instance=*/true);
+  dev.upload_x(x.data());
+  dev.upload_duals(s.data(), y.data(), z.data());
+  dev.upload_mu(mu.data());
+  dev.sweep_full();
+  const hipStream_t st = dev.stream();
+  SLPX_HIP_CHECK(hipMemcpyAsync(pb.V.p, dev.d_V(), B * p.nV * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (m_i) {
+    SLPX_HIP_CHECK(hipMemcpyAsync(pb.s.p, dev.d_s(), B * m_i * sizeof(double), hipMemcpyDeviceToDevice, st));
+    SLPX_HIP_CHECK(hipMemcpyAsync(pb.z.p, dev.d_z(), B * m_i * sizeof(double), hipMemcpyDeviceToDevice, st));
+  }
+  hipLaunchKernelGGL(sens_rhs_kernel, dim3(blocks_for(static_cast<int64_t>(p.n_p) * p.dimM, kSensBatchThreads), pb.B), dim3(kSensBatchThreads), 0, st, view(), ext.d_V(),
+                     static_cast<long long>(p.nVx), pb.V.p, static_cast<long long>(p.nV), pb.s.p, pb.z.p, static_cast<long long>(m_i), pb.M.p,
+                     pb.R.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  dev.assemble();
+  dev.build_rhs();
+  // (what is in memory IS the system now — a request for a step that never came is void; assemble() and build_rhs()
+  // said themselves which layout they wrote)
+  dev.system_written_by_caller(/*lhs=*/false, /*rhs=*/false);
+  SLPX_HIP_CHECK(hipStreamSynchronize(st));  // (the rows are this function's)
+  shared_pool_again.now();
+  pb.evaluated = true;
+}
+
+// NewtonSystem::compute() for the instances that are differentiated, each from a cleared memory; the batch system's own
+// memory is put back afterwards.  An instance whose system cannot be factored leaves the call here (kSensNotFactored).
+void BatchSensitivity::factor(Call& c) {
+  evaluate(c);
+  PerBatch& pb = *c.pb;
+  const int B = pb.B;
+  if (!pb.factored) {
+    const auto t0 = clk::now();
+    std::vector<uint8_t> mask(B, 0);
+    bool any = false;
+    for (int b = 0; b < B; ++b) any = (mask[b] = pb.base_status[b] == kSensComputed ? 1 : 0) || any;
+    if (any) {
+      NewtonSystem& model = *c.model;
+      const NewtonSystem::RegularizationState saved = model.regularization_state();
+      model.reset_regularization();
+      std::vector<FactorInfo> res;
+      try {
+        res = model.compute(/*solve_speculatively=*/false, mask);
+      } catch (...) {
+        model.set_regularization_state(saved);
+        throw;
+      }
+      const std::vector<double> delta = model.hessian_regularization(), gamma = model.constraint_jacobian_regularization();
+      c.factorizations = model.last_factorizations();
+      model.set_regularization_state(saved);
+      std::vector<LdltStats> stats;
+      model.device().read_stats(stats);
+      for (int b = 0; b < B; ++b) {
+        if (!mask[b]) continue;
+        SensitivityInfo& fi = pb.fact[b];
+        fi.delta = delta[b];
+        fi.gamma = gamma[b];
+        if (res[b] == FactorInfo::Success) {
+          // (the counters in memory are those of the LAST launch, which an instance accepted earlier sat out: what the
+          // policy accepts has the ideal inertia and nothing else, ldlt_policy.hpp: ldlt_judge)
+          fi.n_pos = m_plan.n;
+          fi.n_neg = m_plan.m_e;
+          fi.n_zero = 0;
+        } else {  // (gave up in the last launch it took part in; the counters as they stand)
+          fi.n_pos = stats[b].n_pos;
+          fi.n_neg = stats[b].n_neg;
+          fi.n_zero = stats[b].n_zero;
+          pb.base_status[b] = kSensNotFactored;
+        }
+      }
+    }
+    pb.factored = true;
+    c.t_factor = seconds_since(t0);
+  }
+  c.settle();
+  for (int b = 0; b < B; ++b) {
+    if (pb.base_status[b] == kSensSkipped) continue;
+    c.info[b] = pb.fact[b];
+    c.info[b].factorizations = c.factorizations;
+  }
+}
+
+void BatchSensitivity::solve_round(Call& c, const double* rhs, size_t rhs_pitch, double* sol, size_t sol_pitch) {
+  if (!c.any_computed) return;
+  PerBatch& pb = *c.pb;
+  DeviceNlp& dev = c.model->device();
+  const size_t width = static_cast<size_t>(m_plan.dim) * sizeof(double);
+  const hipStream_t st = dev.stream();
+  SLPX_HIP_CHECK(hipMemcpy2DAsync(dev.rhs_raw(), width, rhs, rhs_pitch * sizeof(double), width, pb.B, hipMemcpyDeviceToDevice, st));
+  dev.system_written_by_caller(/*lhs=*/false, /*rhs=*/true);
+  dev.solve();
+  const NewtonSystem::Refinement ref = c.model->refine(2, &c.mask);
+  const NewtonSystem::ErrorBounds eb = c.model->error_bounds(&c.mask, /*want_ferr=*/false);
+  for (int b = 0; b < pb.B; ++b) {
+    if (!c.mask[b]) continue;
+    SensitivityInfo& info = c.info[b];
+    info.solves += 1 + ref.accepted[b];
+    info.refine_steps += ref.accepted[b];
+    if (!(eb.berr[b] <= info.berr_max)) info.berr_max = eb.berr[b];  // (a NaN shows)
+  }
+  SLPX_HIP_CHECK(hipMemcpy2DAsync(sol, sol_pitch * sizeof(double), dev.d_p(), width, width, pb.B, hipMemcpyDeviceToDevice, st));
+}
+
+namespace {
+// rows of `width` entries, one per (instance, column): NaN where the instance was not computed
+void nan_rows(double* out, const std::vector<int32_t>& status, size_t per_instance) {
+  if (out == nullptr || per_instance == 0) return;
+  for (size_t b = 0; b < status.size(); ++b)
+    if (status[b] != kSensComputed) std::fill(out + b * per_instance, out + (b + 1) * per_instance, std::numeric_limits<double>::quiet_NaN());
+}
+}  // namespace
+
+void BatchSensitivity::expand_and_download(Call& c, int columns, const double* r_i, long long r_i_column, long long r_i_instance,
+                                           double* dx, double* ds, double* dy, double* dz) {
+  const SensPlan& p = m_plan;
+  PerBatch& pb = *c.pb;
+  const size_t rows = static_cast<size_t>(pb.B) * columns;
+  if (c.any_computed) {
+    const hipStream_t st = c.model->device().stream();
+    hipLaunchKernelGGL(sens_expand_kernel, dim3(blocks_for(static_cast<int64_t>(columns) * p.dimM, kSensBatchThreads), pb.B), dim3(kSensBatchThreads), 0, st, view(),
+                       columns, pb.V.p, static_cast<long long>(p.nV), pb.s.p, pb.z.p, static_cast<long long>(p.m_i), pb.sol.p, r_i, r_i_column,
+                       r_i_instance, pb.dx.p, pb.ds.p, pb.dy.p, pb.dz.p);
+    SLPX_HIP_CHECK(hipGetLastError());
+    // (the kernel wrote the caller's layout: one copy per output array, one wait for all)
+    const auto fetch = [&](const DevBuf<double>& from, double* to, int width) {
+      const size_t count = rows * width;
+      if (to != nullptr && count) SLPX_HIP_CHECK(hipMemcpyAsync(to, from.p, count * sizeof(double), hipMemcpyDeviceToHost, st));
+    };
+    fetch(pb.dx, dx, p.n);
+    fetch(pb.ds, ds, p.m_i);
+    fetch(pb.dy, dy, p.m_e);
+    fetch(pb.dz, dz, p.m_i);
+    SLPX_HIP_CHECK(hipStreamSynchronize(st));
+  }
+  nan_rows(dx, c.status, static_cast<size_t>(columns) * p.n);
+  nan_rows(ds, c.status, static_cast<size_t>(columns) * p.m_i);
+  nan_rows(dy, c.status, static_cast<size_t>(columns) * p.m_e);
+  nan_rows(dz, c.status, static_cast<size_t>(columns) * p.m_i);
+}
+
+void BatchSensitivity::finish(Call& c, int32_t* status, SensitivityInfo* info) {
+  const double t_total = seconds_since(c.t0) + c.t_compile;
+  if (status) std::copy(c.status.begin(), c.status.end(), status);
+  if (info == nullptr) return;
+  for (int b = 0; b < c.pb->B; ++b) {
+    info[b] = c.info[b];
+    info[b].n_p = m_plan.n_p;
+    info[b].solve_status = 0;  // (the call is not told it)
+    info[b].t_compile = c.t_compile;
+    info[b].t_factor = c.t_factor;
+    info[b].t_total = t_total;
+  }
+}
+
+void BatchSensitivity::jacobian(NewtonSystem& model, NodeId f, const Rows& at, double* dx, double* ds, double* dy, double* dz,
+                                int32_t* status, SensitivityInfo* info) {
+  Call c;
+  begin(c, model, f, at, nullptr, 0);
+  const SensPlan& p = m_plan;
+  PerBatch& pb = *c.pb;
+  ensure_columns(pb, p.n_p);
+  factor(c);
+  // round q: column q of every instance
+  const size_t pitch = static_cast<size_t>(p.n_p) * p.dim;
+  for (int q = 0; q < p.n_p; ++q) solve_round(c, pb.R.p + static_cast<size_t>(q) * p.dim, pitch, pb.sol.p + static_cast<size_t>(q) * p.dim, pitch);
+  expand_and_download(c, p.n_p, pb.M.p + p.dim, p.dimM, static_cast<long long>(p.n_p) * p.dimM, dx, ds, dy, dz);
+  finish(c, status, info);
+}
+
+void BatchSensitivity::jvp(NewtonSystem& model, NodeId f, const Rows& at, const double* dp, double* dx, double* ds, double* dy,
+                           double* dz, int32_t* status, SensitivityInfo* info) {
+  if (dp == nullptr) throw std::runtime_error("slpx: batched sensitivity jvp: dp is null");
+  Call c;
+  begin(c, model, f, at, dp, static_cast<int>(model.structure().parameter_nodes().size()));
+  const SensPlan& p = m_plan;
+  PerBatch& pb = *c.pb;
+  ensure_columns(pb, 1);
+  factor(c);
+  if (c.any_computed) {
+    const hipStream_t st = model.device().stream();
+    SLPX_HIP_CHECK(hipMemcpyAsync(pb.vec.p, c.extra.data(), c.extra.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(sens_combine_kernel, dim3(blocks_for(p.dimM, kSensBatchThreads), pb.B), dim3(kSensBatchThreads), 0, st, view(), pb.M.p, pb.R.p, pb.vec.p, pb.rhs1.p,
+                       pb.ri1.p);
+    SLPX_HIP_CHECK(hipGetLastError());
+    solve_round(c, pb.rhs1.p, p.dim, pb.sol.p, p.dim);
+  }
+  expand_and_download(c, 1, pb.ri1.p, 0, p.m_i, dx, ds, dy, dz);
+  finish(c, status, info);
+}
+
+void BatchSensitivity::vjp(NewtonSystem& model, NodeId f, const Rows& at, const double* vx, double* grad, int32_t* status,
+                           SensitivityInfo* info) {
+  if (vx == nullptr) throw std::runtime_error("slpx: batched sensitivity vjp: vx is null");
+  Call c;
+  begin(c, model, f, at, vx, model.structure().n);
+  const SensPlan& p = m_plan;
+  PerBatch& pb = *c.pb;
+  ensure_columns(pb, 1);
+  factor(c);
+  const size_t B = static_cast<size_t>(pb.B);
+  if (c.any_computed) {
+    DeviceNlp& dev = model.device();
+    const hipStream_t st = dev.stream();
+    std::vector<double> rhs(B * p.dim, 0.0);  // [vx; 0] per instance
+    for (size_t b = 0; b < B; ++b) std::copy(c.extra.begin() + b * p.n, c.extra.begin() + (b + 1) * p.n, rhs.begin() + b * p.dim);
+    SLPX_HIP_CHECK(hipMemcpyAsync(pb.rhs1.p, rhs.data(), rhs.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    SLPX_HIP_CHECK(hipStreamSynchronize(st));
+    solve_round(c, pb.rhs1.p, p.dim, pb.sol.p, p.dim);
+    hipLaunchKernelGGL(sens_vjp_kernel, dim3(p.n_p, pb.B), dim3(kSensVjpThreads), 0, st, view(), pb.R.p, pb.sol.p, pb.grad.p);
+    SLPX_HIP_CHECK(hipGetLastError());
+    if (grad) dev.download(pb.grad.p, grad, B * p.n_p);
+    else SLPX_HIP_CHECK(hipStreamSynchronize(st));
+  }
+  nan_rows(grad, c.status, p.n_p);
+  finish(c, status, info);
+}
+
+void BatchSensitivity::unreduced(NewtonSystem& model, NodeId f, const Rows& at, double* M, int32_t* status) {
+  Call c;
+  begin(c, model, f, at, nullptr, 0);
+  evaluate(c);
+  const size_t per_instance = static_cast<size_t>(m_plan.n_p) * m_plan.dimM;
+  // (an instance a kept factorization found singular still has its M: only what was skipped has none)
+  std::vector<int32_t> st(c.status);
+  bool any = false;
+  for (size_t b = 0; b < st.size(); ++b) any = (st[b] = c.pb->base_status[b] == kSensSkipped ? kSensSkipped : kSensComputed) == kSensComputed || any;
+  if (M && any) model.device().download(c.pb->M.p, M, static_cast<size_t>(c.pb->B) * per_instance);
+  nan_rows(M, st, per_instance);
+  if (status) std::copy(st.begin(), st.end(), status);
 }
 
 }  // namespace slpx

@@ -17,6 +17,7 @@
 // problem drops when the model is compiled again.
 #pragma once
 
+#include <map>
 #include <memory>
 #include <vector>
 
@@ -103,7 +104,83 @@ class Sensitivity {
   DevBuf<int32_t> m_m_ptr, m_m_src, m_red_ptr, m_red_src, m_red_row, m_ai_rowptr, m_ai_col, m_ai_src;
   // M, R; the model's V, s, z at the iterate (copies: the model system's own are its caller's again after a product)
   DevBuf<double> m_M, m_R, m_V, m_s, m_z;
-  DevBuf<double> m_vec, m_rhs1, m_ri1, m_sol, m_out, m_grad;
+  DevBuf<double> m_vec, m_rhs1, m_ri1, m_sol, m_dx, m_ds, m_dy, m_dz, m_grad;
+};
+
+// The same derivatives for B iterates at once, instance b with respect to ITS parameter row (include/slpx.h: batched
+// sensitivities): a function of the rows it is given, not of any state of the problem.  The expensive stages are the
+// batch system's own (`model`: the problem's system compiled for B instances, tape at unit scales) — sweep, assemble,
+// compute() with a mask and per-instance delta / gamma, solve(), refine() and error_bounds() with a mask; the extended
+// system over [x ; p] is compiled once per batch size and kept here, where the parameters are variables: instance b's
+// row is the tail of its x' row.  The plan and its device arrays are shared by every batch size.
+//
+// What a call leaves on `model`: the shared parameter pool with the parameters' current values (the graph's), as
+// solve_batch leaves it, and the regularization memory it found.  The factorization stays in memory: a call with the
+// same B and the same bits in every iterate and parameter row reuses it (factorizations == 0), until forget(B).
+class BatchSensitivity {
+ public:
+  // B iterates in the user's units and their parameter rows: x [B][n], s [B][m_i], y [B][m_e], z [B][m_i], mu [B],
+  // params [B][n_p].  s, y, z may be null where the row has no entries.
+  struct Rows {
+    int B = 0;
+    const double *x = nullptr, *s = nullptr, *y = nullptr, *z = nullptr, *mu = nullptr, *params = nullptr;
+  };
+
+  BatchSensitivity() = default;
+  BatchSensitivity(const BatchSensitivity&) = delete;
+  BatchSensitivity& operator=(const BatchSensitivity&) = delete;
+
+  // Somebody else used the batch system of that size (solve_batch, restoration_steps_batch): the next call of that size
+  // evaluates and factors again.
+  void forget(int batch);
+  void forget_all();
+  bool has_plan() const { return m_have_plan; }
+  const SensPlan& plan() const { return m_plan; }
+
+  // `f`: the cost's root (kNull: none).  status [B] (sens_plan.hpp: kSensComputed, ...), info [B] (null: not wanted).
+  // Rows of an instance whose status is not 0 are NaN in every output.  Any output may be null.
+  // dx [B][n_p][n], ds [B][n_p][m_i], dy [B][n_p][m_e], dz [B][n_p][m_i]: n_p rounds of solves, round q column q of every instance
+  void jacobian(NewtonSystem& model, NodeId f, const Rows& at, double* dx, double* ds, double* dy, double* dz, int32_t* status,
+                SensitivityInfo* info);
+  // dp [B][n_p] -> dx [B][n], ds [B][m_i], dy [B][m_e], dz [B][m_i]: one round
+  void jvp(NewtonSystem& model, NodeId f, const Rows& at, const double* dp, double* dx, double* ds, double* dy, double* dz,
+           int32_t* status, SensitivityInfo* info);
+  // vx [B][n] -> grad [B][n_p]: one round
+  void vjp(NewtonSystem& model, NodeId f, const Rows& at, const double* vx, double* grad, int32_t* status, SensitivityInfo* info);
+  // M [B][n_p][n + m_e + m_i]: neither factors nor solves
+  void unreduced(NewtonSystem& model, NodeId f, const Rows& at, double* M, int32_t* status);
+
+ private:
+  // what belongs to one batch size
+  struct PerBatch {
+    int B = 0;
+    std::unique_ptr<NewtonSystem> ext;
+    double compile_seconds = 0.0;
+    bool evaluated = false, factored = false;
+    std::vector<double> key;            // the rows `evaluated` / `factored` speak of: x, s, y, z, mu, params as given
+    std::vector<int32_t> base_status;   // of those rows: classification, then kSensNotFactored from the factorization
+    std::vector<SensitivityInfo> fact;  // per instance: inertia, delta, gamma of the factorization in memory
+    DevBuf<double> M, R, V, s, z, vec, rhs1, ri1, sol, dx, ds, dy, dz, grad;
+    int sol_columns = 0;
+  };
+  struct Call;  // one call's bookkeeping (sensitivity.hip)
+
+  PerBatch& per_batch(NewtonSystem& model, NodeId f);
+  void ensure_columns(PerBatch& pb, int columns);
+  void begin(Call& c, NewtonSystem& model, NodeId f, const Rows& at, const double* extra, int n_extra);
+  void evaluate(Call& c);
+  void factor(Call& c);
+  // the right-hand sides in rhs (device, [B] rows `rhs_pitch` doubles apart) -> the refined solutions into sol likewise
+  void solve_round(Call& c, const double* rhs, size_t rhs_pitch, double* sol, size_t sol_pitch);
+  void expand_and_download(Call& c, int columns, const double* r_i, long long r_i_column, long long r_i_instance, double* dx,
+                           double* ds, double* dy, double* dz);
+  void finish(Call& c, int32_t* status, SensitivityInfo* info);
+  SensDev view() const;
+
+  bool m_have_plan = false;
+  SensPlan m_plan;
+  DevBuf<int32_t> m_m_ptr, m_m_src, m_red_ptr, m_red_src, m_red_row, m_ai_rowptr, m_ai_col, m_ai_src;
+  std::map<int, PerBatch> m_per_batch;
 };
 
 }  // namespace slpx

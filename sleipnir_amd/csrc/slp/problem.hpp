@@ -284,7 +284,101 @@ class ProblemF64 {
     if (m_sens) m_sens->forget();
   }
 
+  // ---- batched sensitivities (sensitivity.hpp: BatchSensitivity; include/slpx.h: batched sensitivities) ----
+  // The same derivatives for `batch` iterates at once, instance b with respect to ITS parameter row: functions of the
+  // rows they are given — what solve_batch(..., warm) returned in the user's units — not of any state of the problem,
+  // since solve_batch leaves none.  They run on batch_system(batch) alone: the variables, the parameters, the batch-1
+  // system's scaling and regularization memory and a kept single-problem sensitivity factorization are untouched, and a
+  // following solve_batch keeps every bit.  An instance that cannot be differentiated does not throw: status says so
+  // (sens_plan.hpp: kSensComputed, kSensSkipped, kSensNotFactored) and its output rows are NaN.  Calls with the same
+  // rows share one factorization until the next solve_batch / restoration_steps_batch of that batch size.
+  struct BatchIterate {
+    std::span<const double> x, s, y, z, mu;  // [B][n], [B][m_i], [B][m_e], [B][m_i], [B]
+  };
+  struct BatchSensitivities {
+    std::vector<double> dx, ds, dy, dz;  // the Jacobian: [B][n_p][n], ...; a product: [B][n], [B][m_i], [B][m_e], [B][m_i]
+    std::vector<double> grad;            // the vjp: [B][n_p]
+    std::vector<double> M;               // sensitivity_batch_rhs: [B][n_p][n + m_e + m_i]
+    std::vector<int32_t> status;         // [B]
+    std::vector<slpx::SensitivityInfo> info;  // [B]
+  };
+  BatchSensitivities sensitivity_batch(int batch, const BatchIterate& it, std::span<const double> params) {
+    BatchCall c = batch_sensitivity_call(batch, it, params, "sensitivity_batch");
+    BatchSensitivities out = c.outputs(c.n_p);
+    m_batch_sens->jacobian(*c.sys, cost_root(), c.rows, out.dx.data(), out.ds.data(), out.dy.data(), out.dz.data(), out.status.data(),
+                           out.info.data());
+    return out;
+  }
+  BatchSensitivities sensitivity_batch_jvp(int batch, const BatchIterate& it, std::span<const double> params, std::span<const double> dp) {
+    BatchCall c = batch_sensitivity_call(batch, it, params, "sensitivity_batch_jvp");
+    if (dp.size() != c.B * c.n_p) throw std::runtime_error("sensitivity_batch_jvp: dp must have batch x n_p values");
+    BatchSensitivities out = c.outputs(1);
+    m_batch_sens->jvp(*c.sys, cost_root(), c.rows, dp.data(), out.dx.data(), out.ds.data(), out.dy.data(), out.dz.data(), out.status.data(),
+                      out.info.data());
+    return out;
+  }
+  BatchSensitivities sensitivity_batch_vjp(int batch, const BatchIterate& it, std::span<const double> params, std::span<const double> vx) {
+    BatchCall c = batch_sensitivity_call(batch, it, params, "sensitivity_batch_vjp");
+    if (vx.size() != c.B * c.n) throw std::runtime_error("sensitivity_batch_vjp: vx must have batch x n values");
+    BatchSensitivities out;
+    out.grad.resize(c.B * c.n_p);
+    out.status.resize(c.B);
+    out.info.resize(c.B);
+    m_batch_sens->vjp(*c.sys, cost_root(), c.rows, vx.data(), out.grad.data(), out.status.data(), out.info.data());
+    return out;
+  }
+  BatchSensitivities sensitivity_batch_rhs(int batch, const BatchIterate& it, std::span<const double> params) {
+    BatchCall c = batch_sensitivity_call(batch, it, params, "sensitivity_batch_rhs");
+    BatchSensitivities out;
+    out.M.resize(c.B * c.n_p * (c.n + c.m_e + c.m_i));
+    out.status.resize(c.B);
+    m_batch_sens->unreduced(*c.sys, cost_root(), c.rows, out.M.data(), out.status.data());
+    return out;
+  }
+
  private:
+  // the checks every batched sensitivity call makes, the batch system it runs on and the rows as the driver takes them
+  struct BatchCall {
+    slpx::NewtonSystem* sys = nullptr;
+    slpx::BatchSensitivity::Rows rows;
+    size_t B = 0, n = 0, m_e = 0, m_i = 0, n_p = 0;
+    BatchSensitivities outputs(size_t columns) const {
+      BatchSensitivities out;
+      out.dx.resize(B * columns * n);
+      out.ds.resize(B * columns * m_i);
+      out.dy.resize(B * columns * m_e);
+      out.dz.resize(B * columns * m_i);
+      out.status.resize(B);
+      out.info.resize(B);
+      return out;
+    }
+  };
+  NodeId cost_root() const { return m_f ? m_f->expr : slpx::kNull; }
+  BatchCall batch_sensitivity_call(int batch, const BatchIterate& it, std::span<const double> params, const char* who) {
+    const std::string name(who);
+    if (batch <= 0 || batch > 65535) throw std::runtime_error(name + ": batch must be in 1 .. 65535 (one grid slice per instance)");
+    slpx::NewtonSystem& model = compile();
+    if (!model.has_device()) throw std::runtime_error(name + ": no HIP device");
+    BatchCall c;
+    const auto& st = model.structure();
+    c.B = static_cast<size_t>(batch);
+    c.n = st.n;
+    c.m_e = st.m_e;
+    c.m_i = st.m_i;
+    c.n_p = st.parameter_nodes().size();
+    if (c.n_p == 0) throw std::runtime_error(name + ": the model reaches no parameter");
+    if (it.x.size() != c.B * c.n || it.s.size() != c.B * c.m_i || it.y.size() != c.B * c.m_e || it.z.size() != c.B * c.m_i ||
+        it.mu.size() != c.B || params.size() != c.B * c.n_p)
+      throw std::runtime_error(name + ": the iterate and parameter rows do not have batch x the model's sizes");
+    c.sys = &batch_system(batch);
+    c.rows = slpx::BatchSensitivity::Rows{batch, it.x.data(), it.s.data(), it.y.data(), it.z.data(), it.mu.data(), params.data()};
+    if (!m_batch_sens) m_batch_sens = std::make_unique<slpx::BatchSensitivity>();
+    return c;
+  }
+  void batch_sensitivity_forget(int batch) {
+    if (m_batch_sens) m_batch_sens->forget(batch);
+  }
+
   // the checks every sensitivity call makes, and where it differentiates
   slpx::Sensitivity::Point sensitivity_point() {
     if (!m_has_iterate) throw std::runtime_error("sensitivity: the problem has not been solved");
@@ -411,6 +505,7 @@ class ProblemF64 {
     if (x0 == nullptr) throw std::runtime_error("solve_batch: x0 is null");
     if (has_callbacks()) throw std::runtime_error("solve_batch: the problem has callbacks registered");
     sensitivity_forget();  // (restoration hand-offs run on the batch-1 system)
+    batch_sensitivity_forget(batch);
     auto& g = detail::G();
     const size_t B = static_cast<size_t>(batch), n = m_decision_variables.size(), m_e = m_equality_constraints.size(),
                  m_i = m_inequality_constraints.size();
@@ -557,6 +652,7 @@ class ProblemF64 {
     if (batch <= 0) throw std::runtime_error("restoration_steps_batch: batch must be positive");
     if (has_callbacks()) throw std::runtime_error("restoration_steps_batch: the problem has callbacks registered");
     sensitivity_forget();
+    batch_sensitivity_forget(batch);
     auto& g = detail::G();
     compile();
     const auto& st = m_sys->structure();
@@ -737,6 +833,7 @@ class ProblemF64 {
 
   void invalidate() {
     m_sens.reset();  // (it refers to m_sys)
+    m_batch_sens.reset();  // (its extended systems are compiled from the same model)
     m_batch_sys.clear();
     m_sys.reset();
     m_param_snapshot.clear();
@@ -827,6 +924,7 @@ class ProblemF64 {
   // sensitivities: the extended system and its plan (made by the first call, dropped with m_sys), the parameters'
   // values and the status of the solve the iterate came from, and the iterate as a sensitivity call handed it down
   std::unique_ptr<slpx::Sensitivity> m_sens;
+  std::unique_ptr<slpx::BatchSensitivity> m_batch_sens;  // the batched calls: plan, and an extended system per batch size
   std::vector<double> m_iterate_parameters;
   int m_iterate_status = 0;
   Iterate m_sens_iterate;

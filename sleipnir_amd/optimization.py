@@ -22,7 +22,7 @@ from sleipnir_amd.autodiff import (EqualityConstraints, ExpressionType, Inequali
 
 __all__ = ["ExitStatus", "Problem", "OCP", "DynamicsType", "TimestepMethod", "TranscriptionMethod",
            "EqualityConstraints", "InequalityConstraints", "IterationInfo", "bounds", "multistart",
-           "Iterate", "BatchIterate", "BatchResult", "Sensitivity"]
+           "Iterate", "BatchIterate", "BatchResult", "Sensitivity", "BatchSensitivity"]
 
 
 class ExitStatus(enum.IntEnum):
@@ -141,6 +141,20 @@ class BatchIterate(Iterate):
 
 
 @dataclasses.dataclass
+class BatchSensitivity:
+    """What Problem.sensitivity_batch() returns: per instance the derivatives of its end iterate with respect to its
+    parameter row — dx (B, n_p, n), ds (B, n_p, m_i), dy (B, n_p, m_e), dz (B, n_p, m_i) —, `status` (B: 0 computed,
+    1 skipped, 2 not factored; rows of the latter two are NaN) and `info`, a list of B dicts of slpx_sensitivity_info's
+    members."""
+    dx: np.ndarray
+    ds: np.ndarray
+    dy: np.ndarray
+    dz: np.ndarray
+    status: np.ndarray
+    info: list
+
+
+@dataclasses.dataclass
 class BatchResult:
     """What Problem.solve_batch returns: per instance the ExitStatus, the end iterate (x: (B, n),
     s, z: (B, m_i), y: (B, m_e)), the unscaled cost, the iteration and restoration counts; `report` holds
@@ -177,6 +191,7 @@ class Problem:
         self._pattern_cache = None
         self.report = None  # counters and phase times of the last solve() that ran an iteration
         self.sensitivity_info = None  # slpx_sensitivity_info of the last sensitivity_jvp() / sensitivity_vjp()
+        self.sensitivity_status = None  # per-instance status of the last batched sensitivity product
 
     # ---- model ----
     def decision_variable(self, rows=None, cols=1):
@@ -350,6 +365,41 @@ class Problem:
         whatever n_p."""
         grad, self.sensitivity_info = self._p.sensitivity_vjp(v)
         return grad
+
+    # ---- batched sensitivities: functions of a BatchIterate and its parameter rows, not of the problem's state ----
+    def sensitivity_batch(self, iterate, parameters) -> "BatchSensitivity":
+        """The Jacobians of the B end iterates of a solve_batch(parameters=rows, warm_start=...) with respect to their own
+        parameter rows: dx (B, n_p, n), ds (B, n_p, m_i), dy (B, n_p, m_e), dz (B, n_p, m_i), `status` (B: 0 computed,
+        1 skipped — not finite or s <= 0 —, 2 not factored; rows of the latter two are NaN) and `info`, one dict per
+        instance.  `iterate`: a BatchIterate, typically result.iterate.  n_p rounds of solves on one factorization."""
+        r = self._p.sensitivity_batch(iterate, parameters)
+        return BatchSensitivity(dx=r["dx"], ds=r["ds"], dy=r["dy"], dz=r["dz"], status=r["status"], info=r["info"])
+
+    def sensitivity_batch_jvp(self, iterate, parameters, dp) -> "BatchIterate":
+        """The tangents of the B end iterates along dp (B, n_p), one round of solves: a BatchIterate-shaped delta with
+        mu = 0, so that result.iterate + it is the warm start of the next batch:
+
+            r = problem.solve_batch(x0, parameters=rows, warm_start=BatchIterate())
+            it = r.iterate + problem.sensitivity_batch_jvp(r.iterate, rows, rows_next - rows)
+            r = problem.solve_batch(it.x, parameters=rows_next, warm_start=it)
+
+        `sensitivity_status` (B) and `sensitivity_info` (B dicts) are those of this call."""
+        r = self._p.sensitivity_batch_jvp(iterate, parameters, dp)
+        self.sensitivity_status, self.sensitivity_info = r["status"], r["info"]
+        return BatchIterate(x=r["dx"], s=r["ds"], y=r["dy"], z=r["dz"], mu=0.0)
+
+    def sensitivity_batch_vjp(self, iterate, parameters, v) -> np.ndarray:
+        """(d x*_b / d p_b)^T v_b (B, n_p) for cotangents v (B, n) on x, one round of solves whatever n_p.
+        `sensitivity_status` and `sensitivity_info` are those of this call."""
+        r = self._p.sensitivity_batch_vjp(iterate, parameters, v)
+        self.sensitivity_status, self.sensitivity_info = r["status"], r["info"]
+        return r["grad"]
+
+    def sensitivity_batch_rhs(self, iterate, parameters) -> np.ndarray:
+        """M (B, n_p, n + m_e + m_i): per instance and parameter r_x, r_e, r_i at its iterate; no factorization."""
+        r = self._p.sensitivity_batch_rhs(iterate, parameters)
+        self.sensitivity_status = r["status"]
+        return r["M"]
 
     def restoration_steps_batch(self, x, s, y, z, mu, steps, **kwargs):
         """`steps` iterations of feasibility restoration from each of B iterates (rows of x, s, y, z; mu of length B), in

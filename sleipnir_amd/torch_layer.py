@@ -7,6 +7,10 @@ needs torch.
     x = layer(p)                                # set_parameters(p); solve(); x*
     loss(x).backward()                          # p.grad = (dx*/dp)^T dloss/dx, one linear solve
 
+    layer = BatchSolveLayer(problem)            # a minibatch: rows (B, n_p) in, x* (B, n) out
+    x = layer(rows)                             # one solve_batch(parameters=rows), warm from the last forward
+    loss(x).backward()                          # rows.grad from ONE sensitivity_batch_vjp
+
 Plumbing, like the rest of the package: the tensors are float64 on the CPU, the work happens in libslpx on the device.
 """
 from __future__ import annotations
@@ -16,7 +20,7 @@ import torch
 
 from sleipnir_amd import optimization
 
-__all__ = ["SolveLayer"]
+__all__ = ["SolveLayer", "BatchSolveLayer"]
 
 
 class _Solve(torch.autograd.Function):
@@ -62,3 +66,61 @@ class SolveLayer:
 
     def __call__(self, parameters: torch.Tensor) -> torch.Tensor:
         return _Solve.apply(parameters, self)
+
+
+class _BatchSolve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, parameters, layer):
+        if parameters.dtype != torch.float64 or parameters.device.type != "cpu" or parameters.dim() != 2:
+            raise TypeError("BatchSolveLayer: the parameters must be a float64 tensor (B, n_p) on the CPU")
+        problem = layer.problem
+        rows = np.ascontiguousarray(parameters.detach().numpy())
+        B = rows.shape[0]
+        # warm from the iterates the previous forward ended at while the batch size stays; else from x0, duals cold
+        if layer.iterate is not None and np.shape(layer.iterate.x)[0] == B:
+            guesses, warm = layer.iterate.x, layer.iterate
+            layer.warm_forwards += 1
+        else:
+            n = len(problem._decision_variables)
+            x0 = problem._p.get_x() if layer.x0 is None else np.asarray(layer.x0, dtype=np.float64)
+            guesses, warm = np.ascontiguousarray(np.broadcast_to(x0, (B, n))), optimization.BatchIterate()
+        result = problem.solve_batch(guesses, parameters=rows, warm_start=warm, **layer.solve_kwargs)
+        layer.status, layer.iterate, layer.rows = result.status, result.iterate, rows.copy()
+        layer.solves += 1
+        ctx.layer, ctx.solve = layer, layer.solves
+        return torch.from_numpy(np.array(result.iterate.x, dtype=np.float64))
+
+    @staticmethod
+    def backward(ctx, grad_x):
+        layer = ctx.layer
+        if ctx.solve != layer.solves:
+            raise RuntimeError("BatchSolveLayer: backward of a forward that is not the layer's last (the sensitivities are "
+                               "those of the last batch)")
+        grad = layer.problem.sensitivity_batch_vjp(layer.iterate, layer.rows, grad_x.detach().cpu().to(torch.float64).numpy())
+        layer.sensitivity_status = np.array(layer.problem.sensitivity_status)
+        grad = np.where((layer.sensitivity_status != 0)[:, None], 0.0, grad)
+        return torch.from_numpy(np.ascontiguousarray(grad, dtype=np.float64)), None
+
+
+class BatchSolveLayer:
+    """x*_b(p_b) for a minibatch of parameter rows of `problem` (an optimization.Problem) in one solve_batch.
+
+    forward: a float64 CPU tensor (B, n_p) -> solve_batch(parameters=rows, warm_start=...), warm from the previous forward's
+    iterates while B is unchanged (else from x0 — (n) or (B, n); None: the variables' values — with the duals cold), and
+    x* (B, n); `status` holds the instances' ExitStatus and is not judged here.  backward: ONE sensitivity_batch_vjp, valid
+    for the layer's LAST forward only; an instance that could not be differentiated (`sensitivity_status` != 0) gets a
+    zero gradient row."""
+
+    def __init__(self, problem: optimization.Problem, x0=None, **solve_kwargs):
+        self.problem = problem
+        self.x0 = x0
+        self.solve_kwargs = solve_kwargs
+        self.iterate = None
+        self.rows = None
+        self.status = None
+        self.sensitivity_status = None
+        self.solves = 0
+        self.warm_forwards = 0  # forwards that began at the previous forward's iterates
+
+    def __call__(self, parameters: torch.Tensor) -> torch.Tensor:
+        return _BatchSolve.apply(parameters, self)
