@@ -361,6 +361,30 @@ int slpx_problem_sensitivity_jvp(slpx_problem* p, const double* dp, double* dx, 
 /* The vector-Jacobian product for a cotangent vx[n] on x: grad_p[q] = sum_i vx[i] dx_i/dp_q, from ONE solve K w = [vx; 0]
  * and grad_p[q] = w^T R[:, q], R the right-hand sides above (K is symmetric, also when regularized). */
 int slpx_problem_sensitivity_vjp(slpx_problem* p, const double* vx, double* grad_p, slpx_sensitivity_info* info);
+/* THE FULL VJP: cotangents on the whole end iterate and on the optimal cost, still ONE solve on the kept factorization.
+ * `cost` is the value the solve reports as the cost: f as slpx_problem_minimize / slpx_problem_maximize stored it (a
+ * maximized objective is stored negated, and so is reported and differentiated), in the user's units.  Forward, per
+ * parameter q, beside the equations above:    dcost = g . dx + f_p[q]       g = grad_x f, f_p[q] = df/dp_q
+ * Reverse, for cotangents vx[n], vs[m_i], vy[m_e], vz[m_i], vcost[1]:
+ *     t = vs - Sigma o vz        u = vx + A_i^T t + vcost g        K w = [u; -vy]
+ *     grad_p[q] = w^T R[:, q] + t . r_i[:, q] + vcost f_p[q]
+ * the adjoint of ds = A_i dx + r_i, dz = -Sigma ds folded into the right-hand side of the one solve, refined like every
+ * other; K is symmetric also when regularized and the forward products use the same K, so <v, J dp> = <J^T v, dp> holds
+ * to the accuracy of the solves.  A member that is NULL is absent and its terms are skipped (not added as zeros): with
+ * vx alone this is slpx_problem_sensitivity_vjp bit for bit.  All members NULL is an error ("no cotangent"); a cotangent
+ * on rows the model does not have (vs with m_i = 0) is ignored.  vcost = 1 alone gives the gradient of the optimal cost
+ * in one solve instead of the n_p of the Jacobian route.  For an interior-point model that is the derivative of f at the
+ * barrier problem's solution, O(mu) from the model's — NOT the derivative of the barrier function f - mu sum log s.
+ * cotangent_bytes: sizeof(slpx_cotangent) as the caller's header has it (members beyond it are absent), like
+ * options_bytes.  Batched: vx[B][n], vs[B][m_i], vy[B][m_e], vz[B][m_i], vcost[B]; status[b] = 1 for an instance with a
+ * value that is not finite in ANY given cotangent row (its gradient row is NaN, the others do not notice).  Everything
+ * the two vjp entry points promise — factorizations = 0 on a kept factorization, nothing of the problem moved, a
+ * following solve keeps every bit — holds for these. */
+typedef struct slpx_cotangent {
+  const double *vx, *vs, *vy, *vz, *vcost;
+} slpx_cotangent;
+int slpx_problem_sensitivity_vjp_full(slpx_problem* p, const slpx_cotangent* v, uint32_t cotangent_bytes, double* grad_p,
+                                      slpx_sensitivity_info* info);
 /* M[n_p][n + m_e + m_i]: r_x, r_e, r_i per parameter, at the iterate.  Neither factors nor solves. */
 int slpx_problem_sensitivity_rhs(slpx_problem* p, double* M);
 
@@ -412,6 +436,10 @@ int slpx_problem_sensitivity_batch_jvp(slpx_problem* p, int32_t B, const double*
 int slpx_problem_sensitivity_batch_vjp(slpx_problem* p, int32_t B, const double* x, const double* s, const double* y,
                                        const double* z, const double* mu, const double* params, const double* vx, double* grad_p,
                                        int32_t* status, slpx_sensitivity_info* info);
+/* The full vjp (above) per instance: cotangent rows per instance, grad_p[B][n_p]. */
+int slpx_problem_sensitivity_batch_vjp_full(slpx_problem* p, int32_t B, const double* x, const double* s, const double* y,
+                                            const double* z, const double* mu, const double* params, const slpx_cotangent* v,
+                                            uint32_t cotangent_bytes, double* grad_p, int32_t* status, slpx_sensitivity_info* info);
 /* M[B][n_p][n + m_e + m_i]: r_x, r_e, r_i per instance and parameter.  Neither factors nor solves. */
 int slpx_problem_sensitivity_batch_rhs(slpx_problem* p, int32_t B, const double* x, const double* s, const double* y,
                                        const double* z, const double* mu, const double* params, double* M, int32_t* status);

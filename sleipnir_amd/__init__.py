@@ -68,6 +68,12 @@ class WarmStart(ctypes.Structure):
     _fields_ = [("s", ctypes.c_void_p), ("y", ctypes.c_void_p), ("z", ctypes.c_void_p), ("mu", ctypes.c_double)]
 
 
+class Cotangent(ctypes.Structure):
+    """slpx_cotangent: cotangents on x, s, y, z and on the optimal cost (NULL: absent)."""
+    _fields_ = [("vx", ctypes.c_void_p), ("vs", ctypes.c_void_p), ("vy", ctypes.c_void_p), ("vz", ctypes.c_void_p),
+                ("vcost", ctypes.c_void_p)]
+
+
 class SensitivityInfo(ctypes.Structure):
     """slpx_sensitivity_info: what one sensitivity call did (include/slpx.h: solution sensitivities)."""
     _fields_ = [("n_p", ctypes.c_int32), ("solves", ctypes.c_int32), ("factorizations", ctypes.c_int32),
@@ -216,6 +222,11 @@ def lib() -> ctypes.CDLL:
         sig("slpx_problem_sensitivity_jvp", ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.POINTER(SensitivityInfo))
         sig("slpx_problem_sensitivity_vjp", ctypes.c_int, vp, vp, vp, ctypes.POINTER(SensitivityInfo))
         sig("slpx_problem_sensitivity_rhs", ctypes.c_int, vp, vp)
+    if hasattr(L, "slpx_problem_sensitivity_vjp_full"):
+        sig("slpx_problem_sensitivity_vjp_full", ctypes.c_int, vp, ctypes.POINTER(Cotangent), ctypes.c_uint32, vp,
+            ctypes.POINTER(SensitivityInfo))
+        sig("slpx_problem_sensitivity_batch_vjp_full", ctypes.c_int, vp, i32, vp, vp, vp, vp, vp, vp, ctypes.POINTER(Cotangent),
+            ctypes.c_uint32, vp, vp, vp)
     if hasattr(L, "slpx_problem_sensitivity_batch"):
         rows = (vp, i32, vp, vp, vp, vp, vp, vp)  # problem, B, x, s, y, z, mu, params
         sig("slpx_problem_sensitivity_batch", ctypes.c_int, *rows, vp, vp, vp, vp, vp, vp)
@@ -405,6 +416,36 @@ class Problem:
             raise SlpxError(lib().slpx_last_error().decode())
         return grad[:n_p], self._sensitivity_info(info)
 
+    @staticmethod
+    def _cotangent(who, shapes, x, s, y, z, cost):
+        """(slpx_cotangent, the arrays it points into): `shapes` the shape of each of x, s, y, z, cost; None is absent, and
+        so is a cotangent on rows the model does not have."""
+        c, hold = Cotangent(), []
+        for field, name, v in (("vx", "x", x), ("vs", "s", s), ("vy", "y", y), ("vz", "z", z), ("vcost", "cost", cost)):
+            if v is None:
+                continue
+            a = np.ascontiguousarray(np.asarray(v, dtype=np.float64))
+            want = shapes[name]
+            if a.size != int(np.prod(want)):
+                raise SlpxError(f"{who}: the cotangent on {name} must have shape {tuple(want)}")
+            # (an empty one still counts as given: the library ignores it, and says "no cotangent" only when all are None)
+            hold.append(a if a.size else np.zeros(1))
+            setattr(c, field, hold[-1].ctypes.data)
+        return c, hold
+
+    def sensitivity_vjp_full(self, x=None, s=None, y=None, z=None, cost=None):
+        """The vjp for cotangents on the whole end iterate and on the optimal cost — x (n), s (m_i), y (m_e), z (m_i),
+        cost (a number), None: absent — from ONE solve (slpx_problem_sensitivity_vjp_full): (grad (n_p), info)."""
+        fn = self._sensitivity_entry("slpx_problem_sensitivity_vjp_full")
+        n, me, mi = self.dims
+        n_p = max(0, lib().slpx_problem_parameters(self._h, None, 0))
+        c, hold = self._cotangent("sensitivity_vjp_full", {"x": (n,), "s": (mi,), "y": (me,), "z": (mi,), "cost": (1,)}, x, s, y, z, cost)
+        grad = np.zeros(max(1, n_p))
+        info = SensitivityInfo()
+        if fn(self._h, ctypes.byref(c), ctypes.sizeof(c), grad.ctypes.data, ctypes.byref(info)) != 0:
+            raise SlpxError(lib().slpx_last_error().decode())
+        return grad[:n_p], self._sensitivity_info(info)
+
     def sensitivity_rhs(self):
         """M (n_p, n + m_e + m_i): per parameter r_x = d(grad_x L)/dp, r_e = dc_e/dp, r_i = dc_i/dp at the end iterate
         (slpx_problem_sensitivity_rhs)."""
@@ -493,6 +534,22 @@ class Problem:
         out = {"grad": np.zeros((B, n_p)), "status": np.zeros(B, dtype=np.int32)}
         info = (SensitivityInfo * max(1, B))()
         if fn(self._h, B, *ptrs, vx.ctypes.data if vx.size else None, out["grad"].ctypes.data if out["grad"].size else None,
+              out["status"].ctypes.data if B else None, info) != 0:
+            raise SlpxError(lib().slpx_last_error().decode())
+        out["info"] = self._batch_info(info[:B])
+        return out
+
+    def sensitivity_batch_vjp_full(self, iterate, parameters, x=None, s=None, y=None, z=None, cost=None):
+        """The full vjp per instance for cotangent rows x (B, n), s (B, m_i), y (B, m_e), z (B, m_i), cost (B), None:
+        absent, one round of solves (slpx_problem_sensitivity_batch_vjp_full): dict(grad (B, n_p), status, info)."""
+        fn = self._sensitivity_entry("slpx_problem_sensitivity_batch_vjp_full")
+        B, n_p, hold, ptrs = self._batch_rows(iterate, parameters, "sensitivity_batch_vjp_full")
+        n, me, mi = self.dims
+        c, hold_c = self._cotangent("sensitivity_batch_vjp_full",
+                                    {"x": (B, n), "s": (B, mi), "y": (B, me), "z": (B, mi), "cost": (B,)}, x, s, y, z, cost)
+        out = {"grad": np.zeros((B, n_p)), "status": np.zeros(B, dtype=np.int32)}
+        info = (SensitivityInfo * max(1, B))()
+        if fn(self._h, B, *ptrs, ctypes.byref(c), ctypes.sizeof(c), out["grad"].ctypes.data if out["grad"].size else None,
               out["status"].ctypes.data if B else None, info) != 0:
             raise SlpxError(lib().slpx_last_error().decode())
         out["info"] = self._batch_info(info[:B])

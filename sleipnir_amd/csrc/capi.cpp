@@ -279,6 +279,34 @@ int slpx_problem_sensitivity_vjp(slpx_problem* p, const double* vx, double* grad
     sensitivity_info_out(si, info);
   });
 }
+namespace {
+// the caller's slpx_cotangent, as many bytes of it as the caller's header knows (like slpx_options); all absent: an error
+slpx_cotangent cotangent_in(const slpx_cotangent* v, uint32_t cotangent_bytes, const char* who) {
+  slpx_cotangent c{};
+  if (v != nullptr) std::memcpy(&c, v, std::min<size_t>(cotangent_bytes, sizeof(c)));
+  if (!c.vx && !c.vs && !c.vy && !c.vz && !c.vcost) throw std::runtime_error(std::string(who) + ": no cotangent (every member is NULL)");
+  return c;
+}
+std::span<const double> cotangent_rows(const double* a, size_t count) { return a ? std::span<const double>(a, count) : std::span<const double>(); }
+}  // namespace
+int slpx_problem_sensitivity_vjp_full(slpx_problem* p, const slpx_cotangent* v, uint32_t cotangent_bytes, double* grad_p,
+                                      slpx_sensitivity_info* info) {
+  return guard([&] {
+    sensitivity_preconditions(p, "slpx_problem_sensitivity_vjp_full");
+    const slpx_cotangent c = cotangent_in(v, cotangent_bytes, "slpx_problem_sensitivity_vjp_full");
+    const size_t n = p->problem.decision_variables().size(), m_e = p->problem.equality_constraints().size(),
+                 m_i = p->problem.inequality_constraints().size();
+    slp::ProblemF64::Cotangent ct{cotangent_rows(c.vx, n), cotangent_rows(c.vs, m_i), cotangent_rows(c.vy, m_e), cotangent_rows(c.vz, m_i),
+                                  cotangent_rows(c.vcost, 1)};
+    // (given, but on rows the model does not have: ignored — what is left may be nothing, and the gradient zero)
+    slpx::SensitivityInfo si;
+    const std::vector<double> zeros(n, 0.0);
+    if (ct.x.empty() && ct.s.empty() && ct.y.empty() && ct.z.empty() && ct.cost.empty()) ct.x = zeros;
+    const std::vector<double> g = p->problem.sensitivity_vjp(ct, &si);
+    if (grad_p) std::copy(g.begin(), g.end(), grad_p);
+    sensitivity_info_out(si, info);
+  });
+}
 int slpx_problem_sensitivity_rhs(slpx_problem* p, double* M) {
   return guard([&] {
     sensitivity_preconditions(p, "slpx_problem_sensitivity_rhs");
@@ -353,6 +381,22 @@ int slpx_problem_sensitivity_batch_vjp(slpx_problem* p, int32_t B, const double*
     batch_sensitivity_args(a, p, B, x, s, y, z, mu, params, "slpx_problem_sensitivity_batch_vjp");
     if (vx == nullptr) throw std::runtime_error("slpx_problem_sensitivity_batch_vjp: vx is null");
     const auto r = p->problem.sensitivity_batch_vjp(B, a.it, a.params, std::span<const double>(vx, a.B * a.n));
+    if (grad_p) std::copy(r.grad.begin(), r.grad.end(), grad_p);
+    batch_sensitivity_out(r, nullptr, nullptr, nullptr, nullptr, status, info);
+  });
+}
+int slpx_problem_sensitivity_batch_vjp_full(slpx_problem* p, int32_t B, const double* x, const double* s, const double* y,
+                                            const double* z, const double* mu, const double* params, const slpx_cotangent* v,
+                                            uint32_t cotangent_bytes, double* grad_p, int32_t* status, slpx_sensitivity_info* info) {
+  return guard([&] {
+    BatchSensitivityArgs a;
+    batch_sensitivity_args(a, p, B, x, s, y, z, mu, params, "slpx_problem_sensitivity_batch_vjp_full");
+    const slpx_cotangent c = cotangent_in(v, cotangent_bytes, "slpx_problem_sensitivity_batch_vjp_full");
+    slp::ProblemF64::BatchCotangent ct{cotangent_rows(c.vx, a.B * a.n), cotangent_rows(c.vs, a.B * a.m_i), cotangent_rows(c.vy, a.B * a.m_e),
+                                       cotangent_rows(c.vz, a.B * a.m_i), cotangent_rows(c.vcost, a.B)};
+    const std::vector<double> zeros(a.B * a.n, 0.0);
+    if (ct.x.empty() && ct.s.empty() && ct.y.empty() && ct.z.empty() && ct.cost.empty()) ct.x = zeros;  // (all on rows the model lacks)
+    const auto r = p->problem.sensitivity_batch_vjp(B, a.it, a.params, ct);
     if (grad_p) std::copy(r.grad.begin(), r.grad.end(), grad_p);
     batch_sensitivity_out(r, nullptr, nullptr, nullptr, nullptr, status, info);
   });

@@ -75,6 +75,19 @@ SensPlan build_sens_plan(const NlpStructure& model, const NlpStructure& ext) {
         p.ai_src[at] = model.off_Ai + t;
       }
   }
+
+  // the cost's gradient over x in V, and its parameter columns in V'
+  const auto one_entry = [](const CscPattern& g, int col, int off) -> int32_t {
+    const int32_t first = g.colptr[col], count = g.colptr[col + 1] - first;
+    if (count > 1) throw std::runtime_error("slpx: sensitivity plan: a column of the cost's gradient has more than one entry");
+    return count == 1 ? off + first : -1;
+  };
+  if (static_cast<int>(model.g_pat.colptr.size()) != n + 1 || static_cast<int>(ext.g_pat.colptr.size()) != ext.n + 1)
+    throw std::runtime_error("slpx: sensitivity plan: the pattern of the cost's gradient is not over the variables");
+  p.g_src.resize(n);
+  p.fp_src.resize(n_p);
+  for (int i = 0; i < n; ++i) p.g_src[i] = one_entry(model.g_pat, i, model.off_g);
+  for (int q = 0; q < n_p; ++q) p.fp_src[q] = one_entry(ext.g_pat, n + q, ext.off_g);
   return p;
 }
 
@@ -113,6 +126,47 @@ void sens_host_vjp(const SensPlan& p, const double* R, const double* w, double* 
     for (int width = kSensVjpThreads / 2; width > 0; width >>= 1)
       for (int t = 0; t < width; ++t) part[t] = part[t] + part[t + width];
     grad[q] = part[0];
+  }
+}
+
+void sens_host_adjoint_rhs(const SensPlan& p, const double* V, const double* s, const double* z, const SensCotangent& v, double* rhs) {
+  for (int row = 0; row < p.dim; ++row)
+    rhs[row] = sens_adjoint_rhs_entry(p.n, p.red_ptr.data(), p.red_src.data(), p.red_row.data(), p.g_src.data(), V, s, z, v.vx, v.vs, v.vy,
+                                      v.vz, v.vcost, row);
+}
+
+void sens_host_vjp_full(const SensPlan& p, const double* Vx, const double* M, const double* R, const double* s, const double* z,
+                        const double* w, const SensCotangent& v, double* grad) {
+  const auto fold = [](double* part) {
+    for (int width = kSensVjpThreads / 2; width > 0; width >>= 1)
+      for (int t = 0; t < width; ++t) part[t] = part[t] + part[t + width];
+    return part[0];
+  };
+  const bool direct = sens_adjoint_has_t(p.m_i, v.vs, v.vz);
+  for (int q = 0; q < p.n_p; ++q) {
+    double part[kSensVjpThreads], part_t[kSensVjpThreads];
+    for (int t = 0; t < kSensVjpThreads; ++t) part[t] = sens_vjp_partial(p.dim, R + static_cast<int64_t>(q) * p.dim, w, t);
+    const double wR = fold(part);
+    double tr = 0.0;
+    if (direct) {
+      const double* r_i = M + static_cast<int64_t>(q) * p.dimM + p.dim;
+      for (int t = 0; t < kSensVjpThreads; ++t) part_t[t] = sens_adjoint_direct_partial(p.m_i, r_i, s, z, v.vs, v.vz, t);
+      tr = fold(part_t);
+    }
+    grad[q] = sens_vjp_full_sum(wR, direct, tr, v.vcost, p.fp_src[q], Vx);
+  }
+}
+
+void sens_classify_extras(int B, const SensExtraRows* extras, int count, int32_t* status) {
+  for (int b = 0; b < B; ++b) {
+    bool ok = true;
+    for (int k = 0; k < count && ok; ++k) {
+      if (extras[k].rows == nullptr) continue;
+      const double* row = extras[k].rows + static_cast<int64_t>(b) * extras[k].width;
+      for (int i = 0; i < extras[k].width; ++i)
+        if (!(row[i] - row[i] == 0.0)) ok = false;
+    }
+    status[b] = ok ? kSensComputed : kSensSkipped;
   }
 }
 

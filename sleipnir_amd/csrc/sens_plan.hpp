@@ -45,6 +45,10 @@ struct SensPlan {
 
   // expansion: A_i by rows, columns ascending: (A_i dx)[j] = sum_t V[ai_src[t]] * dx[ai_col[t]], t in [ai_rowptr[j], ai_rowptr[j + 1])
   std::vector<int32_t> ai_rowptr, ai_col, ai_src;
+
+  // the cost's derivatives, for the cotangent on the optimal cost (the adjoint below): g_i = V[g_src[i]], i < n, and
+  // f_p[q] = ∂f/∂p_q = V'[fp_src[q]] (column n + q of the extended structure's g_pat); −1 where the pattern has no entry
+  std::vector<int32_t> g_src, fp_src;
 };
 
 // `model`: the structure of the model over x; `extended`: the same model over [x ; p] (n + n_p variables, the same
@@ -62,6 +66,21 @@ void sens_host_expand(const SensPlan& p, const double* V, const double* s, const
 // grad [n_p]: grad[q] = wᵀ R[:, q], w [dim]
 void sens_host_vjp(const SensPlan& p, const double* R, const double* w, double* grad);
 
+// ---- the adjoint of the whole map p -> (x, s, y, z, cost), cost = f at the iterate (include/slpx.h: "the full vjp") ----
+// Forward, per parameter q:  K [dx; −dy] = R[:, q]   ds = A_i dx + r_i   dz = −Σ ds   dcost = g·dx + f_p[q].
+// Reverse, for cotangents vx [n], vs [m_i], vy [m_e], vz [m_i], vcost [1], any of them absent (null):
+//   t = vs − Σ ∘ vz      u = vx + A_iᵀ t + vcost g      K w = [u; −vy]      grad_q = wᵀR[:, q] + t·r_i[:, q] + vcost f_p[q]
+// A term whose cotangent is absent is skipped, not added as zero: with vx alone the right-hand side is [vx; 0] and
+// the gradient wᵀR, bit for bit sens_host_vjp's.
+struct SensCotangent {
+  const double *vx = nullptr, *vs = nullptr, *vy = nullptr, *vz = nullptr, *vcost = nullptr;
+};
+// V [nV], s, z [m_i] -> rhs [dim] = [u; −vy]
+void sens_host_adjoint_rhs(const SensPlan& p, const double* V, const double* s, const double* z, const SensCotangent& v, double* rhs);
+// Vx = V' [nVx], M [n_p * dimM], R [n_p * dim], s, z [m_i], w [dim] -> grad [n_p]
+void sens_host_vjp_full(const SensPlan& p, const double* Vx, const double* M, const double* R, const double* s, const double* z,
+                        const double* w, const SensCotangent& v, double* grad);
+
 // ---- batched calls: which instances are differentiated at all (include/slpx.h: batched sensitivities) ----
 // The per-instance outcome of a batched sensitivity call (slpx.h: status[B]).
 constexpr int32_t kSensComputed = 0;     // differentiated
@@ -73,5 +92,13 @@ constexpr int32_t kSensNotFactored = 2;  // the KKT system at its iterate could 
 void sens_classify_instances(int B, int n, int m_e, int m_i, int n_p, const double* x, const double* s, const double* y,
                              const double* z, const double* mu, const double* params, const double* extra, int n_extra,
                              int32_t* status);
+// The same for several arrays beside the iterate — the cotangents of the full vjp: status[b] = kSensSkipped where row b of
+// ANY given array (rows [B][width]; a null one, or one without entries, is not looked at) holds a value that is not
+// finite, kSensComputed otherwise.  A pure function.
+struct SensExtraRows {
+  const double* rows = nullptr;
+  int width = 0;
+};
+void sens_classify_extras(int B, const SensExtraRows* extras, int count, int32_t* status);
 
 }  // namespace slpx

@@ -75,4 +75,55 @@ SLPX_SENS double sens_vjp_partial(int dim, const double* Rq, const double* w, in
   return acc;
 }
 
+// ---- the adjoint: cotangents on x, s, y, z and on the cost (sens_plan.hpp: the adjoint) ----
+// A null cotangent is absent and its term is skipped; one on rows the model does not have is absent too.
+
+// whether t = vs − Σ ∘ vz has any term
+SLPX_SENS bool sens_adjoint_has_t(int m_i, const double* vs, const double* vz) { return m_i > 0 && (vs != nullptr || vz != nullptr); }
+
+// t[j] = vs[j] − (z_j / s_j) vz[j] (sens_adjoint_has_t holds)
+SLPX_SENS double sens_adjoint_t_entry(const double* s, const double* z, const double* vs, const double* vz, int j) {
+#pragma clang fp contract(off) reassociate(off)
+  if (vz == nullptr) return vs[j];
+  const double sigma = z[j] / s[j];
+  if (vs == nullptr) return -(sigma * vz[j]);
+  return __builtin_fma(-sigma, vz[j], vs[j]);
+}
+
+// entry `row` < n + m_e of the adjoint's right-hand side [u; −vy]: above the equality rows
+//   vx[row] + sum_j A_i[j, row] t_j + vcost g_row
+// with the entries of column `row` of A_i in pattern order and t_j recomputed in place (as sens_reduced_entry
+// recomputes r_i), below them −vy.  With vx alone: [vx; 0], the bits of vx.
+SLPX_SENS double sens_adjoint_rhs_entry(int n, const int32_t* red_ptr, const int32_t* red_src, const int32_t* red_row, const int32_t* g_src,
+                                        const double* V, const double* s, const double* z, const double* vx, const double* vs,
+                                        const double* vy, const double* vz, const double* vcost, int row) {
+#pragma clang fp contract(off) reassociate(off)
+  if (row >= n) return vy != nullptr ? -vy[row - n] : 0.0;
+  double acc = vx != nullptr ? vx[row] : 0.0;
+  if (vs != nullptr || vz != nullptr)
+    for (int32_t t = red_ptr[row]; t < red_ptr[row + 1]; ++t)
+      acc = __builtin_fma(V[red_src[t]], sens_adjoint_t_entry(s, z, vs, vz, red_row[t]), acc);
+  if (vcost != nullptr && g_src[row] >= 0) acc = __builtin_fma(vcost[0], V[g_src[row]], acc);
+  return acc;
+}
+
+// t · r_i[:, q] in the order of sens_vjp_partial: lane t of kSensVjpThreads sums the rows t, t + kSensVjpThreads, ...
+// ascending, the lanes' sums folded pairwise like those of wᵀR.  r_i: M[q] + n + m_e.
+SLPX_SENS double sens_adjoint_direct_partial(int m_i, const double* r_i, const double* s, const double* z, const double* vs,
+                                             const double* vz, int lane) {
+#pragma clang fp contract(off) reassociate(off)
+  double acc = 0.0;
+  for (int j = lane; j < m_i; j += kSensVjpThreads) acc = __builtin_fma(sens_adjoint_t_entry(s, z, vs, vz, j), r_i[j], acc);
+  return acc;
+}
+
+// grad[q] = (wᵀR) + (t·r_i) + vcost f_p[q], in that order; a term that is absent is skipped
+SLPX_SENS double sens_vjp_full_sum(double wR, bool direct, double tr, const double* vcost, int32_t fp_src, const double* Vx) {
+#pragma clang fp contract(off) reassociate(off)
+  double acc = wR;
+  if (direct) acc = acc + tr;
+  if (vcost != nullptr && fp_src >= 0) acc = __builtin_fma(vcost[0], Vx[fp_src], acc);
+  return acc;
+}
+
 }  // namespace slpx

@@ -1,13 +1,15 @@
 // The kernels of the solution sensitivities and their drivers (sensitivity.hpp): one problem (Sensitivity) and B
 // instances at once (BatchSensitivity).  Opt-in: nothing on the path of a solve comes here.
 //
-// Four kernels, all row-local gathers — one lane computes one output entry with the row formulas of sens_rows.h, the
+// Six kernels, all row-local gathers — one lane computes one output entry with the row formulas of sens_rows.h, the
 // bodies the host executor (sens_plan.cpp) runs — so an entry's bits do not depend on the launch geometry, on the batch
 // size, on the instance's position or on its neighbours:
 //   sens_rhs_kernel      V' (extended sweep), V, s, z -> every column of M and of R in one launch
 //   sens_combine_kernel  R dp and (dc_i/dp) dp for the jvp
 //   sens_expand_kernel   [dx; -dy] -> dx, ds = A_i dx + r_i, dy, dz = -Sigma ds, straight into the caller's layout
 //   sens_vjp_kernel      w^T R[:, q], one workgroup per parameter, lanes and fold in the fixed order of sens_rows.h
+//   sens_adjoint_rhs_kernel  the full vjp's right-hand side [vx + A_i^T t + vcost g; -vy], t = vs - Sigma o vz (sens_plan.hpp)
+//   sens_vjp_full_kernel     w^T R[:, q] + t . r_i[:, q] + vcost f_p[q]: two dot products in sens_vjp_kernel's order, side by side
 // THE GRID.  blockIdx.y is the instance (at most 65535 of them: one grid slice each) and every buffer has an instance
 // stride, 0 or unused for one problem.  blockIdx.x runs over the entries of ONE instance with the columns folded in —
 // (parameter, row) for rhs and expand.  A batched launch uses workgroups of one wave (kSensBatchThreads): the models
@@ -106,6 +108,47 @@ __global__ __launch_bounds__(kSensVjpThreads) void sens_vjp_kernel(SensDev d, co
   if (t == 0) grad[b * d.n_p + q] = part[0];
 }
 
+// v: the cotangents of the call on the device (null: absent), instance b's rows at vx + b * n, vs + b * m_i, vy + b * m_e,
+// vz + b * m_i, vcost + b.  Row `row` < dim of instance blockIdx.y: rhs [b][dim], the buffer the solve is given.
+__global__ __launch_bounds__(kSensThreads) void sens_adjoint_rhs_kernel(SensDev d, const double* __restrict__ V, long long V_stride,
+                                                                       const double* __restrict__ s, const double* __restrict__ z,
+                                                                       long long sz_stride, SensCotangent v, double* __restrict__ rhs) {
+  const int row = static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x);
+  if (row >= d.dim) return;
+  const int64_t b = blockIdx.y;
+  rhs[b * d.dim + row] = sens_adjoint_rhs_entry(d.n, d.red_ptr, d.red_src, d.red_row, d.g_src, V + b * V_stride, s + b * sz_stride,
+                                                z + b * sz_stride, v.vx ? v.vx + b * d.n : nullptr, v.vs ? v.vs + b * d.m_i : nullptr,
+                                                v.vy ? v.vy + b * d.m_e : nullptr, v.vz ? v.vz + b * d.m_i : nullptr,
+                                                v.vcost ? v.vcost + b : nullptr, row);
+}
+
+// workgroup (q, b): grad [b][q] = w[b]^T R[b][:, q] + t[b] . r_i[b][:, q] + vcost[b] f_p[b][q]
+__global__ __launch_bounds__(kSensVjpThreads) void sens_vjp_full_kernel(SensDev d, const double* __restrict__ M, const double* __restrict__ R,
+                                                                       const double* __restrict__ w, const double* __restrict__ Vx,
+                                                                       long long Vx_stride, const double* __restrict__ s,
+                                                                       const double* __restrict__ z, long long sz_stride, SensCotangent v,
+                                                                       double* __restrict__ grad) {
+  __shared__ double part[kSensVjpThreads], part_t[kSensVjpThreads];
+  const int q = static_cast<int>(blockIdx.x);
+  const int64_t b = blockIdx.y;
+  const int t = static_cast<int>(threadIdx.x);
+  const double* vs = v.vs ? v.vs + b * d.m_i : nullptr;
+  const double* vz = v.vz ? v.vz + b * d.m_i : nullptr;
+  const bool direct = sens_adjoint_has_t(d.m_i, vs, vz);  // (uniform over the workgroup)
+  part[t] = sens_vjp_partial(d.dim, R + (b * d.n_p + q) * d.dim, w + b * d.dim, t);
+  part_t[t] = direct ? sens_adjoint_direct_partial(d.m_i, M + (b * d.n_p + q) * d.dimM + d.dim, s + b * sz_stride, z + b * sz_stride, vs, vz, t)
+                     : 0.0;
+  __syncthreads();
+  for (int width = kSensVjpThreads / 2; width > 0; width >>= 1) {
+    if (t < width) {
+      part[t] = part[t] + part[t + width];
+      part_t[t] = part_t[t] + part_t[t + width];
+    }
+    __syncthreads();
+  }
+  if (t == 0) grad[b * d.n_p + q] = sens_vjp_full_sum(part[0], direct, part_t[0], v.vcost ? v.vcost + b : nullptr, d.fp_src[q], Vx + b * Vx_stride);
+}
+
 namespace {
 using clk = std::chrono::steady_clock;
 double seconds_since(clk::time_point t0) { return std::chrono::duration<double>(clk::now() - t0).count(); }
@@ -136,7 +179,10 @@ Sensitivity::Sensitivity(NewtonSystem& model, NodeId f) : m_model(model) {
   m_ai_rowptr.upload(p.ai_rowptr);
   m_ai_col.upload(p.ai_col);
   m_ai_src.upload(p.ai_src);
+  m_g_src.upload(p.g_src);
+  m_fp_src.upload(p.fp_src);
   const size_t n_p = static_cast<size_t>(p.n_p);
+  m_cot.alloc(static_cast<size_t>(p.n + 2 * p.m_i + p.m_e + 1));
   m_M.alloc(n_p * p.dimM);
   m_R.alloc(n_p * p.dim);
   m_V.alloc(static_cast<size_t>(p.nV));
@@ -159,7 +205,7 @@ Sensitivity::~Sensitivity() = default;
 SensDev Sensitivity::view() const {
   const SensPlan& p = m_plan;
   return SensDev{p.n, p.n_p, p.m_e, p.m_i, p.dim, p.dimM, m_m_ptr.p, m_m_src.p, m_red_ptr.p, m_red_src.p, m_red_row.p,
-                 m_ai_rowptr.p, m_ai_col.p, m_ai_src.p};
+                 m_ai_rowptr.p, m_ai_col.p, m_ai_src.p, m_g_src.p, m_fp_src.p};
 }
 
 // Both systems at the iterate, unit scales, the user's units: V' and V swept, M and R written, the model's lhs
@@ -315,20 +361,45 @@ void Sensitivity::jvp(const Point& at, const double* dp, double* dx, double* ds,
 }
 
 void Sensitivity::vjp(const Point& at, const double* vx, double* grad, SensitivityInfo& info) {
-  const auto t0 = clk::now();
-  const SensPlan& p = m_plan;
   if (vx == nullptr) throw std::runtime_error("slpx: sensitivity vjp: vx is null");
+  SensCotangent v;
+  v.vx = vx;
+  vjp_full(at, v, grad, info);
+}
+
+void Sensitivity::vjp_full(const Point& at, const SensCotangent& given, double* grad, SensitivityInfo& info) {
+  const auto t0 = clk::now();
+  if (!given.vx && !given.vs && !given.vy && !given.vz && !given.vcost) throw std::runtime_error("slpx: sensitivity vjp: no cotangent");
+  const SensPlan& p = m_plan;
   info.n_p = p.n_p;
   info.t_compile = take_compile_seconds();
   factor(at, info);
   DeviceNlp& dev = m_model.device();
   const hipStream_t st = dev.stream();
-  std::vector<double> rhs(static_cast<size_t>(p.dim), 0.0);  // [vx; 0]
-  std::copy(vx, vx + p.n, rhs.begin());
-  SLPX_HIP_CHECK(hipMemcpyAsync(m_rhs1.p, rhs.data(), rhs.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  SLPX_HIP_CHECK(hipStreamSynchronize(st));
+  // the cotangents behind one another, as they lie in m_cot; one on rows the model does not have is absent
+  std::vector<double> host;
+  SensCotangent v;
+  const auto place = [&](const double* from, int count, const double*& on_device) {
+    if (from == nullptr || count == 0) return;
+    on_device = m_cot.p + host.size();
+    host.insert(host.end(), from, from + count);
+  };
+  place(given.vx, p.n, v.vx);
+  place(given.vs, p.m_i, v.vs);
+  place(given.vy, p.m_e, v.vy);
+  place(given.vz, p.m_i, v.vz);
+  place(given.vcost, 1, v.vcost);
+  if (!host.empty()) SLPX_HIP_CHECK(hipMemcpyAsync(m_cot.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(sens_adjoint_rhs_kernel, dim3(blocks_for(p.dim)), dim3(kSensThreads), 0, st, view(), m_V.p, 0LL, m_s.p, m_z.p, 0LL, v, m_rhs1.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  SLPX_HIP_CHECK(hipStreamSynchronize(st));  // (`host` is this function's)
   solve_one(m_rhs1.p, m_sol.p, info);
-  hipLaunchKernelGGL(sens_vjp_kernel, dim3(p.n_p, 1), dim3(kSensVjpThreads), 0, st, view(), m_R.p, m_sol.p, m_grad.p);
+  // (w^T R alone — a cotangent on x, or on y — is sens_vjp_kernel's, as before there were others)
+  if (!sens_adjoint_has_t(p.m_i, v.vs, v.vz) && v.vcost == nullptr)
+    hipLaunchKernelGGL(sens_vjp_kernel, dim3(p.n_p, 1), dim3(kSensVjpThreads), 0, st, view(), m_R.p, m_sol.p, m_grad.p);
+  else
+    hipLaunchKernelGGL(sens_vjp_full_kernel, dim3(p.n_p, 1), dim3(kSensVjpThreads), 0, st, view(), m_M.p, m_R.p, m_sol.p, m_ext->device().d_V(),
+                       0LL, m_s.p, m_z.p, 0LL, v, m_grad.p);
   SLPX_HIP_CHECK(hipGetLastError());
   std::vector<double> g(static_cast<size_t>(p.n_p));
   dev.download(m_grad.p, g.data(), g.size());
@@ -347,7 +418,7 @@ void Sensitivity::unreduced(const Point& at, double* M) {
 // ---- B instances at once ----
 
 // One call's bookkeeping.  status: the outcome of every instance IN THIS CALL — that of its rows (PerBatch::base_status),
-// or skipped for a dp / vx that is not finite; mask: the instances the solves of this call are for.
+// or skipped for a dp / cotangent that is not finite; mask: the instances the solves of this call are for.
 struct BatchSensitivity::Call {
   PerBatch* pb = nullptr;
   NewtonSystem* model = nullptr;
@@ -356,7 +427,8 @@ struct BatchSensitivity::Call {
   std::vector<int32_t> status;
   std::vector<uint8_t> extra_bad, mask;
   std::vector<SensitivityInfo> info;
-  std::vector<double> extra;  // dp / vx, zeros in the rows of the instances left out: no kernel reads a NaN
+  std::vector<double> extra;  // dp / the cotangents behind one another, zeros in the rows of the instances left out: no kernel reads a NaN
+  std::vector<size_t> extra_at;  // where each of them begins in `extra`
   double t_compile = 0.0, t_factor = 0.0;
   int factorizations = 0;
 
@@ -376,7 +448,7 @@ struct BatchSensitivity::Call {
 SensDev BatchSensitivity::view() const {
   const SensPlan& p = m_plan;
   return SensDev{p.n, p.n_p, p.m_e, p.m_i, p.dim, p.dimM, m_m_ptr.p, m_m_src.p, m_red_ptr.p, m_red_src.p, m_red_row.p,
-                 m_ai_rowptr.p, m_ai_col.p, m_ai_src.p};
+                 m_ai_rowptr.p, m_ai_col.p, m_ai_src.p, m_g_src.p, m_fp_src.p};
 }
 
 void BatchSensitivity::forget(int batch) {
@@ -414,6 +486,8 @@ BatchSensitivity::PerBatch& BatchSensitivity::per_batch(NewtonSystem& model, Nod
     m_ai_rowptr.upload(m_plan.ai_rowptr);
     m_ai_col.upload(m_plan.ai_col);
     m_ai_src.upload(m_plan.ai_src);
+    m_g_src.upload(m_plan.g_src);
+    m_fp_src.upload(m_plan.fp_src);
     m_have_plan = true;
   }
   const SensPlan& p = m_plan;
@@ -430,6 +504,7 @@ BatchSensitivity::PerBatch& BatchSensitivity::per_batch(NewtonSystem& model, Nod
   pb.rhs1.alloc(Bz * p.dim);
   pb.ri1.alloc(Bz * std::max(1, p.m_i));
   pb.grad.alloc(Bz * n_p);
+  pb.cot.alloc(Bz * static_cast<size_t>(p.n + 2 * p.m_i + p.m_e + 1));
   pb.base_status.assign(Bz, kSensSkipped);
   pb.fact.assign(Bz, SensitivityInfo{});
   pb.ext = std::move(ext);
@@ -452,7 +527,7 @@ void BatchSensitivity::ensure_columns(PerBatch& pb, int columns) {
 
 // The checks every call makes, the classification of its instances, and whether what the last call of this batch size
 // left in memory is still the system of these rows.
-void BatchSensitivity::begin(Call& c, NewtonSystem& model, NodeId f, const Rows& at, const double* extra, int n_extra) {
+void BatchSensitivity::begin(Call& c, NewtonSystem& model, NodeId f, const Rows& at, const SensExtraRows* extras, int n_extras) {
   c.t0 = clk::now();
   c.model = &model;
   c.at = at;
@@ -488,14 +563,20 @@ void BatchSensitivity::begin(Call& c, NewtonSystem& model, NodeId f, const Rows&
   c.extra_bad.assign(Bz, 0);
   c.mask.assign(Bz, 0);
   c.info.assign(Bz, SensitivityInfo{});
-  if (extra != nullptr) {
+  if (n_extras > 0) {
     std::vector<int32_t> st(Bz);
-    sens_classify_instances(B, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, extra, n_extra, st.data());
-    c.extra.assign(extra, extra + Bz * n_extra);
+    sens_classify_extras(B, extras, n_extras, st.data());
+    c.extra_at.assign(static_cast<size_t>(n_extras), 0);
+    for (int k = 0; k < n_extras; ++k) {
+      c.extra_at[k] = c.extra.size();
+      if (extras[k].rows != nullptr) c.extra.insert(c.extra.end(), extras[k].rows, extras[k].rows + Bz * extras[k].width);
+    }
     for (size_t b = 0; b < Bz; ++b)
       if (st[b] != kSensComputed) {
         c.extra_bad[b] = 1;
-        std::fill(c.extra.begin() + b * n_extra, c.extra.begin() + (b + 1) * n_extra, 0.0);
+        for (int k = 0; k < n_extras; ++k)
+          if (extras[k].rows != nullptr)
+            std::fill_n(c.extra.begin() + c.extra_at[k] + b * extras[k].width, extras[k].width, 0.0);
       }
   }
   c.settle();
@@ -728,7 +809,8 @@ void BatchSensitivity::jvp(NewtonSystem& model, NodeId f, const Rows& at, const 
                            double* dz, int32_t* status, SensitivityInfo* info) {
   if (dp == nullptr) throw std::runtime_error("slpx: batched sensitivity jvp: dp is null");
   Call c;
-  begin(c, model, f, at, dp, static_cast<int>(model.structure().parameter_nodes().size()));
+  const SensExtraRows extra{dp, static_cast<int>(model.structure().parameter_nodes().size())};
+  begin(c, model, f, at, &extra, 1);
   const SensPlan& p = m_plan;
   PerBatch& pb = *c.pb;
   ensure_columns(pb, 1);
@@ -748,8 +830,20 @@ void BatchSensitivity::jvp(NewtonSystem& model, NodeId f, const Rows& at, const 
 void BatchSensitivity::vjp(NewtonSystem& model, NodeId f, const Rows& at, const double* vx, double* grad, int32_t* status,
                            SensitivityInfo* info) {
   if (vx == nullptr) throw std::runtime_error("slpx: batched sensitivity vjp: vx is null");
+  SensCotangent v;
+  v.vx = vx;
+  vjp_full(model, f, at, v, grad, status, info);
+}
+
+void BatchSensitivity::vjp_full(NewtonSystem& model, NodeId f, const Rows& at, const SensCotangent& given, double* grad, int32_t* status,
+                                SensitivityInfo* info) {
+  if (!given.vx && !given.vs && !given.vy && !given.vz && !given.vcost) throw std::runtime_error("slpx: batched sensitivity vjp: no cotangent");
+  const NlpStructure& ms = model.structure();
+  // (a cotangent on rows the model does not have is absent)
+  const SensExtraRows extras[5] = {{given.vx, ms.n}, {ms.m_i ? given.vs : nullptr, ms.m_i}, {ms.m_e ? given.vy : nullptr, ms.m_e},
+                                   {ms.m_i ? given.vz : nullptr, ms.m_i}, {given.vcost, 1}};
   Call c;
-  begin(c, model, f, at, vx, model.structure().n);
+  begin(c, model, f, at, extras, 5);
   const SensPlan& p = m_plan;
   PerBatch& pb = *c.pb;
   ensure_columns(pb, 1);
@@ -758,12 +852,22 @@ void BatchSensitivity::vjp(NewtonSystem& model, NodeId f, const Rows& at, const 
   if (c.any_computed) {
     DeviceNlp& dev = model.device();
     const hipStream_t st = dev.stream();
-    std::vector<double> rhs(B * p.dim, 0.0);  // [vx; 0] per instance
-    for (size_t b = 0; b < B; ++b) std::copy(c.extra.begin() + b * p.n, c.extra.begin() + (b + 1) * p.n, rhs.begin() + b * p.dim);
-    SLPX_HIP_CHECK(hipMemcpyAsync(pb.rhs1.p, rhs.data(), rhs.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    SensCotangent v;
+    const double** on_device[5] = {&v.vx, &v.vs, &v.vy, &v.vz, &v.vcost};
+    for (int k = 0; k < 5; ++k)
+      if (extras[k].rows != nullptr) *on_device[k] = pb.cot.p + c.extra_at[k];
+    if (!c.extra.empty()) SLPX_HIP_CHECK(hipMemcpyAsync(pb.cot.p, c.extra.data(), c.extra.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(sens_adjoint_rhs_kernel, dim3(blocks_for(p.dim, kSensBatchThreads), pb.B), dim3(kSensBatchThreads), 0, st, view(), pb.V.p,
+                       static_cast<long long>(p.nV), pb.s.p, pb.z.p, static_cast<long long>(p.m_i), v, pb.rhs1.p);
+    SLPX_HIP_CHECK(hipGetLastError());
     SLPX_HIP_CHECK(hipStreamSynchronize(st));
     solve_round(c, pb.rhs1.p, p.dim, pb.sol.p, p.dim);
-    hipLaunchKernelGGL(sens_vjp_kernel, dim3(p.n_p, pb.B), dim3(kSensVjpThreads), 0, st, view(), pb.R.p, pb.sol.p, pb.grad.p);
+    // (w^T R alone is sens_vjp_kernel's, as before there were other cotangents)
+    if (!sens_adjoint_has_t(p.m_i, v.vs, v.vz) && v.vcost == nullptr)
+      hipLaunchKernelGGL(sens_vjp_kernel, dim3(p.n_p, pb.B), dim3(kSensVjpThreads), 0, st, view(), pb.R.p, pb.sol.p, pb.grad.p);
+    else
+      hipLaunchKernelGGL(sens_vjp_full_kernel, dim3(p.n_p, pb.B), dim3(kSensVjpThreads), 0, st, view(), pb.M.p, pb.R.p, pb.sol.p,
+                         pb.ext->device().d_V(), static_cast<long long>(p.nVx), pb.s.p, pb.z.p, static_cast<long long>(p.m_i), v, pb.grad.p);
     SLPX_HIP_CHECK(hipGetLastError());
     if (grad) dev.download(pb.grad.p, grad, B * p.n_p);
     else SLPX_HIP_CHECK(hipStreamSynchronize(st));

@@ -40,7 +40,7 @@ struct SensitivityInfo {
 // the plan on the device: what the kernels of sensitivity.hip take (SensPlan's arrays by the same names)
 struct SensDev {
   int n, n_p, m_e, m_i, dim, dimM;
-  const int32_t *m_ptr, *m_src, *red_ptr, *red_src, *red_row, *ai_rowptr, *ai_col, *ai_src;
+  const int32_t *m_ptr, *m_src, *red_ptr, *red_src, *red_row, *ai_rowptr, *ai_col, *ai_src, *g_src, *fp_src;
 };
 
 class Sensitivity {
@@ -79,8 +79,12 @@ class Sensitivity {
   void jacobian(const Point& at, double* dx, double* ds, double* dy, double* dz, SensitivityInfo& info);
   // The directional derivative along dp [n_p]: one solve.  dx [n], ds [m_i], dy [m_e], dz [m_i].
   void jvp(const Point& at, const double* dp, double* dx, double* ds, double* dy, double* dz, SensitivityInfo& info);
-  // grad [n_p] = (dx/dp)^T vx for a cotangent vx [n] on x: one solve, K w = [vx; 0], then w^T R.
+  // grad [n_p] = (dx/dp)^T vx for a cotangent vx [n] on x: one solve, K w = [vx; 0], then w^T R.  vjp_full with vx alone.
   void vjp(const Point& at, const double* vx, double* grad, SensitivityInfo& info);
+  // grad [n_p] for cotangents on the whole iterate and on the cost (sens_plan.hpp: the adjoint; host arrays vx [n],
+  // vs [m_i], vy [m_e], vz [m_i], vcost [1], null: absent, and one on rows the model does not have is ignored): ONE
+  // solve, K w = [vx + A_i^T t + vcost g; -vy], then w^T R + t . r_i + vcost f_p.
+  void vjp_full(const Point& at, const SensCotangent& v, double* grad, SensitivityInfo& info);
   // M [n_p][n + m_e + m_i]: r_x, r_e, r_i per parameter.  No factorization.
   void unreduced(const Point& at, double* M);
 
@@ -101,7 +105,8 @@ class Sensitivity {
   int32_t m_n_pos = 0, m_n_neg = 0, m_n_zero = 0;
   double m_delta = 0.0, m_gamma = 0.0;
 
-  DevBuf<int32_t> m_m_ptr, m_m_src, m_red_ptr, m_red_src, m_red_row, m_ai_rowptr, m_ai_col, m_ai_src;
+  DevBuf<int32_t> m_m_ptr, m_m_src, m_red_ptr, m_red_src, m_red_row, m_ai_rowptr, m_ai_col, m_ai_src, m_g_src, m_fp_src;
+  DevBuf<double> m_cot;  // the cotangents of vjp_full: vx, vs, vy, vz, vcost behind one another
   // M, R; the model's V, s, z at the iterate (copies: the model system's own are its caller's again after a product)
   DevBuf<double> m_M, m_R, m_V, m_s, m_z;
   DevBuf<double> m_vec, m_rhs1, m_ri1, m_sol, m_dx, m_ds, m_dy, m_dz, m_grad;
@@ -145,8 +150,12 @@ class BatchSensitivity {
   // dp [B][n_p] -> dx [B][n], ds [B][m_i], dy [B][m_e], dz [B][m_i]: one round
   void jvp(NewtonSystem& model, NodeId f, const Rows& at, const double* dp, double* dx, double* ds, double* dy, double* dz,
            int32_t* status, SensitivityInfo* info);
-  // vx [B][n] -> grad [B][n_p]: one round
+  // vx [B][n] -> grad [B][n_p]: one round.  vjp_full with vx alone.
   void vjp(NewtonSystem& model, NodeId f, const Rows& at, const double* vx, double* grad, int32_t* status, SensitivityInfo* info);
+  // cotangents vx [B][n], vs [B][m_i], vy [B][m_e], vz [B][m_i], vcost [B] (null: absent) -> grad [B][n_p]: one round.
+  // An instance with a value that is not finite in ANY given cotangent row is skipped (kSensSkipped).
+  void vjp_full(NewtonSystem& model, NodeId f, const Rows& at, const SensCotangent& v, double* grad, int32_t* status,
+                SensitivityInfo* info);
   // M [B][n_p][n + m_e + m_i]: neither factors nor solves
   void unreduced(NewtonSystem& model, NodeId f, const Rows& at, double* M, int32_t* status);
 
@@ -160,14 +169,15 @@ class BatchSensitivity {
     std::vector<double> key;            // the rows `evaluated` / `factored` speak of: x, s, y, z, mu, params as given
     std::vector<int32_t> base_status;   // of those rows: classification, then kSensNotFactored from the factorization
     std::vector<SensitivityInfo> fact;  // per instance: inertia, delta, gamma of the factorization in memory
-    DevBuf<double> M, R, V, s, z, vec, rhs1, ri1, sol, dx, ds, dy, dz, grad;
+    DevBuf<double> M, R, V, s, z, vec, rhs1, ri1, sol, dx, ds, dy, dz, grad, cot;
     int sol_columns = 0;
   };
   struct Call;  // one call's bookkeeping (sensitivity.hip)
 
   PerBatch& per_batch(NewtonSystem& model, NodeId f);
   void ensure_columns(PerBatch& pb, int columns);
-  void begin(Call& c, NewtonSystem& model, NodeId f, const Rows& at, const double* extra, int n_extra);
+  // extras: the arrays beside the rows (dp; the cotangents), classified together and kept behind one another in c.extra
+  void begin(Call& c, NewtonSystem& model, NodeId f, const Rows& at, const SensExtraRows* extras, int n_extras);
   void evaluate(Call& c);
   void factor(Call& c);
   // the right-hand sides in rhs (device, [B] rows `rhs_pitch` doubles apart) -> the refined solutions into sol likewise
@@ -179,7 +189,7 @@ class BatchSensitivity {
 
   bool m_have_plan = false;
   SensPlan m_plan;
-  DevBuf<int32_t> m_m_ptr, m_m_src, m_red_ptr, m_red_src, m_red_row, m_ai_rowptr, m_ai_col, m_ai_src;
+  DevBuf<int32_t> m_m_ptr, m_m_src, m_red_ptr, m_red_src, m_red_row, m_ai_rowptr, m_ai_col, m_ai_src, m_g_src, m_fp_src;
   std::map<int, PerBatch> m_per_batch;
 };
 

@@ -270,6 +270,43 @@ class ProblemF64 {
     if (info) *info = local;
     return grad;
   }
+  // Cotangents on the whole end iterate and on the optimal cost — cost: the value the solve reports, f as minimize()
+  // or maximize() stored it, in the user's units.  An empty span is absent; at least one must be given.
+  struct Cotangent {
+    std::span<const double> x, s, y, z;  // [n], [m_i], [m_e], [m_i]
+    std::span<const double> cost;        // [1]
+  };
+  // sum over the given blocks of (d block/dp)^T v_block, plus v_cost d cost/dp: [n_p], ONE solve whatever n_p and
+  // whichever blocks (sens_plan.hpp: the adjoint).  With x alone: sensitivity_vjp(vx), bit for bit.
+  std::vector<double> sensitivity_vjp(const Cotangent& v, slpx::SensitivityInfo* info = nullptr) {
+    const slpx::Sensitivity::Point at = sensitivity_point();
+    const auto& st = m_sys->structure();
+    const auto given = [](std::span<const double> a, size_t count, const char* what) -> const double* {
+      if (a.empty()) return nullptr;
+      if (a.size() != count) throw std::runtime_error(std::string("sensitivity_vjp: wrong number of values in the cotangent on ") + what);
+      return a.data();
+    };
+    slpx::SensCotangent c;
+    c.vx = given(v.x, st.n, "x");
+    c.vs = given(v.s, st.m_i, "s");
+    c.vy = given(v.y, st.m_e, "y");
+    c.vz = given(v.z, st.m_i, "z");
+    c.vcost = given(v.cost, 1, "the cost");
+    if (!c.vx && !c.vs && !c.vy && !c.vz && !c.vcost) throw std::runtime_error("sensitivity_vjp: no cotangent");
+    std::vector<double> grad(m_iterate_parameters.size());
+    slpx::SensitivityInfo local;
+    local.solve_status = m_iterate_status;
+    m_sens->vjp_full(at, c, grad.data(), local);
+    if (info) *info = local;
+    return grad;
+  }
+  // d cost/dp [n_p]: the cotangent 1 on the cost alone
+  std::vector<double> cost_gradient(slpx::SensitivityInfo* info = nullptr) {
+    const double one = 1.0;
+    Cotangent v;
+    v.cost = std::span<const double>(&one, 1);
+    return sensitivity_vjp(v, info);
+  }
   // M [n_p][n + m_e + m_i]: per parameter r_x = d(grad_x L)/dp_q, r_e = dc_e/dp_q, r_i = dc_i/dp_q at the iterate
   std::vector<double> sensitivity_rhs() {
     const slpx::Sensitivity::Point at = sensitivity_point();
@@ -325,6 +362,32 @@ class ProblemF64 {
     out.status.resize(c.B);
     out.info.resize(c.B);
     m_batch_sens->vjp(*c.sys, cost_root(), c.rows, vx.data(), out.grad.data(), out.status.data(), out.info.data());
+    return out;
+  }
+  // the cotangents of a batch: rows per instance, an empty span is absent
+  struct BatchCotangent {
+    std::span<const double> x, s, y, z;  // [B][n], [B][m_i], [B][m_e], [B][m_i]
+    std::span<const double> cost;        // [B]
+  };
+  BatchSensitivities sensitivity_batch_vjp(int batch, const BatchIterate& it, std::span<const double> params, const BatchCotangent& v) {
+    BatchCall c = batch_sensitivity_call(batch, it, params, "sensitivity_batch_vjp");
+    const auto given = [&](std::span<const double> a, size_t count, const char* what) -> const double* {
+      if (a.empty()) return nullptr;
+      if (a.size() != c.B * count) throw std::runtime_error(std::string("sensitivity_batch_vjp: the cotangent on ") + what + " must have batch rows of the model's size");
+      return a.data();
+    };
+    slpx::SensCotangent sc;
+    sc.vx = given(v.x, c.n, "x");
+    sc.vs = given(v.s, c.m_i, "s");
+    sc.vy = given(v.y, c.m_e, "y");
+    sc.vz = given(v.z, c.m_i, "z");
+    sc.vcost = given(v.cost, 1, "the cost");
+    if (!sc.vx && !sc.vs && !sc.vy && !sc.vz && !sc.vcost) throw std::runtime_error("sensitivity_batch_vjp: no cotangent");
+    BatchSensitivities out;
+    out.grad.resize(c.B * c.n_p);
+    out.status.resize(c.B);
+    out.info.resize(c.B);
+    m_batch_sens->vjp_full(*c.sys, cost_root(), c.rows, sc, out.grad.data(), out.status.data(), out.info.data());
     return out;
   }
   BatchSensitivities sensitivity_batch_rhs(int batch, const BatchIterate& it, std::span<const double> params) {

@@ -22,7 +22,7 @@ from sleipnir_amd.autodiff import (EqualityConstraints, ExpressionType, Inequali
 
 __all__ = ["ExitStatus", "Problem", "OCP", "DynamicsType", "TimestepMethod", "TranscriptionMethod",
            "EqualityConstraints", "InequalityConstraints", "IterationInfo", "bounds", "multistart",
-           "Iterate", "BatchIterate", "BatchResult", "Sensitivity", "BatchSensitivity"]
+           "Iterate", "BatchIterate", "BatchResult", "Sensitivity", "BatchSensitivity", "Cotangent"]
 
 
 class ExitStatus(enum.IntEnum):
@@ -123,6 +123,22 @@ class Iterate:
 
 
 @dataclasses.dataclass
+class Cotangent:
+    """Cotangents on the whole end iterate and on the optimal cost, for Problem.sensitivity_vjp and
+    Problem.sensitivity_batch_vjp: x (n), s (m_i), y (m_e), z (m_i) and cost (a number) — for a batch (B, n), (B, m_i),
+    (B, m_e), (B, m_i) and (B).  None is absent; at least one must be given.  `cost` is the cost the solve reports: the
+    cost of minimize(), the NEGATED objective of maximize()."""
+    x: object = None
+    s: object = None
+    y: object = None
+    z: object = None
+    cost: object = None
+
+    def _blocks(self):
+        return {k: getattr(self, k) for k in ("x", "s", "y", "z", "cost") if getattr(self, k) is not None}
+
+
+@dataclasses.dataclass
 class Sensitivity:
     """What Problem.sensitivity() returns: the derivatives of the end iterate with respect to the parameters, in the
     user's units — dx (n_p, n), ds (n_p, m_i), dy (n_p, m_e), dz (n_p, m_i) — and `info`, a dict of
@@ -189,6 +205,7 @@ class Problem:
         self._p = _sa.Problem()
         self._decision_variables: list[Variable] = []
         self._pattern_cache = None
+        self._cost = None  # (expression, sign) of minimize() / maximize()
         self.report = None  # counters and phase times of the last solve() that ran an iteration
         self.sensitivity_info = None  # slpx_sensitivity_info of the last sensitivity_jvp() / sensitivity_vjp()
         self.sensitivity_status = None  # per-instance status of the last batched sensitivity product
@@ -220,11 +237,20 @@ class Problem:
 
     def minimize(self, cost):
         self._pattern_cache = None
-        self._p.minimize(Variable._lift(cost).node)
+        self._cost = (Variable._lift(cost), 1.0)
+        self._p.minimize(self._cost[0].node)
 
     def maximize(self, objective):
         self._pattern_cache = None
-        self._p.maximize(Variable._lift(objective).node)
+        self._cost = (Variable._lift(objective), -1.0)  # (stored, reported and differentiated negated)
+        self._p.maximize(self._cost[0].node)
+
+    def cost_value(self) -> float:
+        """The cost at the variables' current values as a solve reports it: the cost of minimize(), the NEGATED objective
+        of maximize(); 0 without either.  What cost_gradient() differentiates."""
+        if self._cost is None:
+            return 0.0
+        return self._cost[1] * self._cost[0].value()
 
     def subject_to(self, constraint):
         self._pattern_cache = None
@@ -362,9 +388,19 @@ class Problem:
 
     def sensitivity_vjp(self, v) -> np.ndarray:
         """(d x*/d p)^T v (n_p) for a cotangent v (n) on x: the gradient of l(x*(p)) with v = dl/dx, from ONE solve
-        whatever n_p."""
-        grad, self.sensitivity_info = self._p.sensitivity_vjp(v)
+        whatever n_p.  With a Cotangent instead of an array: the gradient of a loss on all of (x*, s*, y*, z*, cost*),
+        sum_blocks (d block/dp)^T v_block + v_cost d cost*/dp, still from one solve."""
+        if isinstance(v, Cotangent):
+            grad, self.sensitivity_info = self._p.sensitivity_vjp_full(**v._blocks())
+        else:
+            grad, self.sensitivity_info = self._p.sensitivity_vjp(v)
         return grad
+
+    def cost_gradient(self) -> np.ndarray:
+        """d cost*/d p (n_p), the gradient of the optimal cost the last solve reported, from ONE solve instead of the n_p
+        of sensitivity(): sensitivity_vjp(Cotangent(cost=1.0)).  For an interior-point model: of f at the barrier
+        problem's solution, O(mu) from the model's."""
+        return self.sensitivity_vjp(Cotangent(cost=1.0))
 
     # ---- batched sensitivities: functions of a BatchIterate and its parameter rows, not of the problem's state ----
     def sensitivity_batch(self, iterate, parameters) -> "BatchSensitivity":
@@ -391,9 +427,17 @@ class Problem:
     def sensitivity_batch_vjp(self, iterate, parameters, v) -> np.ndarray:
         """(d x*_b / d p_b)^T v_b (B, n_p) for cotangents v (B, n) on x, one round of solves whatever n_p.
         `sensitivity_status` and `sensitivity_info` are those of this call."""
-        r = self._p.sensitivity_batch_vjp(iterate, parameters, v)
+        if isinstance(v, Cotangent):  # (rows per instance on any of x, s, y, z, cost)
+            r = self._p.sensitivity_batch_vjp_full(iterate, parameters, **v._blocks())
+        else:
+            r = self._p.sensitivity_batch_vjp(iterate, parameters, v)
         self.sensitivity_status, self.sensitivity_info = r["status"], r["info"]
         return r["grad"]
+
+    def cost_gradient_batch(self, iterate, parameters) -> np.ndarray:
+        """d cost*_b / d p_b (B, n_p): sensitivity_batch_vjp with the cotangent 1 on every instance's cost alone."""
+        B = np.shape(np.asarray(parameters))[0]
+        return self.sensitivity_batch_vjp(iterate, parameters, Cotangent(cost=np.ones(B)))
 
     def sensitivity_batch_rhs(self, iterate, parameters) -> np.ndarray:
         """M (B, n_p, n + m_e + m_i): per instance and parameter r_x, r_e, r_i at its iterate; no factorization."""
