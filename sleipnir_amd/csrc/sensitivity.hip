@@ -1,5 +1,6 @@
-// The kernels of the solution sensitivities and their drivers (sensitivity.hpp): one problem (Sensitivity) and B
-// instances at once (BatchSensitivity).  Opt-in: nothing on the path of a solve comes here.
+// The kernels of the solution sensitivities, the layer that launches them, and the two drivers on top of it
+// (sensitivity.hpp): one problem (Sensitivity) and B instances at once (BatchSensitivity).  Opt-in: nothing on the path
+// of a solve comes here.
 //
 // Six kernels, all row-local gathers — one lane computes one output entry with the row formulas of sens_rows.h, the
 // bodies the host executor (sens_plan.cpp) runs — so an entry's bits do not depend on the launch geometry, on the batch
@@ -11,12 +12,14 @@
 //   sens_adjoint_rhs_kernel  the full vjp's right-hand side [vx + A_i^T t + vcost g; -vy], t = vs - Sigma o vz (sens_plan.hpp)
 //   sens_vjp_full_kernel     w^T R[:, q] + t . r_i[:, q] + vcost f_p[q]: two dot products in sens_vjp_kernel's order, side by side
 // THE GRID.  blockIdx.y is the instance (at most 65535 of them: one grid slice each) and every buffer has an instance
-// stride, 0 or unused for one problem.  blockIdx.x runs over the entries of ONE instance with the columns folded in —
-// (parameter, row) for rhs and expand.  A batched launch uses workgroups of one wave (kSensBatchThreads): the models
-// the batch serves have n_p * dimM of a few dozen to a few thousand, so a 256-lane workgroup per (instance, column)
-// would be mostly idle lanes, and it is the instance axis that fills the machine.  The single-slice launches of one
-// problem keep 256 lanes (kSensThreads), the geometry profiles/sensitivity.txt was measured with; the kernels take the
-// workgroup size from the launch.  Plain vector loads and stores only; no LDS beyond the fold of the vjp.
+// stride.  blockIdx.x runs over the entries of ONE instance with the columns folded in — (parameter, row) for rhs and
+// expand.  Each kernel is launched in ONE place, a stage of the layer below, for a SensState of B instances: a grid of
+// (blocks, B), the real instance strides — with B = 1 they multiply blockIdx.y = 0 — and the state's launch width.  A
+// batch system's state has workgroups of one wave (kSensBatchThreads): the models the batch serves have n_p * dimM of a
+// few dozen to a few thousand, so a 256-lane workgroup per (instance, column) would be mostly idle lanes, and it is the
+// instance axis that fills the machine.  The state of the problem's own system keeps 256 lanes (kSensThreads), the
+// geometry profiles/sensitivity.txt was measured with; the kernels take the workgroup size from the launch.  Plain
+// vector loads and stores only; no LDS beyond the fold of the vjp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,8 +33,8 @@
 
 namespace slpx {
 
-constexpr int kSensThreads = 256;      // one problem
-constexpr int kSensBatchThreads = 64;  // B instances: one wave
+constexpr int kSensThreads = 256;      // the problem's own system
+constexpr int kSensBatchThreads = 64;  // a batch system: one wave
 
 // entry e = q * dimM + row of instance blockIdx.y
 __global__ __launch_bounds__(kSensThreads) void sens_rhs_kernel(SensDev d, const double* __restrict__ Vx, long long Vx_stride,
@@ -149,75 +152,245 @@ __global__ __launch_bounds__(kSensVjpThreads) void sens_vjp_full_kernel(SensDev 
   if (t == 0) grad[b * d.n_p + q] = sens_vjp_full_sum(part[0], direct, part_t[0], v.vcost ? v.vcost + b : nullptr, d.fp_src[q], Vx + b * Vx_stride);
 }
 
+// ---- the layer under both drivers: every stage once, for a state of B instances ----
+
+void SensPlanDev::build(const NlpStructure& model, const NlpStructure& extended) {
+  plan = build_sens_plan(model, extended);
+  m_ptr.upload(plan.m_ptr);
+  m_src.upload(plan.m_src);
+  red_ptr.upload(plan.red_ptr);
+  red_src.upload(plan.red_src);
+  red_row.upload(plan.red_row);
+  ai_rowptr.upload(plan.ai_rowptr);
+  ai_col.upload(plan.ai_col);
+  ai_src.upload(plan.ai_src);
+  g_src.upload(plan.g_src);
+  fp_src.upload(plan.fp_src);
+  built = true;
+}
+
+SensDev SensPlanDev::view() const {
+  const SensPlan& p = plan;
+  return SensDev{p.n, p.n_p, p.m_e, p.m_i, p.dim, p.dimM, m_ptr.p, m_src.p, red_ptr.p, red_src.p, red_row.p,
+                 ai_rowptr.p, ai_col.p, ai_src.p, g_src.p, fp_src.p};
+}
+
 namespace {
 using clk = std::chrono::steady_clock;
 double seconds_since(clk::time_point t0) { return std::chrono::duration<double>(clk::now() - t0).count(); }
-unsigned blocks_for(int64_t count, int threads = kSensThreads) { return static_cast<unsigned>(std::max<int64_t>(1, (count + threads - 1) / threads)); }
-}  // namespace
+unsigned blocks_for(int64_t count, int threads) { return static_cast<unsigned>(std::max<int64_t>(1, (count + threads - 1) / threads)); }
 
-Sensitivity::Sensitivity(NewtonSystem& model, NodeId f) : m_model(model) {
-  const auto t0 = clk::now();
-  if (!model.has_device()) throw std::runtime_error("slpx: sensitivity: the model's system has no device");
-  if (model.batch() != 1) throw std::runtime_error("slpx: sensitivity: the model's system must be a single problem");
+// The model over x' = [x ; p], the parameters behind the decision variables in the order of every parameter vector:
+// the tape and device options of `model`, `batch` instances, unit scales.
+std::unique_ptr<NewtonSystem> extended_system(NewtonSystem& model, NodeId f, int batch) {
   const std::vector<NodeId> params = model.structure().parameter_nodes();
-  if (params.empty()) throw std::runtime_error("slpx: sensitivity: the model reaches no parameter");
-  // x' = [x ; p]: the parameters behind the decision variables, in the order of every parameter vector
   std::vector<NodeId> xp = model.x_nodes();
   xp.insert(xp.end(), params.begin(), params.end());
   NewtonOptions opt;
   opt.tape = model.options().tape;
   opt.device = model.options().device;
-  m_ext = std::make_unique<NewtonSystem>(model.graph(), xp, f, model.c_e_nodes(), model.c_i_nodes(), opt);
-  m_ext->device().set_scaling(std::vector<double>(m_ext->structure().n_scales(), 1.0));
-  m_plan = build_sens_plan(model.structure(), m_ext->structure());
-  const SensPlan& p = m_plan;
-  m_m_ptr.upload(p.m_ptr);
-  m_m_src.upload(p.m_src);
-  m_red_ptr.upload(p.red_ptr);
-  m_red_src.upload(p.red_src);
-  m_red_row.upload(p.red_row);
-  m_ai_rowptr.upload(p.ai_rowptr);
-  m_ai_col.upload(p.ai_col);
-  m_ai_src.upload(p.ai_src);
-  m_g_src.upload(p.g_src);
-  m_fp_src.upload(p.fp_src);
-  const size_t n_p = static_cast<size_t>(p.n_p);
-  m_cot.alloc(static_cast<size_t>(p.n + 2 * p.m_i + p.m_e + 1));
-  m_M.alloc(n_p * p.dimM);
-  m_R.alloc(n_p * p.dim);
-  m_V.alloc(static_cast<size_t>(p.nV));
-  m_s.alloc(static_cast<size_t>(std::max(1, p.m_i)));
-  m_z.alloc(static_cast<size_t>(std::max(1, p.m_i)));
-  m_vec.alloc(static_cast<size_t>(std::max(p.n_p, p.dim)));
-  m_rhs1.alloc(static_cast<size_t>(p.dim));
-  m_ri1.alloc(static_cast<size_t>(std::max(1, p.m_i)));
-  m_sol.alloc(n_p * p.dim);
-  m_dx.alloc(std::max<size_t>(1, n_p * p.n));
-  m_ds.alloc(std::max<size_t>(1, n_p * p.m_i));
-  m_dy.alloc(std::max<size_t>(1, n_p * p.m_e));
-  m_dz.alloc(std::max<size_t>(1, n_p * p.m_i));
-  m_grad.alloc(n_p);
+  opt.batch = batch;
+  auto ext = std::make_unique<NewtonSystem>(model.graph(), xp, f, model.c_e_nodes(), model.c_i_nodes(), opt);
+  ext->device().set_scaling(std::vector<double>(ext->structure().n_scales(), 1.0));
+  return ext;
+}
+
+// The buffers of a state whose B is set, and room for `columns` solutions per instance and their expansion.
+void size_state(SensState& S, const SensPlan& p, int columns) {
+  const size_t B = static_cast<size_t>(S.B), n_p = static_cast<size_t>(p.n_p);
+  if (S.M.p == nullptr) {
+    S.M.alloc(B * n_p * p.dimM);
+    S.R.alloc(B * n_p * p.dim);
+    S.V.alloc(B * p.nV);
+    S.s.alloc(B * std::max(1, p.m_i));
+    S.z.alloc(B * std::max(1, p.m_i));
+    S.vec.alloc(B * n_p);
+    S.rhs1.alloc(B * p.dim);
+    S.ri1.alloc(B * std::max(1, p.m_i));
+    S.grad.alloc(B * n_p);
+    S.cot.alloc(B * static_cast<size_t>(p.n + 2 * p.m_i + p.m_e + 1));
+  }
+  if (S.columns >= columns) return;
+  const size_t rows = B * columns;
+  S.sol.alloc(rows * p.dim);
+  S.dx.alloc(std::max<size_t>(1, rows * p.n));
+  S.ds.alloc(std::max<size_t>(1, rows * p.m_i));
+  S.dy.alloc(std::max<size_t>(1, rows * p.m_e));
+  S.dz.alloc(std::max<size_t>(1, rows * p.m_i));
+  S.columns = columns;
+}
+
+// After the sweeps of both systems: V, s, z of the model system (`dev`) into the state's copies, then M and R.
+void gather(const SensPlanDev& P, SensState& S, DeviceNlp& dev, hipStream_t st) {
+  const SensPlan& p = P.plan;
+  const size_t B = static_cast<size_t>(S.B), m_i = static_cast<size_t>(p.m_i);
+  SLPX_HIP_CHECK(hipMemcpyAsync(S.V.p, dev.d_V(), B * p.nV * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (m_i) {
+    SLPX_HIP_CHECK(hipMemcpyAsync(S.s.p, dev.d_s(), B * m_i * sizeof(double), hipMemcpyDeviceToDevice, st));
+    SLPX_HIP_CHECK(hipMemcpyAsync(S.z.p, dev.d_z(), B * m_i * sizeof(double), hipMemcpyDeviceToDevice, st));
+  }
+  hipLaunchKernelGGL(sens_rhs_kernel, dim3(blocks_for(static_cast<int64_t>(p.n_p) * p.dimM, S.threads), S.B), dim3(S.threads), 0, st, P.view(),
+                     S.ext->device().d_V(), static_cast<long long>(p.nVx), S.V.p, static_cast<long long>(p.nV), S.s.p, S.z.p,
+                     static_cast<long long>(p.m_i), S.M.p, S.R.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+}
+
+// dp (host, [B][n_p]) -> rhs1 = R dp and ri1 = (dc_i/dp) dp of every instance.  Asynchronous: dp is read until `st` is through.
+void combine(const SensPlanDev& P, SensState& S, const double* dp, hipStream_t st) {
+  const SensPlan& p = P.plan;
+  SLPX_HIP_CHECK(hipMemcpyAsync(S.vec.p, dp, static_cast<size_t>(S.B) * p.n_p * sizeof(double), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(sens_combine_kernel, dim3(blocks_for(p.dimM, S.threads), S.B), dim3(S.threads), 0, st, P.view(), S.M.p, S.R.p, S.vec.p,
+                     S.rhs1.p, S.ri1.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+}
+
+// The cotangents of a call as arrays beside the iterate — vx, vs, vy, vz, vcost; one on rows the model does not have is absent.
+void cotangent_arrays(const SensCotangent& v, int n, int m_e, int m_i, SensExtraRows out[5]) {
+  const SensExtraRows rows[5] = {{n ? v.vx : nullptr, n}, {m_i ? v.vs : nullptr, m_i}, {m_e ? v.vy : nullptr, m_e}, {m_i ? v.vz : nullptr, m_i}, {v.vcost, 1}};
+  std::copy(rows, rows + 5, out);
+}
+
+// Arrays of B rows each (a null one is absent) behind one another in `packed`, as they will lie on the device; at[k]:
+// where array k begins.
+void pack_rows(int B, const SensExtraRows* extras, int count, std::vector<double>& packed, std::vector<size_t>& at) {
+  at.assign(static_cast<size_t>(count), 0);
+  for (int k = 0; k < count; ++k) {
+    at[k] = packed.size();
+    if (extras[k].rows != nullptr) packed.insert(packed.end(), extras[k].rows, extras[k].rows + static_cast<size_t>(B) * extras[k].width);
+  }
+}
+
+// The packed cotangents (cotangent_arrays, pack_rows) into `cot`, and the right-hand side of the adjoint solve into rhs1.
+// Returns them as the kernels take them; `packed` is free again on return.
+SensCotangent adjoint_rhs(const SensPlanDev& P, SensState& S, const SensExtraRows* extras, const std::vector<double>& packed,
+                          const std::vector<size_t>& at, hipStream_t st) {
+  const SensPlan& p = P.plan;
+  SensCotangent v;
+  const double** on_device[5] = {&v.vx, &v.vs, &v.vy, &v.vz, &v.vcost};
+  for (int k = 0; k < 5; ++k)
+    if (extras[k].rows != nullptr) *on_device[k] = S.cot.p + at[k];
+  if (!packed.empty()) SLPX_HIP_CHECK(hipMemcpyAsync(S.cot.p, packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(sens_adjoint_rhs_kernel, dim3(blocks_for(p.dim, S.threads), S.B), dim3(S.threads), 0, st, P.view(), S.V.p,
+                     static_cast<long long>(p.nV), S.s.p, S.z.p, static_cast<long long>(p.m_i), v, S.rhs1.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  SLPX_HIP_CHECK(hipStreamSynchronize(st));
+  return v;
+}
+
+// grad (host, [B][n_p], null: not wanted) from the adjoint solutions in `sol`; ends synchronized.
+void vjp_reduce(const SensPlanDev& P, SensState& S, const SensCotangent& v, double* grad, hipStream_t st) {
+  const SensPlan& p = P.plan;
+  // (w^T R alone — a cotangent on x, or on y — is sens_vjp_kernel's, as before there were others)
+  if (!sens_adjoint_has_t(p.m_i, v.vs, v.vz) && v.vcost == nullptr)
+    hipLaunchKernelGGL(sens_vjp_kernel, dim3(p.n_p, S.B), dim3(kSensVjpThreads), 0, st, P.view(), S.R.p, S.sol.p, S.grad.p);
+  else
+    hipLaunchKernelGGL(sens_vjp_full_kernel, dim3(p.n_p, S.B), dim3(kSensVjpThreads), 0, st, P.view(), S.M.p, S.R.p, S.sol.p,
+                       S.ext->device().d_V(), static_cast<long long>(p.nVx), S.s.p, S.z.p, static_cast<long long>(p.m_i), v, S.grad.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  if (grad) SLPX_HIP_CHECK(hipMemcpyAsync(grad, S.grad.p, static_cast<size_t>(S.B) * p.n_p * sizeof(double), hipMemcpyDeviceToHost, st));
+  SLPX_HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// `columns` solutions per instance in `sol`, r_i of column c of instance b at r_i + b * r_i_instance + c * r_i_column, into
+// the host arrays that are given ([B][columns][.], null: not wanted); ends synchronized.
+void expand_and_download(const SensPlanDev& P, SensState& S, int columns, const double* r_i, long long r_i_column, long long r_i_instance,
+                         double* dx, double* ds, double* dy, double* dz, hipStream_t st) {
+  const SensPlan& p = P.plan;
+  hipLaunchKernelGGL(sens_expand_kernel, dim3(blocks_for(static_cast<int64_t>(columns) * p.dimM, S.threads), S.B), dim3(S.threads), 0, st, P.view(),
+                     columns, S.V.p, static_cast<long long>(p.nV), S.s.p, S.z.p, static_cast<long long>(p.m_i), S.sol.p, r_i, r_i_column,
+                     r_i_instance, S.dx.p, S.ds.p, S.dy.p, S.dz.p);
+  SLPX_HIP_CHECK(hipGetLastError());
+  // (the kernel wrote the caller's layout: one copy per output array, one wait for all)
+  const size_t rows = static_cast<size_t>(S.B) * columns;
+  const auto fetch = [&](const DevBuf<double>& from, double* to, int width) {
+    const size_t count = rows * width;
+    if (to != nullptr && count) SLPX_HIP_CHECK(hipMemcpyAsync(to, from.p, count * sizeof(double), hipMemcpyDeviceToHost, st));
+  };
+  fetch(S.dx, dx, p.n);
+  fetch(S.ds, ds, p.m_i);
+  fetch(S.dy, dy, p.m_e);
+  fetch(S.dz, dz, p.m_i);
+  SLPX_HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// NewtonSystem::compute() on the lhs in memory — for the instances of `mask` (null: the unmasked call) — as the ordinary
+// policy loop from a CLEARED regularization memory; the memory the system had is put back, also when compute() throws.
+struct Factored {
+  std::vector<FactorInfo> result;
+  std::vector<double> delta, gamma;
+  int factorizations = 0;
+};
+Factored factor_from_cleared_memory(NewtonSystem& model, const std::vector<uint8_t>* mask) {
+  const NewtonSystem::RegularizationState saved = model.regularization_state();
+  model.reset_regularization();
+  Factored out;
+  try {
+    out.result = mask ? model.compute(/*solve_speculatively=*/false, *mask) : model.compute();
+  } catch (...) {
+    model.set_regularization_state(saved);
+    throw;
+  }
+  out.delta = model.hessian_regularization();
+  out.gamma = model.constraint_jacobian_regularization();
+  out.factorizations = model.last_factorizations();
+  model.set_regularization_state(saved);
+  return out;
+}
+
+// One round of solves on the factorization in memory: the right-hand sides in rhs (device, [B] rows `rhs_pitch` doubles
+// apart) -> the refined solutions into sol likewise; info [B] of the instances of `mask` (null: all) accounts for it.
+void solve_round(NewtonSystem& model, int dim, const double* rhs, size_t rhs_pitch, double* sol, size_t sol_pitch,
+                 const std::vector<uint8_t>* mask, SensitivityInfo* info) {
+  DeviceNlp& dev = model.device();
+  const int B = model.batch();
+  const size_t width = static_cast<size_t>(dim) * sizeof(double);
+  const hipStream_t st = dev.stream();
+  const auto copy_rows = [&](double* to, size_t to_pitch, const double* from, size_t from_pitch) {
+    if (B == 1) SLPX_HIP_CHECK(hipMemcpyAsync(to, from, width, hipMemcpyDeviceToDevice, st));
+    else SLPX_HIP_CHECK(hipMemcpy2DAsync(to, to_pitch * sizeof(double), from, from_pitch * sizeof(double), width, B, hipMemcpyDeviceToDevice, st));
+  };
+  copy_rows(dev.rhs_raw(), dim, rhs, rhs_pitch);
+  dev.system_written_by_caller(/*lhs=*/false, /*rhs=*/true);
+  dev.solve();
+  const NewtonSystem::Refinement ref = model.refine(2, mask);
+  const NewtonSystem::ErrorBounds eb = model.error_bounds(mask, /*want_ferr=*/false);
+  for (int b = 0; b < B; ++b) {
+    if (mask != nullptr && !(*mask)[b]) continue;
+    info[b].solves += 1 + ref.accepted[b];
+    info[b].refine_steps += ref.accepted[b];
+    if (!(eb.berr[b] <= info[b].berr_max)) info[b].berr_max = eb.berr[b];  // (a NaN shows)
+  }
+  copy_rows(sol, sol_pitch, dev.d_p(), dim);
+}
+}  // namespace
+
+// ---- one problem ----
+
+Sensitivity::Sensitivity(NewtonSystem& model, NodeId f) : m_model(model) {
+  const auto t0 = clk::now();
+  if (!model.has_device()) throw std::runtime_error("slpx: sensitivity: the model's system has no device");
+  if (model.batch() != 1) throw std::runtime_error("slpx: sensitivity: the model's system must be a single problem");
+  if (model.structure().parameter_nodes().empty()) throw std::runtime_error("slpx: sensitivity: the model reaches no parameter");
+  m_state.B = 1;
+  m_state.threads = kSensThreads;
+  m_state.ext = extended_system(model, f, 1);
+  m_plan.build(model.structure(), m_state.ext->structure());
+  size_state(m_state, m_plan.plan, m_plan.plan.n_p);
   m_compile_seconds = seconds_since(t0);
 }
 
 Sensitivity::~Sensitivity() = default;
 
-SensDev Sensitivity::view() const {
-  const SensPlan& p = m_plan;
-  return SensDev{p.n, p.n_p, p.m_e, p.m_i, p.dim, p.dimM, m_m_ptr.p, m_m_src.p, m_red_ptr.p, m_red_src.p, m_red_row.p,
-                 m_ai_rowptr.p, m_ai_col.p, m_ai_src.p, m_g_src.p, m_fp_src.p};
-}
-
 // Both systems at the iterate, unit scales, the user's units: V' and V swept, M and R written, the model's lhs
 // assembled (and a right-hand side of its own built: the factorization carries one along).
 void Sensitivity::evaluate(const Point& at) {
   if (m_evaluated) return;
-  const SensPlan& p = m_plan;
+  const SensPlan& p = m_plan.plan;
   const size_t n = p.n, n_p = p.n_p, m_e = p.m_e, m_i = p.m_i;
   if (at.x->size() != n || at.s->size() != m_i || at.y->size() != m_e || at.z->size() != m_i || at.parameters->size() != n_p)
     throw std::runtime_error("slpx: sensitivity: the iterate does not have the model's sizes");
   DeviceNlp& dev = m_model.device();
-  DeviceNlp& ext = m_ext->device();
+  DeviceNlp& ext = m_state.ext->device();
   m_factored = false;
   // (upload_duals reads all three arrays whatever the sizes)
   const std::vector<double> pad(1, 1.0);
@@ -237,14 +410,7 @@ void Sensitivity::evaluate(const Point& at) {
   dev.upload_mu(&at.mu);
   dev.sweep_full();
   const hipStream_t st = dev.stream();
-  SLPX_HIP_CHECK(hipMemcpyAsync(m_V.p, dev.d_V(), static_cast<size_t>(p.nV) * sizeof(double), hipMemcpyDeviceToDevice, st));
-  if (m_i) {
-    SLPX_HIP_CHECK(hipMemcpyAsync(m_s.p, dev.d_s(), m_i * sizeof(double), hipMemcpyDeviceToDevice, st));
-    SLPX_HIP_CHECK(hipMemcpyAsync(m_z.p, dev.d_z(), m_i * sizeof(double), hipMemcpyDeviceToDevice, st));
-  }
-  hipLaunchKernelGGL(sens_rhs_kernel, dim3(blocks_for(static_cast<int64_t>(p.n_p) * p.dimM)), dim3(kSensThreads), 0, st, view(), ext.d_V(), 0LL,
-                     m_V.p, 0LL, m_s.p, m_z.p, 0LL, m_M.p, m_R.p);
-  SLPX_HIP_CHECK(hipGetLastError());
+  gather(m_plan, m_state, dev, st);
   dev.assemble();
   dev.build_rhs();
   // (what is in memory IS the system now: a request the last solve left for a step that never came is void)
@@ -253,26 +419,17 @@ void Sensitivity::evaluate(const Point& at) {
   m_evaluated = true;
 }
 
-// NewtonSystem::compute() on the lhs evaluate() left: the ordinary policy loop from a cleared memory, the system's own
-// memory and the caller's scaling put back afterwards.
+// The lhs evaluate() left, factored from a cleared memory; the inertia is read back, the caller's scaling is put back
+// afterwards, and a system that cannot be factored throws.
 void Sensitivity::factor(const Point& at, SensitivityInfo& info) {
   evaluate(at);
   if (!m_factored) {
     const auto t0 = clk::now();
     DeviceNlp& dev = m_model.device();
-    const NewtonSystem::RegularizationState saved = m_model.regularization_state();
-    m_model.reset_regularization();
-    std::vector<FactorInfo> res;
-    try {
-      res = m_model.compute();
-    } catch (...) {
-      m_model.set_regularization_state(saved);
-      throw;
-    }
-    m_delta = m_model.hessian_regularization()[0];
-    m_gamma = m_model.constraint_jacobian_regularization()[0];
-    info.factorizations += m_model.last_factorizations();
-    m_model.set_regularization_state(saved);
+    const Factored fac = factor_from_cleared_memory(m_model, nullptr);
+    m_delta = fac.delta[0];
+    m_gamma = fac.gamma[0];
+    info.factorizations += fac.factorizations;
     std::vector<LdltStats> stats;
     dev.read_stats(stats);
     m_n_pos = stats[0].n_pos;
@@ -281,7 +438,7 @@ void Sensitivity::factor(const Point& at, SensitivityInfo& info) {
     // (V of the model system is its own copy here; the lhs in memory stays the one that was factored)
     if (at.scales_after != nullptr && static_cast<int>(at.scales_after->size()) == m_model.structure().n_scales())
       dev.set_scaling(*at.scales_after);
-    if (res[0] != FactorInfo::Success)
+    if (fac.result[0] != FactorInfo::Success)
       throw std::runtime_error("slpx: sensitivity: the KKT system at the iterate could not be factored (delta " + std::to_string(m_delta) +
                                ", gamma " + std::to_string(m_gamma) + ")");
     m_factored = true;
@@ -294,69 +451,33 @@ void Sensitivity::factor(const Point& at, SensitivityInfo& info) {
   info.gamma = m_gamma;
 }
 
-void Sensitivity::solve_one(const double* rhs, double* sol, SensitivityInfo& info) {
-  DeviceNlp& dev = m_model.device();
-  const size_t bytes = static_cast<size_t>(m_plan.dim) * sizeof(double);
-  const hipStream_t st = dev.stream();
-  SLPX_HIP_CHECK(hipMemcpyAsync(dev.rhs_raw(), rhs, bytes, hipMemcpyDeviceToDevice, st));
-  dev.system_written_by_caller(/*lhs=*/false, /*rhs=*/true);
-  dev.solve();
-  ++info.solves;
-  const NewtonSystem::Refinement ref = m_model.refine(2);
-  info.refine_steps += ref.accepted[0];
-  info.solves += ref.accepted[0];
-  const double berr = m_model.error_bounds(nullptr, /*want_ferr=*/false).berr[0];
-  if (!(berr <= info.berr_max)) info.berr_max = berr;  // (a NaN shows)
-  SLPX_HIP_CHECK(hipMemcpyAsync(sol, dev.d_p(), bytes, hipMemcpyDeviceToDevice, st));
-}
-
-void Sensitivity::expand_and_download(int columns, const double* r_i, long long r_i_stride, double* dx, double* ds, double* dy,
-                                      double* dz) {
-  const SensPlan& p = m_plan;
-  DeviceNlp& dev = m_model.device();
-  const hipStream_t st = dev.stream();
-  hipLaunchKernelGGL(sens_expand_kernel, dim3(blocks_for(static_cast<int64_t>(columns) * p.dimM)), dim3(kSensThreads), 0, st, view(), columns,
-                     m_V.p, 0LL, m_s.p, m_z.p, 0LL, m_sol.p, r_i, r_i_stride, 0LL, m_dx.p, m_ds.p, m_dy.p, m_dz.p);
-  SLPX_HIP_CHECK(hipGetLastError());
-  // (the kernel wrote the caller's layout: one copy per output array, one wait for all)
-  const auto fetch = [&](const DevBuf<double>& from, double* to, int width) {
-    const size_t count = static_cast<size_t>(columns) * width;
-    if (to != nullptr && count) SLPX_HIP_CHECK(hipMemcpyAsync(to, from.p, count * sizeof(double), hipMemcpyDeviceToHost, st));
-  };
-  fetch(m_dx, dx, p.n);
-  fetch(m_ds, ds, p.m_i);
-  fetch(m_dy, dy, p.m_e);
-  fetch(m_dz, dz, p.m_i);
-  SLPX_HIP_CHECK(hipStreamSynchronize(st));
-}
-
 void Sensitivity::jacobian(const Point& at, double* dx, double* ds, double* dy, double* dz, SensitivityInfo& info) {
   const auto t0 = clk::now();
-  const SensPlan& p = m_plan;
+  const SensPlan& p = m_plan.plan;
+  SensState& S = m_state;
   info.n_p = p.n_p;
   info.t_compile = take_compile_seconds();
   factor(at, info);
-  for (int q = 0; q < p.n_p; ++q) solve_one(m_R.p + static_cast<size_t>(q) * p.dim, m_sol.p + static_cast<size_t>(q) * p.dim, info);
-  expand_and_download(p.n_p, m_M.p + p.dim, p.dimM, dx, ds, dy, dz);
+  const size_t pitch = static_cast<size_t>(p.n_p) * p.dim;
+  for (int q = 0; q < p.n_p; ++q)
+    solve_round(m_model, p.dim, S.R.p + static_cast<size_t>(q) * p.dim, pitch, S.sol.p + static_cast<size_t>(q) * p.dim, pitch, nullptr, &info);
+  expand_and_download(m_plan, S, p.n_p, S.M.p + p.dim, p.dimM, static_cast<long long>(p.n_p) * p.dimM, dx, ds, dy, dz, m_model.device().stream());
   info.t_total = seconds_since(t0) + info.t_compile;
 }
 
 void Sensitivity::jvp(const Point& at, const double* dp, double* dx, double* ds, double* dy, double* dz, SensitivityInfo& info) {
   const auto t0 = clk::now();
-  const SensPlan& p = m_plan;
+  const SensPlan& p = m_plan.plan;
+  SensState& S = m_state;
   if (dp == nullptr) throw std::runtime_error("slpx: sensitivity jvp: dp is null");
   info.n_p = p.n_p;
   info.t_compile = take_compile_seconds();
   factor(at, info);
-  DeviceNlp& dev = m_model.device();
-  const hipStream_t st = dev.stream();
-  SLPX_HIP_CHECK(hipMemcpyAsync(m_vec.p, dp, static_cast<size_t>(p.n_p) * sizeof(double), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(sens_combine_kernel, dim3(blocks_for(p.dimM)), dim3(kSensThreads), 0, st, view(), m_M.p, m_R.p, m_vec.p, m_rhs1.p,
-                     m_ri1.p);
-  SLPX_HIP_CHECK(hipGetLastError());
+  const hipStream_t st = m_model.device().stream();
+  combine(m_plan, S, dp, st);
   SLPX_HIP_CHECK(hipStreamSynchronize(st));  // (dp is the caller's)
-  solve_one(m_rhs1.p, m_sol.p, info);
-  expand_and_download(1, m_ri1.p, 0, dx, ds, dy, dz);
+  solve_round(m_model, p.dim, S.rhs1.p, p.dim, S.sol.p, p.dim, nullptr, &info);
+  expand_and_download(m_plan, S, 1, S.ri1.p, 0, p.m_i, dx, ds, dy, dz, st);
   info.t_total = seconds_since(t0) + info.t_compile;
 }
 
@@ -370,40 +491,20 @@ void Sensitivity::vjp(const Point& at, const double* vx, double* grad, Sensitivi
 void Sensitivity::vjp_full(const Point& at, const SensCotangent& given, double* grad, SensitivityInfo& info) {
   const auto t0 = clk::now();
   if (!given.vx && !given.vs && !given.vy && !given.vz && !given.vcost) throw std::runtime_error("slpx: sensitivity vjp: no cotangent");
-  const SensPlan& p = m_plan;
+  const SensPlan& p = m_plan.plan;
+  SensState& S = m_state;
   info.n_p = p.n_p;
   info.t_compile = take_compile_seconds();
   factor(at, info);
-  DeviceNlp& dev = m_model.device();
-  const hipStream_t st = dev.stream();
-  // the cotangents behind one another, as they lie in m_cot; one on rows the model does not have is absent
-  std::vector<double> host;
-  SensCotangent v;
-  const auto place = [&](const double* from, int count, const double*& on_device) {
-    if (from == nullptr || count == 0) return;
-    on_device = m_cot.p + host.size();
-    host.insert(host.end(), from, from + count);
-  };
-  place(given.vx, p.n, v.vx);
-  place(given.vs, p.m_i, v.vs);
-  place(given.vy, p.m_e, v.vy);
-  place(given.vz, p.m_i, v.vz);
-  place(given.vcost, 1, v.vcost);
-  if (!host.empty()) SLPX_HIP_CHECK(hipMemcpyAsync(m_cot.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(sens_adjoint_rhs_kernel, dim3(blocks_for(p.dim)), dim3(kSensThreads), 0, st, view(), m_V.p, 0LL, m_s.p, m_z.p, 0LL, v, m_rhs1.p);
-  SLPX_HIP_CHECK(hipGetLastError());
-  SLPX_HIP_CHECK(hipStreamSynchronize(st));  // (`host` is this function's)
-  solve_one(m_rhs1.p, m_sol.p, info);
-  // (w^T R alone — a cotangent on x, or on y — is sens_vjp_kernel's, as before there were others)
-  if (!sens_adjoint_has_t(p.m_i, v.vs, v.vz) && v.vcost == nullptr)
-    hipLaunchKernelGGL(sens_vjp_kernel, dim3(p.n_p, 1), dim3(kSensVjpThreads), 0, st, view(), m_R.p, m_sol.p, m_grad.p);
-  else
-    hipLaunchKernelGGL(sens_vjp_full_kernel, dim3(p.n_p, 1), dim3(kSensVjpThreads), 0, st, view(), m_M.p, m_R.p, m_sol.p, m_ext->device().d_V(),
-                       0LL, m_s.p, m_z.p, 0LL, v, m_grad.p);
-  SLPX_HIP_CHECK(hipGetLastError());
-  std::vector<double> g(static_cast<size_t>(p.n_p));
-  dev.download(m_grad.p, g.data(), g.size());
-  if (grad) std::copy(g.begin(), g.end(), grad);
+  const hipStream_t st = m_model.device().stream();
+  SensExtraRows extras[5];
+  cotangent_arrays(given, p.n, p.m_e, p.m_i, extras);
+  std::vector<double> packed;
+  std::vector<size_t> packed_at;
+  pack_rows(1, extras, 5, packed, packed_at);
+  const SensCotangent v = adjoint_rhs(m_plan, S, extras, packed, packed_at, st);
+  solve_round(m_model, p.dim, S.rhs1.p, p.dim, S.sol.p, p.dim, nullptr, &info);
+  vjp_reduce(m_plan, S, v, grad, st);
   info.t_total = seconds_since(t0) + info.t_compile;
 }
 
@@ -412,7 +513,7 @@ void Sensitivity::unreduced(const Point& at, double* M) {
   // (evaluate() installed unit scales on the model system: the caller's back, as after a factorization)
   if (at.scales_after != nullptr && static_cast<int>(at.scales_after->size()) == m_model.structure().n_scales() && !m_factored)
     m_model.device().set_scaling(*at.scales_after);
-  if (M) m_model.device().download(m_M.p, M, static_cast<size_t>(m_plan.n_p) * m_plan.dimM);
+  if (M) m_model.device().download(m_state.M.p, M, static_cast<size_t>(m_plan.plan.n_p) * m_plan.plan.dimM);
 }
 
 // ---- B instances at once ----
@@ -427,13 +528,13 @@ struct BatchSensitivity::Call {
   std::vector<int32_t> status;
   std::vector<uint8_t> extra_bad, mask;
   std::vector<SensitivityInfo> info;
-  std::vector<double> extra;  // dp / the cotangents behind one another, zeros in the rows of the instances left out: no kernel reads a NaN
+  std::vector<double> extra;  // dp / the cotangents behind one another (pack_rows), zeros in the rows of the instances left out: no kernel reads a NaN
   std::vector<size_t> extra_at;  // where each of them begins in `extra`
   double t_compile = 0.0, t_factor = 0.0;
   int factorizations = 0;
 
   void settle() {
-    const int B = pb->B;
+    const int B = pb->state.B;
     bool any = false;
     for (int b = 0; b < B; ++b) {
       status[b] = pb->base_status[b] != kSensComputed ? pb->base_status[b] : extra_bad[b] ? kSensSkipped : kSensComputed;
@@ -445,12 +546,6 @@ struct BatchSensitivity::Call {
   bool any_computed = false;
 };
 
-SensDev BatchSensitivity::view() const {
-  const SensPlan& p = m_plan;
-  return SensDev{p.n, p.n_p, p.m_e, p.m_i, p.dim, p.dimM, m_m_ptr.p, m_m_src.p, m_red_ptr.p, m_red_src.p, m_red_row.p,
-                 m_ai_rowptr.p, m_ai_col.p, m_ai_src.p, m_g_src.p, m_fp_src.p};
-}
-
 void BatchSensitivity::forget(int batch) {
   const auto it = m_per_batch.find(batch);
   if (it != m_per_batch.end()) it->second.evaluated = it->second.factored = false;
@@ -459,75 +554,31 @@ void BatchSensitivity::forget_all() {
   for (auto& [batch, pb] : m_per_batch) pb.evaluated = pb.factored = false;
 }
 
-// The extended system of this batch size (made on the first call for it) and, on the very first call, the plan.
+// The state of this batch size (its extended system is made on the first call for it) and, on the very first call, the plan.
 BatchSensitivity::PerBatch& BatchSensitivity::per_batch(NewtonSystem& model, NodeId f) {
   const int B = model.batch();
   PerBatch& pb = m_per_batch[B];
-  if (pb.ext) return pb;
+  if (pb.state.ext) return pb;
   const auto t0 = clk::now();
   if (!model.has_device()) throw std::runtime_error("slpx: batched sensitivity: no HIP device");
-  const std::vector<NodeId> params = model.structure().parameter_nodes();
-  if (params.empty()) throw std::runtime_error("slpx: batched sensitivity: the model reaches no parameter");
-  std::vector<NodeId> xp = model.x_nodes();
-  xp.insert(xp.end(), params.begin(), params.end());
-  NewtonOptions opt;
-  opt.tape = model.options().tape;
-  opt.device = model.options().device;
-  opt.batch = B;
-  auto ext = std::make_unique<NewtonSystem>(model.graph(), xp, f, model.c_e_nodes(), model.c_i_nodes(), opt);
-  ext->device().set_scaling(std::vector<double>(ext->structure().n_scales(), 1.0));
-  if (!m_have_plan) {
-    m_plan = build_sens_plan(model.structure(), ext->structure());
-    m_m_ptr.upload(m_plan.m_ptr);
-    m_m_src.upload(m_plan.m_src);
-    m_red_ptr.upload(m_plan.red_ptr);
-    m_red_src.upload(m_plan.red_src);
-    m_red_row.upload(m_plan.red_row);
-    m_ai_rowptr.upload(m_plan.ai_rowptr);
-    m_ai_col.upload(m_plan.ai_col);
-    m_ai_src.upload(m_plan.ai_src);
-    m_g_src.upload(m_plan.g_src);
-    m_fp_src.upload(m_plan.fp_src);
-    m_have_plan = true;
-  }
-  const SensPlan& p = m_plan;
+  if (model.structure().parameter_nodes().empty()) throw std::runtime_error("slpx: batched sensitivity: the model reaches no parameter");
+  auto ext = extended_system(model, f, B);
+  if (!m_plan.built) m_plan.build(model.structure(), ext->structure());
+  const SensPlan& p = m_plan.plan;
   if (ext->structure().nV != p.nVx || model.structure().nV != p.nV || model.kkt().dim != p.dim)
     throw std::runtime_error("slpx: batched sensitivity: the batch system does not belong to the plan");
-  const size_t Bz = static_cast<size_t>(B), n_p = static_cast<size_t>(p.n_p);
-  pb.B = B;
-  pb.M.alloc(Bz * n_p * p.dimM);
-  pb.R.alloc(Bz * n_p * p.dim);
-  pb.V.alloc(Bz * p.nV);
-  pb.s.alloc(Bz * std::max(1, p.m_i));
-  pb.z.alloc(Bz * std::max(1, p.m_i));
-  pb.vec.alloc(Bz * n_p);
-  pb.rhs1.alloc(Bz * p.dim);
-  pb.ri1.alloc(Bz * std::max(1, p.m_i));
-  pb.grad.alloc(Bz * n_p);
-  pb.cot.alloc(Bz * static_cast<size_t>(p.n + 2 * p.m_i + p.m_e + 1));
-  pb.base_status.assign(Bz, kSensSkipped);
-  pb.fact.assign(Bz, SensitivityInfo{});
-  pb.ext = std::move(ext);
+  pb.state.B = B;
+  pb.state.threads = kSensBatchThreads;
+  pb.state.ext = std::move(ext);
+  pb.base_status.assign(static_cast<size_t>(B), kSensSkipped);
+  pb.fact.assign(static_cast<size_t>(B), SensitivityInfo{});
   pb.compile_seconds = seconds_since(t0);
   return pb;
 }
 
-// room for `columns` solutions per instance and their expansion
-void BatchSensitivity::ensure_columns(PerBatch& pb, int columns) {
-  if (pb.sol_columns >= columns) return;
-  const SensPlan& p = m_plan;
-  const size_t rows = static_cast<size_t>(pb.B) * columns;
-  pb.sol.alloc(rows * p.dim);
-  pb.dx.alloc(std::max<size_t>(1, rows * p.n));
-  pb.ds.alloc(std::max<size_t>(1, rows * p.m_i));
-  pb.dy.alloc(std::max<size_t>(1, rows * p.m_e));
-  pb.dz.alloc(std::max<size_t>(1, rows * p.m_i));
-  pb.sol_columns = columns;
-}
-
-// The checks every call makes, the classification of its instances, and whether what the last call of this batch size
-// left in memory is still the system of these rows.
-void BatchSensitivity::begin(Call& c, NewtonSystem& model, NodeId f, const Rows& at, const SensExtraRows* extras, int n_extras) {
+// The checks every call makes, room for `columns` solutions per instance, the classification of its instances, and
+// whether what the last call of this batch size left in memory is still the system of these rows.
+void BatchSensitivity::begin(Call& c, NewtonSystem& model, NodeId f, const Rows& at, const SensExtraRows* extras, int n_extras, int columns) {
   c.t0 = clk::now();
   c.model = &model;
   c.at = at;
@@ -538,10 +589,11 @@ void BatchSensitivity::begin(Call& c, NewtonSystem& model, NodeId f, const Rows&
   c.pb = &pb;
   c.t_compile = pb.compile_seconds;
   pb.compile_seconds = 0.0;
-  const SensPlan& p = m_plan;
+  const SensPlan& p = m_plan.plan;
   if (at.x == nullptr || at.mu == nullptr || at.params == nullptr || (p.m_i && (at.s == nullptr || at.z == nullptr)) ||
       (p.m_e && at.y == nullptr))
     throw std::runtime_error("slpx: batched sensitivity: a required input is null");
+  size_state(pb.state, p, columns);
   const size_t Bz = static_cast<size_t>(B);
   // the rows as one vector: what the kept factorization is the factorization OF
   std::vector<double> key;
@@ -566,11 +618,7 @@ void BatchSensitivity::begin(Call& c, NewtonSystem& model, NodeId f, const Rows&
   if (n_extras > 0) {
     std::vector<int32_t> st(Bz);
     sens_classify_extras(B, extras, n_extras, st.data());
-    c.extra_at.assign(static_cast<size_t>(n_extras), 0);
-    for (int k = 0; k < n_extras; ++k) {
-      c.extra_at[k] = c.extra.size();
-      if (extras[k].rows != nullptr) c.extra.insert(c.extra.end(), extras[k].rows, extras[k].rows + Bz * extras[k].width);
-    }
+    pack_rows(B, extras, n_extras, c.extra, c.extra_at);
     for (size_t b = 0; b < Bz; ++b)
       if (st[b] != kSensComputed) {
         c.extra_bad[b] = 1;
@@ -588,9 +636,9 @@ void BatchSensitivity::begin(Call& c, NewtonSystem& model, NodeId f, const Rows&
 void BatchSensitivity::evaluate(Call& c) {
   PerBatch& pb = *c.pb;
   if (pb.evaluated) return;
-  const SensPlan& p = m_plan;
+  const SensPlan& p = m_plan.plan;
   const Rows& at = c.at;
-  const size_t B = static_cast<size_t>(pb.B), n = p.n, n_p = p.n_p, m_e = p.m_e, m_i = p.m_i;
+  const size_t B = static_cast<size_t>(pb.state.B), n = p.n, n_p = p.n_p, m_e = p.m_e, m_i = p.m_i;
   pb.factored = false;
   size_t h = B;
   for (size_t b = 0; b < B && h == B; ++b)
@@ -615,7 +663,7 @@ void BatchSensitivity::evaluate(Call& c) {
     mu[b] = at.mu[from];
   }
   DeviceNlp& dev = c.model->device();
-  DeviceNlp& ext = pb.ext->device();
+  DeviceNlp& ext = pb.state.ext->device();
   ext.upload_x(xp.data());
   ext.upload_duals(s.data(), y.data(), z.data());
   ext.sweep_full();
@@ -642,15 +690,7 @@ void BatchSensitivity::evaluate(Call& c) {
   dev.upload_mu(mu.data());
   dev.sweep_full();
   const hipStream_t st = dev.stream();
-  SLPX_HIP_CHECK(hipMemcpyAsync(pb.V.p, dev.d_V(), B * p.nV * sizeof(double), hipMemcpyDeviceToDevice, st));
-  if (m_i) {
-    SLPX_HIP_CHECK(hipMemcpyAsync(pb.s.p, dev.d_s(), B * m_i * sizeof(double), hipMemcpyDeviceToDevice, st));
-    SLPX_HIP_CHECK(hipMemcpyAsync(pb.z.p, dev.d_z(), B * m_i * sizeof(double), hipMemcpyDeviceToDevice, st));
-  }
-  hipLaunchKernelGGL(sens_rhs_kernel, dim3(blocks_for(static_cast<int64_t>(p.n_p) * p.dimM, kSensBatchThreads), pb.B), dim3(kSensBatchThreads), 0, st, view(), ext.d_V(),
-                     static_cast<long long>(p.nVx), pb.V.p, static_cast<long long>(p.nV), pb.s.p, pb.z.p, static_cast<long long>(m_i), pb.M.p,
-                     pb.R.p);
-  SLPX_HIP_CHECK(hipGetLastError());
+  gather(m_plan, pb.state, dev, st);
   dev.assemble();
   dev.build_rhs();
   // (what is in memory IS the system now — a request for a step that never came is void; assemble() and build_rhs()
@@ -661,43 +701,32 @@ void BatchSensitivity::evaluate(Call& c) {
   pb.evaluated = true;
 }
 
-// NewtonSystem::compute() for the instances that are differentiated, each from a cleared memory; the batch system's own
-// memory is put back afterwards.  An instance whose system cannot be factored leaves the call here (kSensNotFactored).
+// The instances that are differentiated, factored from a cleared memory.  An instance whose system cannot be factored
+// leaves the call here (kSensNotFactored); one that can reports the accepted inertia.
 void BatchSensitivity::factor(Call& c) {
   evaluate(c);
   PerBatch& pb = *c.pb;
-  const int B = pb.B;
+  const int B = pb.state.B;
   if (!pb.factored) {
     const auto t0 = clk::now();
     std::vector<uint8_t> mask(B, 0);
     bool any = false;
     for (int b = 0; b < B; ++b) any = (mask[b] = pb.base_status[b] == kSensComputed ? 1 : 0) || any;
     if (any) {
-      NewtonSystem& model = *c.model;
-      const NewtonSystem::RegularizationState saved = model.regularization_state();
-      model.reset_regularization();
-      std::vector<FactorInfo> res;
-      try {
-        res = model.compute(/*solve_speculatively=*/false, mask);
-      } catch (...) {
-        model.set_regularization_state(saved);
-        throw;
-      }
-      const std::vector<double> delta = model.hessian_regularization(), gamma = model.constraint_jacobian_regularization();
-      c.factorizations = model.last_factorizations();
-      model.set_regularization_state(saved);
+      const Factored fac = factor_from_cleared_memory(*c.model, &mask);
+      c.factorizations = fac.factorizations;
       std::vector<LdltStats> stats;
-      model.device().read_stats(stats);
+      c.model->device().read_stats(stats);
       for (int b = 0; b < B; ++b) {
         if (!mask[b]) continue;
         SensitivityInfo& fi = pb.fact[b];
-        fi.delta = delta[b];
-        fi.gamma = gamma[b];
-        if (res[b] == FactorInfo::Success) {
+        fi.delta = fac.delta[b];
+        fi.gamma = fac.gamma[b];
+        if (fac.result[b] == FactorInfo::Success) {
           // (the counters in memory are those of the LAST launch, which an instance accepted earlier sat out: what the
           // policy accepts has the ideal inertia and nothing else, ldlt_policy.hpp: ldlt_judge)
-          fi.n_pos = m_plan.n;
-          fi.n_neg = m_plan.m_e;
+          fi.n_pos = m_plan.plan.n;
+          fi.n_neg = m_plan.plan.m_e;
           fi.n_zero = 0;
         } else {  // (gave up in the last launch it took part in; the counters as they stand)
           fi.n_pos = stats[b].n_pos;
@@ -718,27 +747,6 @@ void BatchSensitivity::factor(Call& c) {
   }
 }
 
-void BatchSensitivity::solve_round(Call& c, const double* rhs, size_t rhs_pitch, double* sol, size_t sol_pitch) {
-  if (!c.any_computed) return;
-  PerBatch& pb = *c.pb;
-  DeviceNlp& dev = c.model->device();
-  const size_t width = static_cast<size_t>(m_plan.dim) * sizeof(double);
-  const hipStream_t st = dev.stream();
-  SLPX_HIP_CHECK(hipMemcpy2DAsync(dev.rhs_raw(), width, rhs, rhs_pitch * sizeof(double), width, pb.B, hipMemcpyDeviceToDevice, st));
-  dev.system_written_by_caller(/*lhs=*/false, /*rhs=*/true);
-  dev.solve();
-  const NewtonSystem::Refinement ref = c.model->refine(2, &c.mask);
-  const NewtonSystem::ErrorBounds eb = c.model->error_bounds(&c.mask, /*want_ferr=*/false);
-  for (int b = 0; b < pb.B; ++b) {
-    if (!c.mask[b]) continue;
-    SensitivityInfo& info = c.info[b];
-    info.solves += 1 + ref.accepted[b];
-    info.refine_steps += ref.accepted[b];
-    if (!(eb.berr[b] <= info.berr_max)) info.berr_max = eb.berr[b];  // (a NaN shows)
-  }
-  SLPX_HIP_CHECK(hipMemcpy2DAsync(sol, sol_pitch * sizeof(double), dev.d_p(), width, width, pb.B, hipMemcpyDeviceToDevice, st));
-}
-
 namespace {
 // rows of `width` entries, one per (instance, column): NaN where the instance was not computed
 void nan_rows(double* out, const std::vector<int32_t>& status, size_t per_instance) {
@@ -748,28 +756,12 @@ void nan_rows(double* out, const std::vector<int32_t>& status, size_t per_instan
 }
 }  // namespace
 
-void BatchSensitivity::expand_and_download(Call& c, int columns, const double* r_i, long long r_i_column, long long r_i_instance,
-                                           double* dx, double* ds, double* dy, double* dz) {
-  const SensPlan& p = m_plan;
-  PerBatch& pb = *c.pb;
-  const size_t rows = static_cast<size_t>(pb.B) * columns;
-  if (c.any_computed) {
-    const hipStream_t st = c.model->device().stream();
-    hipLaunchKernelGGL(sens_expand_kernel, dim3(blocks_for(static_cast<int64_t>(columns) * p.dimM, kSensBatchThreads), pb.B), dim3(kSensBatchThreads), 0, st, view(),
-                       columns, pb.V.p, static_cast<long long>(p.nV), pb.s.p, pb.z.p, static_cast<long long>(p.m_i), pb.sol.p, r_i, r_i_column,
-                       r_i_instance, pb.dx.p, pb.ds.p, pb.dy.p, pb.dz.p);
-    SLPX_HIP_CHECK(hipGetLastError());
-    // (the kernel wrote the caller's layout: one copy per output array, one wait for all)
-    const auto fetch = [&](const DevBuf<double>& from, double* to, int width) {
-      const size_t count = rows * width;
-      if (to != nullptr && count) SLPX_HIP_CHECK(hipMemcpyAsync(to, from.p, count * sizeof(double), hipMemcpyDeviceToHost, st));
-    };
-    fetch(pb.dx, dx, p.n);
-    fetch(pb.ds, ds, p.m_i);
-    fetch(pb.dy, dy, p.m_e);
-    fetch(pb.dz, dz, p.m_i);
-    SLPX_HIP_CHECK(hipStreamSynchronize(st));
-  }
+// the expansion for the instances that were computed, NaN rows for the others
+void BatchSensitivity::expand(Call& c, int columns, const double* r_i, long long r_i_column, long long r_i_instance, double* dx, double* ds,
+                              double* dy, double* dz) {
+  const SensPlan& p = m_plan.plan;
+  if (c.any_computed)
+    expand_and_download(m_plan, c.pb->state, columns, r_i, r_i_column, r_i_instance, dx, ds, dy, dz, c.model->device().stream());
   nan_rows(dx, c.status, static_cast<size_t>(columns) * p.n);
   nan_rows(ds, c.status, static_cast<size_t>(columns) * p.m_i);
   nan_rows(dy, c.status, static_cast<size_t>(columns) * p.m_e);
@@ -780,9 +772,9 @@ void BatchSensitivity::finish(Call& c, int32_t* status, SensitivityInfo* info) {
   const double t_total = seconds_since(c.t0) + c.t_compile;
   if (status) std::copy(c.status.begin(), c.status.end(), status);
   if (info == nullptr) return;
-  for (int b = 0; b < c.pb->B; ++b) {
+  for (int b = 0; b < c.pb->state.B; ++b) {
     info[b] = c.info[b];
-    info[b].n_p = m_plan.n_p;
+    info[b].n_p = m_plan.plan.n_p;
     info[b].solve_status = 0;  // (the call is not told it)
     info[b].t_compile = c.t_compile;
     info[b].t_factor = c.t_factor;
@@ -793,15 +785,15 @@ void BatchSensitivity::finish(Call& c, int32_t* status, SensitivityInfo* info) {
 void BatchSensitivity::jacobian(NewtonSystem& model, NodeId f, const Rows& at, double* dx, double* ds, double* dy, double* dz,
                                 int32_t* status, SensitivityInfo* info) {
   Call c;
-  begin(c, model, f, at, nullptr, 0);
-  const SensPlan& p = m_plan;
-  PerBatch& pb = *c.pb;
-  ensure_columns(pb, p.n_p);
+  begin(c, model, f, at, nullptr, 0, static_cast<int>(model.structure().parameter_nodes().size()));
+  const SensPlan& p = m_plan.plan;
+  SensState& S = c.pb->state;
   factor(c);
   // round q: column q of every instance
   const size_t pitch = static_cast<size_t>(p.n_p) * p.dim;
-  for (int q = 0; q < p.n_p; ++q) solve_round(c, pb.R.p + static_cast<size_t>(q) * p.dim, pitch, pb.sol.p + static_cast<size_t>(q) * p.dim, pitch);
-  expand_and_download(c, p.n_p, pb.M.p + p.dim, p.dimM, static_cast<long long>(p.n_p) * p.dimM, dx, ds, dy, dz);
+  for (int q = 0; q < p.n_p && c.any_computed; ++q)
+    solve_round(model, p.dim, S.R.p + static_cast<size_t>(q) * p.dim, pitch, S.sol.p + static_cast<size_t>(q) * p.dim, pitch, &c.mask, c.info.data());
+  expand(c, p.n_p, S.M.p + p.dim, p.dimM, static_cast<long long>(p.n_p) * p.dimM, dx, ds, dy, dz);
   finish(c, status, info);
 }
 
@@ -810,20 +802,15 @@ void BatchSensitivity::jvp(NewtonSystem& model, NodeId f, const Rows& at, const 
   if (dp == nullptr) throw std::runtime_error("slpx: batched sensitivity jvp: dp is null");
   Call c;
   const SensExtraRows extra{dp, static_cast<int>(model.structure().parameter_nodes().size())};
-  begin(c, model, f, at, &extra, 1);
-  const SensPlan& p = m_plan;
-  PerBatch& pb = *c.pb;
-  ensure_columns(pb, 1);
+  begin(c, model, f, at, &extra, 1, 1);
+  const SensPlan& p = m_plan.plan;
+  SensState& S = c.pb->state;
   factor(c);
   if (c.any_computed) {
-    const hipStream_t st = model.device().stream();
-    SLPX_HIP_CHECK(hipMemcpyAsync(pb.vec.p, c.extra.data(), c.extra.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(sens_combine_kernel, dim3(blocks_for(p.dimM, kSensBatchThreads), pb.B), dim3(kSensBatchThreads), 0, st, view(), pb.M.p, pb.R.p, pb.vec.p, pb.rhs1.p,
-                       pb.ri1.p);
-    SLPX_HIP_CHECK(hipGetLastError());
-    solve_round(c, pb.rhs1.p, p.dim, pb.sol.p, p.dim);
+    combine(m_plan, S, c.extra.data(), model.device().stream());
+    solve_round(model, p.dim, S.rhs1.p, p.dim, S.sol.p, p.dim, &c.mask, c.info.data());
   }
-  expand_and_download(c, 1, pb.ri1.p, 0, p.m_i, dx, ds, dy, dz);
+  expand(c, 1, S.ri1.p, 0, p.m_i, dx, ds, dy, dz);
   finish(c, status, info);
 }
 
@@ -839,38 +826,18 @@ void BatchSensitivity::vjp_full(NewtonSystem& model, NodeId f, const Rows& at, c
                                 SensitivityInfo* info) {
   if (!given.vx && !given.vs && !given.vy && !given.vz && !given.vcost) throw std::runtime_error("slpx: batched sensitivity vjp: no cotangent");
   const NlpStructure& ms = model.structure();
-  // (a cotangent on rows the model does not have is absent)
-  const SensExtraRows extras[5] = {{given.vx, ms.n}, {ms.m_i ? given.vs : nullptr, ms.m_i}, {ms.m_e ? given.vy : nullptr, ms.m_e},
-                                   {ms.m_i ? given.vz : nullptr, ms.m_i}, {given.vcost, 1}};
+  SensExtraRows extras[5];
+  cotangent_arrays(given, ms.n, ms.m_e, ms.m_i, extras);
   Call c;
-  begin(c, model, f, at, extras, 5);
-  const SensPlan& p = m_plan;
-  PerBatch& pb = *c.pb;
-  ensure_columns(pb, 1);
+  begin(c, model, f, at, extras, 5, 1);
+  const SensPlan& p = m_plan.plan;
+  SensState& S = c.pb->state;
   factor(c);
-  const size_t B = static_cast<size_t>(pb.B);
   if (c.any_computed) {
-    DeviceNlp& dev = model.device();
-    const hipStream_t st = dev.stream();
-    SensCotangent v;
-    const double** on_device[5] = {&v.vx, &v.vs, &v.vy, &v.vz, &v.vcost};
-    for (int k = 0; k < 5; ++k)
-      if (extras[k].rows != nullptr) *on_device[k] = pb.cot.p + c.extra_at[k];
-    if (!c.extra.empty()) SLPX_HIP_CHECK(hipMemcpyAsync(pb.cot.p, c.extra.data(), c.extra.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(sens_adjoint_rhs_kernel, dim3(blocks_for(p.dim, kSensBatchThreads), pb.B), dim3(kSensBatchThreads), 0, st, view(), pb.V.p,
-                       static_cast<long long>(p.nV), pb.s.p, pb.z.p, static_cast<long long>(p.m_i), v, pb.rhs1.p);
-    SLPX_HIP_CHECK(hipGetLastError());
-    SLPX_HIP_CHECK(hipStreamSynchronize(st));
-    solve_round(c, pb.rhs1.p, p.dim, pb.sol.p, p.dim);
-    // (w^T R alone is sens_vjp_kernel's, as before there were other cotangents)
-    if (!sens_adjoint_has_t(p.m_i, v.vs, v.vz) && v.vcost == nullptr)
-      hipLaunchKernelGGL(sens_vjp_kernel, dim3(p.n_p, pb.B), dim3(kSensVjpThreads), 0, st, view(), pb.R.p, pb.sol.p, pb.grad.p);
-    else
-      hipLaunchKernelGGL(sens_vjp_full_kernel, dim3(p.n_p, pb.B), dim3(kSensVjpThreads), 0, st, view(), pb.M.p, pb.R.p, pb.sol.p,
-                         pb.ext->device().d_V(), static_cast<long long>(p.nVx), pb.s.p, pb.z.p, static_cast<long long>(p.m_i), v, pb.grad.p);
-    SLPX_HIP_CHECK(hipGetLastError());
-    if (grad) dev.download(pb.grad.p, grad, B * p.n_p);
-    else SLPX_HIP_CHECK(hipStreamSynchronize(st));
+    const hipStream_t st = model.device().stream();
+    const SensCotangent v = adjoint_rhs(m_plan, S, extras, c.extra, c.extra_at, st);
+    solve_round(model, p.dim, S.rhs1.p, p.dim, S.sol.p, p.dim, &c.mask, c.info.data());
+    vjp_reduce(m_plan, S, v, grad, st);
   }
   nan_rows(grad, c.status, p.n_p);
   finish(c, status, info);
@@ -878,14 +845,14 @@ void BatchSensitivity::vjp_full(NewtonSystem& model, NodeId f, const Rows& at, c
 
 void BatchSensitivity::unreduced(NewtonSystem& model, NodeId f, const Rows& at, double* M, int32_t* status) {
   Call c;
-  begin(c, model, f, at, nullptr, 0);
+  begin(c, model, f, at, nullptr, 0, 0);
   evaluate(c);
-  const size_t per_instance = static_cast<size_t>(m_plan.n_p) * m_plan.dimM;
+  const size_t per_instance = static_cast<size_t>(m_plan.plan.n_p) * m_plan.plan.dimM;
   // (an instance a kept factorization found singular still has its M: only what was skipped has none)
   std::vector<int32_t> st(c.status);
   bool any = false;
   for (size_t b = 0; b < st.size(); ++b) any = (st[b] = c.pb->base_status[b] == kSensSkipped ? kSensSkipped : kSensComputed) == kSensComputed || any;
-  if (M && any) model.device().download(c.pb->M.p, M, static_cast<size_t>(c.pb->B) * per_instance);
+  if (M && any) model.device().download(c.pb->state.M.p, M, static_cast<size_t>(c.pb->state.B) * per_instance);
   nan_rows(M, st, per_instance);
   if (status) std::copy(st.begin(), st.end(), status);
 }

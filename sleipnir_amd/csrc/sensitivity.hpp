@@ -13,8 +13,16 @@
 // units, whatever scaling the solve ran with.  The scaling the caller names is installed again afterwards.
 //
 // The extended system is a whole NewtonSystem (its KKT plan and symbolic factorization are made and never used: the
-// shortest route, and the measured cost is in profiles/sensitivity.txt); it lives as long as this object, which the
-// problem drops when the model is compiled again.
+// shortest route, and the measured cost is in profiles/sensitivity.txt); it lives as long as the driver that made it,
+// which the problem drops when the model is compiled again.
+//
+// TWO DRIVERS, ONE LAYER.  Sensitivity differentiates the problem's own iterate and throws where it cannot;
+// BatchSensitivity differentiates B rows it is given and reports a status per instance.  The device work under both is
+// written once (sensitivity.hip): the plan on the device (SensPlanDev), the extended system, the state of one system
+// of B instances (SensState) and the stages that take it — gather after the sweeps, combine, adjoint right-hand side,
+// vjp reduction, expand and download, factor from a cleared regularization memory, one round of solves.  The problem's
+// own system is a state with B = 1.  What a driver owns is its contract: which rows it reads, what it does with the
+// outcome of the factorization, and what it leaves on the model system.
 #pragma once
 
 #include <map>
@@ -43,6 +51,29 @@ struct SensDev {
   const int32_t *m_ptr, *m_src, *red_ptr, *red_src, *red_row, *ai_rowptr, *ai_col, *ai_src, *g_src, *fp_src;
 };
 
+// The plan and its tables on the device.  A function of the model alone: one serves every batch size.
+struct SensPlanDev {
+  SensPlan plan;
+  DevBuf<int32_t> m_ptr, m_src, red_ptr, red_src, red_row, ai_rowptr, ai_col, ai_src, g_src, fp_src;
+  bool built = false;
+  // build_sens_plan of the two structures (the model's and the extended one's), uploaded
+  void build(const NlpStructure& model, const NlpStructure& extended);
+  SensDev view() const;
+};
+
+// The state of one system of B instances that is differentiated: its extended system over x' = [x ; p] and the working
+// buffers, each with instance b's part at b times its size per instance.
+struct SensState {
+  int B = 0;
+  int threads = 0;  // the workgroup size of the launches for this system: 256 for the problem's own, one wave for a batch system
+  std::unique_ptr<NewtonSystem> ext;
+  // M [n_p][dimM], R [n_p][dim]; the model's V, s, z at the iterate (copies: the model system's own are its caller's
+  // again after a call); dp; the right-hand side and r_i of one product; grad [n_p]; the cotangents of the full vjp
+  DevBuf<double> M, R, V, s, z, vec, rhs1, ri1, grad, cot;
+  DevBuf<double> sol, dx, ds, dy, dz;  // `columns` solutions per instance and their expansion
+  int columns = 0;
+};
+
 class Sensitivity {
  public:
   // Where the derivatives are taken: the iterate in the user's units, the parameters' values (the order of
@@ -61,8 +92,6 @@ class Sensitivity {
   Sensitivity(const Sensitivity&) = delete;
   Sensitivity& operator=(const Sensitivity&) = delete;
 
-  const SensPlan& plan() const { return m_plan; }
-  const NewtonSystem& extended() const { return *m_ext; }
   // seconds the constructor took; reported as t_compile by the first product and 0 afterwards
   double take_compile_seconds() {
     const double t = m_compile_seconds;
@@ -91,25 +120,15 @@ class Sensitivity {
  private:
   void evaluate(const Point& at);
   void factor(const Point& at, SensitivityInfo& info);
-  // rhs (device, dim) -> the refined solution into sol (device, dim)
-  void solve_one(const double* rhs, double* sol, SensitivityInfo& info);
-  void expand_and_download(int columns, const double* r_i, long long r_i_stride, double* dx, double* ds, double* dy, double* dz);
-  SensDev view() const;
 
   NewtonSystem& m_model;
-  std::unique_ptr<NewtonSystem> m_ext;
-  SensPlan m_plan;
+  SensPlanDev m_plan;
+  SensState m_state;  // B = 1, n_p columns
   double m_compile_seconds = 0.0;
   bool m_evaluated = false, m_factored = false;
   // of the factorization in memory (reported by every product that reuses it)
   int32_t m_n_pos = 0, m_n_neg = 0, m_n_zero = 0;
   double m_delta = 0.0, m_gamma = 0.0;
-
-  DevBuf<int32_t> m_m_ptr, m_m_src, m_red_ptr, m_red_src, m_red_row, m_ai_rowptr, m_ai_col, m_ai_src, m_g_src, m_fp_src;
-  DevBuf<double> m_cot;  // the cotangents of vjp_full: vx, vs, vy, vz, vcost behind one another
-  // M, R; the model's V, s, z at the iterate (copies: the model system's own are its caller's again after a product)
-  DevBuf<double> m_M, m_R, m_V, m_s, m_z;
-  DevBuf<double> m_vec, m_rhs1, m_ri1, m_sol, m_dx, m_ds, m_dy, m_dz, m_grad;
 };
 
 // The same derivatives for B iterates at once, instance b with respect to ITS parameter row (include/slpx.h: batched
@@ -139,8 +158,6 @@ class BatchSensitivity {
   // evaluates and factors again.
   void forget(int batch);
   void forget_all();
-  bool has_plan() const { return m_have_plan; }
-  const SensPlan& plan() const { return m_plan; }
 
   // `f`: the cost's root (kNull: none).  status [B] (sens_plan.hpp: kSensComputed, ...), info [B] (null: not wanted).
   // Rows of an instance whose status is not 0 are NaN in every output.  Any output may be null.
@@ -160,36 +177,28 @@ class BatchSensitivity {
   void unreduced(NewtonSystem& model, NodeId f, const Rows& at, double* M, int32_t* status);
 
  private:
-  // what belongs to one batch size
+  // what belongs to one batch size: the state of its batch system, and what this driver knows about it
   struct PerBatch {
-    int B = 0;
-    std::unique_ptr<NewtonSystem> ext;
+    SensState state;
     double compile_seconds = 0.0;
     bool evaluated = false, factored = false;
     std::vector<double> key;            // the rows `evaluated` / `factored` speak of: x, s, y, z, mu, params as given
     std::vector<int32_t> base_status;   // of those rows: classification, then kSensNotFactored from the factorization
     std::vector<SensitivityInfo> fact;  // per instance: inertia, delta, gamma of the factorization in memory
-    DevBuf<double> M, R, V, s, z, vec, rhs1, ri1, sol, dx, ds, dy, dz, grad, cot;
-    int sol_columns = 0;
   };
   struct Call;  // one call's bookkeeping (sensitivity.hip)
 
   PerBatch& per_batch(NewtonSystem& model, NodeId f);
-  void ensure_columns(PerBatch& pb, int columns);
-  // extras: the arrays beside the rows (dp; the cotangents), classified together and kept behind one another in c.extra
-  void begin(Call& c, NewtonSystem& model, NodeId f, const Rows& at, const SensExtraRows* extras, int n_extras);
+  // extras: the arrays beside the rows (dp; the cotangents), classified together and kept behind one another in c.extra;
+  // columns: the solutions per instance the call needs room for
+  void begin(Call& c, NewtonSystem& model, NodeId f, const Rows& at, const SensExtraRows* extras, int n_extras, int columns);
   void evaluate(Call& c);
   void factor(Call& c);
-  // the right-hand sides in rhs (device, [B] rows `rhs_pitch` doubles apart) -> the refined solutions into sol likewise
-  void solve_round(Call& c, const double* rhs, size_t rhs_pitch, double* sol, size_t sol_pitch);
-  void expand_and_download(Call& c, int columns, const double* r_i, long long r_i_column, long long r_i_instance, double* dx,
-                           double* ds, double* dy, double* dz);
+  void expand(Call& c, int columns, const double* r_i, long long r_i_column, long long r_i_instance, double* dx, double* ds, double* dy,
+              double* dz);
   void finish(Call& c, int32_t* status, SensitivityInfo* info);
-  SensDev view() const;
 
-  bool m_have_plan = false;
-  SensPlan m_plan;
-  DevBuf<int32_t> m_m_ptr, m_m_src, m_red_ptr, m_red_src, m_red_row, m_ai_rowptr, m_ai_col, m_ai_src, m_g_src, m_fp_src;
+  SensPlanDev m_plan;  // built by the first call, shared by every batch size
   std::map<int, PerBatch> m_per_batch;
 };
 

@@ -232,13 +232,8 @@ class ProblemF64 {
   // every parameter's column: n_p solves
   Sensitivities sensitivity() {
     const slpx::Sensitivity::Point at = sensitivity_point();
-    const auto& st = m_sys->structure();
-    const size_t n_p = m_iterate_parameters.size();
     Sensitivities out;
-    out.dx.resize(n_p * st.n);
-    out.ds.resize(n_p * st.m_i);
-    out.dy.resize(n_p * st.m_e);
-    out.dz.resize(n_p * st.m_i);
+    size_blocks(m_sys->structure(), m_iterate_parameters.size(), out.dx, out.ds, out.dy, out.dz);
     out.info.solve_status = m_iterate_status;
     m_sens->jacobian(at, out.dx.data(), out.ds.data(), out.dy.data(), out.dz.data(), out.info);
     return out;
@@ -247,12 +242,8 @@ class ProblemF64 {
   Iterate sensitivity_jvp(std::span<const double> dp, slpx::SensitivityInfo* info = nullptr) {
     const slpx::Sensitivity::Point at = sensitivity_point();
     if (dp.size() != m_iterate_parameters.size()) throw std::runtime_error("sensitivity_jvp: wrong number of values in dp");
-    const auto& st = m_sys->structure();
     Iterate d;
-    d.x.resize(st.n);
-    d.s.resize(st.m_i);
-    d.y.resize(st.m_e);
-    d.z.resize(st.m_i);
+    size_blocks(m_sys->structure(), 1, d.x, d.s, d.y, d.z);
     slpx::SensitivityInfo local;
     local.solve_status = m_iterate_status;
     m_sens->jvp(at, dp.data(), d.x.data(), d.s.data(), d.y.data(), d.z.data(), local);
@@ -263,12 +254,9 @@ class ProblemF64 {
   std::vector<double> sensitivity_vjp(std::span<const double> vx, slpx::SensitivityInfo* info = nullptr) {
     const slpx::Sensitivity::Point at = sensitivity_point();
     if (vx.size() != static_cast<size_t>(m_sys->structure().n)) throw std::runtime_error("sensitivity_vjp: wrong number of values in vx");
-    std::vector<double> grad(m_iterate_parameters.size());
-    slpx::SensitivityInfo local;
-    local.solve_status = m_iterate_status;
-    m_sens->vjp(at, vx.data(), grad.data(), local);
-    if (info) *info = local;
-    return grad;
+    slpx::SensCotangent c;
+    c.vx = vx.data();
+    return sensitivity_vjp_at(at, c, /*x_alone=*/true, info);
   }
   // Cotangents on the whole end iterate and on the optimal cost — cost: the value the solve reports, f as minimize()
   // or maximize() stored it, in the user's units.  An empty span is absent; at least one must be given.
@@ -280,25 +268,9 @@ class ProblemF64 {
   // whichever blocks (sens_plan.hpp: the adjoint).  With x alone: sensitivity_vjp(vx), bit for bit.
   std::vector<double> sensitivity_vjp(const Cotangent& v, slpx::SensitivityInfo* info = nullptr) {
     const slpx::Sensitivity::Point at = sensitivity_point();
-    const auto& st = m_sys->structure();
-    const auto given = [](std::span<const double> a, size_t count, const char* what) -> const double* {
-      if (a.empty()) return nullptr;
-      if (a.size() != count) throw std::runtime_error(std::string("sensitivity_vjp: wrong number of values in the cotangent on ") + what);
-      return a.data();
-    };
-    slpx::SensCotangent c;
-    c.vx = given(v.x, st.n, "x");
-    c.vs = given(v.s, st.m_i, "s");
-    c.vy = given(v.y, st.m_e, "y");
-    c.vz = given(v.z, st.m_i, "z");
-    c.vcost = given(v.cost, 1, "the cost");
-    if (!c.vx && !c.vs && !c.vy && !c.vz && !c.vcost) throw std::runtime_error("sensitivity_vjp: no cotangent");
-    std::vector<double> grad(m_iterate_parameters.size());
-    slpx::SensitivityInfo local;
-    local.solve_status = m_iterate_status;
-    m_sens->vjp_full(at, c, grad.data(), local);
-    if (info) *info = local;
-    return grad;
+    const slpx::SensCotangent c = cotangents_given(v.x, v.s, v.y, v.z, v.cost, 1, m_sys->structure(), "sensitivity_vjp",
+                                                   ": wrong number of values in the cotangent on ", "");
+    return sensitivity_vjp_at(at, c, /*x_alone=*/false, info);
   }
   // d cost/dp [n_p]: the cotangent 1 on the cost alone
   std::vector<double> cost_gradient(slpx::SensitivityInfo* info = nullptr) {
@@ -357,10 +329,7 @@ class ProblemF64 {
   BatchSensitivities sensitivity_batch_vjp(int batch, const BatchIterate& it, std::span<const double> params, std::span<const double> vx) {
     BatchCall c = batch_sensitivity_call(batch, it, params, "sensitivity_batch_vjp");
     if (vx.size() != c.B * c.n) throw std::runtime_error("sensitivity_batch_vjp: vx must have batch x n values");
-    BatchSensitivities out;
-    out.grad.resize(c.B * c.n_p);
-    out.status.resize(c.B);
-    out.info.resize(c.B);
+    BatchSensitivities out = c.gradients();
     m_batch_sens->vjp(*c.sys, cost_root(), c.rows, vx.data(), out.grad.data(), out.status.data(), out.info.data());
     return out;
   }
@@ -371,22 +340,9 @@ class ProblemF64 {
   };
   BatchSensitivities sensitivity_batch_vjp(int batch, const BatchIterate& it, std::span<const double> params, const BatchCotangent& v) {
     BatchCall c = batch_sensitivity_call(batch, it, params, "sensitivity_batch_vjp");
-    const auto given = [&](std::span<const double> a, size_t count, const char* what) -> const double* {
-      if (a.empty()) return nullptr;
-      if (a.size() != c.B * count) throw std::runtime_error(std::string("sensitivity_batch_vjp: the cotangent on ") + what + " must have batch rows of the model's size");
-      return a.data();
-    };
-    slpx::SensCotangent sc;
-    sc.vx = given(v.x, c.n, "x");
-    sc.vs = given(v.s, c.m_i, "s");
-    sc.vy = given(v.y, c.m_e, "y");
-    sc.vz = given(v.z, c.m_i, "z");
-    sc.vcost = given(v.cost, 1, "the cost");
-    if (!sc.vx && !sc.vs && !sc.vy && !sc.vz && !sc.vcost) throw std::runtime_error("sensitivity_batch_vjp: no cotangent");
-    BatchSensitivities out;
-    out.grad.resize(c.B * c.n_p);
-    out.status.resize(c.B);
-    out.info.resize(c.B);
+    const slpx::SensCotangent sc = cotangents_given(v.x, v.s, v.y, v.z, v.cost, c.B, c.sys->structure(), "sensitivity_batch_vjp",
+                                                    ": the cotangent on ", " must have batch rows of the model's size");
+    BatchSensitivities out = c.gradients();
     m_batch_sens->vjp_full(*c.sys, cost_root(), c.rows, sc, out.grad.data(), out.status.data(), out.info.data());
     return out;
   }
@@ -407,15 +363,56 @@ class ProblemF64 {
     size_t B = 0, n = 0, m_e = 0, m_i = 0, n_p = 0;
     BatchSensitivities outputs(size_t columns) const {
       BatchSensitivities out;
-      out.dx.resize(B * columns * n);
-      out.ds.resize(B * columns * m_i);
-      out.dy.resize(B * columns * m_e);
-      out.dz.resize(B * columns * m_i);
+      size_blocks(sys->structure(), B * columns, out.dx, out.ds, out.dy, out.dz);
+      out.status.resize(B);
+      out.info.resize(B);
+      return out;
+    }
+    BatchSensitivities gradients() const {
+      BatchSensitivities out;
+      out.grad.resize(B * n_p);
       out.status.resize(B);
       out.info.resize(B);
       return out;
     }
   };
+  // the four blocks of a result with `rows` rows: [rows][n], [rows][m_i], [rows][m_e], [rows][m_i]
+  static void size_blocks(const slpx::NlpStructure& st, size_t rows, std::vector<double>& dx, std::vector<double>& ds, std::vector<double>& dy,
+                          std::vector<double>& dz) {
+    dx.resize(rows * st.n);
+    ds.resize(rows * st.m_i);
+    dy.resize(rows * st.m_e);
+    dz.resize(rows * st.m_i);
+  }
+  // The cotangents of a call, `rows` rows per block (1: one problem), as the drivers take them: an empty span is absent,
+  // at least one must be given, and one of the wrong size throws `who` + before + its name + after.
+  static slpx::SensCotangent cotangents_given(std::span<const double> x, std::span<const double> s, std::span<const double> y,
+                                              std::span<const double> z, std::span<const double> cost, size_t rows,
+                                              const slpx::NlpStructure& st, const std::string& who, const char* before, const char* after) {
+    const auto given = [&](std::span<const double> a, size_t count, const char* what) -> const double* {
+      if (a.empty()) return nullptr;
+      if (a.size() != rows * count) throw std::runtime_error(who + before + what + after);
+      return a.data();
+    };
+    slpx::SensCotangent c;
+    c.vx = given(x, st.n, "x");
+    c.vs = given(s, st.m_i, "s");
+    c.vy = given(y, st.m_e, "y");
+    c.vz = given(z, st.m_i, "z");
+    c.vcost = given(cost, 1, "the cost");
+    if (!c.vx && !c.vs && !c.vy && !c.vz && !c.vcost) throw std::runtime_error(who + ": no cotangent");
+    return c;
+  }
+  // the tail of both single-problem vjps: the gradient block, the info with the solve's status
+  std::vector<double> sensitivity_vjp_at(const slpx::Sensitivity::Point& at, const slpx::SensCotangent& c, bool x_alone, slpx::SensitivityInfo* info) {
+    std::vector<double> grad(m_iterate_parameters.size());
+    slpx::SensitivityInfo local;
+    local.solve_status = m_iterate_status;
+    if (x_alone) m_sens->vjp(at, c.vx, grad.data(), local);
+    else m_sens->vjp_full(at, c, grad.data(), local);
+    if (info) *info = local;
+    return grad;
+  }
   NodeId cost_root() const { return m_f ? m_f->expr : slpx::kNull; }
   BatchCall batch_sensitivity_call(int batch, const BatchIterate& it, std::span<const double> params, const char* who) {
     const std::string name(who);

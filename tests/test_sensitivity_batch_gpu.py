@@ -19,7 +19,8 @@ MEASURED (MI355X, profiles/sensitivity_batch.txt): the largest relative differen
 single-problem Jacobian, jvp and vjp per case — the two paths factor with different kernel families, so they agree to
 conditioning times rounding — and of test 6.  The tests assert ten times the figure, never more than CAP, and never
 less than FLOOR (1000 ulp: a figure of 0 says that both paths ran the same kernels, which the batch system of another
-size need not do).
+size need not do).  At B = 1 both paths run the same stages on systems of one instance: there test 1 asserts equal
+bits as well (profiles/sensitivity_stages.txt).
 
 Figures are printed (run with -s)."""
 from __future__ import annotations
@@ -126,6 +127,12 @@ def test_against_the_single_problem_path(m, case, B):
         assert info["solves"] >= n_p, info
     print(f"{case} B={B}: batched against single-problem, largest relative difference {worst:.3e} (bound {bound_for(case):.3e})")
     assert worst <= bound_for(case), (worst, bound_for(case))
+    if B == 1:
+        # the batch system of one instance and the problem's own system run the same stages and the same kernel families:
+        # the same bits, not only the measured bound (profiles/sensitivity_stages.txt)
+        assert bits_equal(vjp["grad"][0], ref["grad"][idx[0]]), case
+        for k in OUT:
+            assert bits_equal(jac[k][0], ref[k][idx[0]]) and bits_equal(jvp[k][0], ref["j" + k][idx[0]]), (case, k)
     # closed forms, per instance with different rows in one batch
     if case == "m2":
         assert np.max(np.abs(jac["dx"] - np.array([[1.0, 0.0]]))) <= 1e-12
