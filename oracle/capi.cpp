@@ -103,6 +103,8 @@ int orc_unary(int op, int a) {
     case Op::COSH: r = cosh(x); break;
     case Op::TANH: r = tanh(x); break;
     case Op::ERF: r = erf(x); break;
+    case Op::ISNONNEG: r = is_nonnegative(x); break;
+    case Op::ISPOS: r = is_positive(x); break;
     default: return -1;
   }
   return reg(r);

@@ -457,6 +457,8 @@ int32_t hc_tape_jit_compiles(hc_handle* h) {
   opt.compile_without_device = true;
   const TapeJitResult r = build_tape_templates(h->s.full, opt);
   if (r.compiled_without_device < 0) std::fprintf(stderr, "hc_tape_jit_compiles: %s\n", r.log.c_str());
+  // (where a device is visible the bodies are compiled FOR it and loaded: the groups are the count)
+  if (r.compiled_without_device == 0 && !r.groups.empty()) return static_cast<int32_t>(r.groups.size());
   return r.compiled_without_device;
 }
 

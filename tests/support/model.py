@@ -321,6 +321,8 @@ class NlpProblem:
         self.stats = None
         if isinstance(self.be, OracleBackend):
             self.p = _oracle.OracleProblem.new()
+        elif hasattr(self.be, "new_problem"):  # a backend that keeps its problems itself (tests/support/mpref.py)
+            self.p = self.be.new_problem()
         else:
             self.p = self.be.sa.Problem()
 
@@ -340,6 +342,8 @@ class NlpProblem:
     def _call(self, name, node):
         if isinstance(self.be, OracleBackend):
             getattr(self.be.L, "orc_problem_" + name)(self.p.pid, node)
+        elif hasattr(self.be, "new_problem"):
+            getattr(self.p, name)(node)
         else:
             getattr(self.be.L, "slpx_problem_" + name)(self.p._h, node)
 

@@ -110,6 +110,31 @@ def assert_forward_error(errs, solve_correction, lcp, lri, Kreg, rhs, p, p_true,
     assert errs["p1_vs_true"] <= max(tol_step, 10.0 * errs["po_vs_true"], errs["p_vs_true"]), (label, errs)
 
 
+def unpack_sweep(backend, V):
+    """The sweep's V as the oracle's objects: f, c_e, c_i as arrays; g as {(column, 0): the column's sum over its
+    entries of pattern 0}; A_e, A_i as {(row, column): value} (patterns 1, 2); H = d_f H_f + H_c as {(row, column): value},
+    lower triangle (patterns 3 and 4 added).  backend: HostCheck, GpuBackend or a sleipnir_amd.System (info, pattern)."""
+    I = backend.info
+    n, me, mi = I["n"], I["m_e"], I["m_i"]
+    out = {"f": V[0:1], "c_e": V[1:1 + me], "c_i": V[1 + me:1 + me + mi]}
+    cp, ri = backend.pattern(0)
+    g = np.zeros(n)
+    for c in range(n):
+        for p in range(cp[c], cp[c + 1]):
+            g[c] += V[I["off_g"] + p]
+    out["g"] = {(c, 0): g[c] for c in range(n)}
+    for name, which, off in (("A_e", 1, "off_Ae"), ("A_i", 2, "off_Ai")):
+        cp, ri = backend.pattern(which)
+        out[name] = cases.csc_to_dict(cp, ri, V[I[off]:I[off] + len(ri)])
+    hcp, hri = backend.pattern(3)
+    ccp, cri = backend.pattern(4)
+    H = cases.csc_to_dict(hcp, hri, V[I["off_Hf"]:I["off_Hf"] + len(hri)])
+    for k, v in cases.csc_to_dict(ccp, cri, V[I["off_Hc"]:I["off_Hc"] + len(cri)]).items():
+        H[k] = H.get(k, 0.0) + v
+    out["H"] = H
+    return out
+
+
 def check_newton_step(backend, op, case, tol_ad=1e-11, tol_kkt=1e-10, tol_resid=1e-10, tol_step=1e-8,
                       verbose=False):
     """Runs the step on `backend` and on the oracle `op` (same permutation) and asserts
@@ -128,11 +153,8 @@ def check_newton_step(backend, op, case, tol_ad=1e-11, tol_kkt=1e-10, tol_resid=
     errs["f"] = abs(V[0] - op.f()) / max(1.0, abs(op.f()))
     errs["c_e"] = cases.max_rel(V[1:1 + me], op.vec("c_e"))
     errs["c_i"] = cases.max_rel(V[1 + me:1 + me + mi], op.vec("c_i"))
-    cp, ri = backend.pattern(0)
-    g = np.zeros(n)
-    for c in range(n):
-        for p in range(cp[c], cp[c + 1]):
-            g[c] += V[I["off_g"] + p]
+    mine = unpack_sweep(backend, V)
+    g = np.array([mine["g"][(c, 0)] for c in range(n)])
     errs["g"] = cases.max_rel(g, op.vec("g"))
     for name, which, off in (("A_e", 1, "off_Ae"), ("A_i", 2, "off_Ai")):
         cp, ri = backend.pattern(which)
@@ -140,11 +162,7 @@ def check_newton_step(backend, op, case, tol_ad=1e-11, tol_kkt=1e-10, tol_resid=
         assert np.array_equal(cp, ocp) and np.array_equal(ri, ori), f"{name} pattern differs"
         errs[name] = cases.max_rel(V[I[off]:I[off] + len(ri)], ov)
     # H = d_f H_f + H_c: compare through the oracle's H (lower)
-    hcp, hri = backend.pattern(3)
-    ccp, cri = backend.pattern(4)
-    H = cases.csc_to_dict(hcp, hri, V[I["off_Hf"]:I["off_Hf"] + len(hri)])
-    for k, v in cases.csc_to_dict(ccp, cri, V[I["off_Hc"]:I["off_Hc"] + len(cri)]).items():
-        H[k] = H.get(k, 0.0) + v
+    H = mine["H"]
     ocp, ori, ov = op.csc("H")
     Ho = cases.csc_to_dict(ocp, ori, ov)
     assert set(Ho.keys()) == set(H.keys()), "H pattern differs"

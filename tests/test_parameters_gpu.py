@@ -9,7 +9,7 @@ Models: tests/support/param_models.py (M2: Newton, Mq: SQP, chain(8): interior p
 chain(4): interpreted tasks only).  Task classes exercised: the generated bodies, the interpreted 64-thread tasks riding
 in their launch (chain(8)), tape_sweep_lds_kernel<64> on its own (chain(4); chain(8) under SLPX_TAPE_JIT=0 and
 SLPX_TAPE_TEMPLATES=0).  The 256-thread and the global-memory classes take the same one-line change and are not
-reached at these sizes."""
+reached at these sizes; tests/test_tape_sweep_gpu.py::test_parameter_pool_per_instance reaches them."""
 import numpy as np
 import pytest
 
