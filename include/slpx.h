@@ -573,7 +573,9 @@ int slpx_newton_steps(slpx_system* s, int32_t count, int refresh_ad, int forget_
 int slpx_system_regularization(slpx_system* s, double* reg);
 
 /* Device -> host copies.  which: 0 V, 1 lhs, 2 rhs, 3 p, 4 p_s, 5 p_z, 6 D (pivot order), 7 L values,
- * 8 x, 9 s, 10 y, 11 z (the resident iterate) */
+ * 8 x, 9 s, 10 y, 11 z (the resident iterate); for tests of the factorization kernels, per problem: 12 z = D^-1 L^-1 P rhs
+ * of the right-hand side that rode in the last factorization (pivot order), 13 the update blocks its rounds handed
+ * each other */
 int64_t slpx_system_get(slpx_system* s, int which, double* out);
 int slpx_system_set_rhs(slpx_system* s, const double* rhs);
 /* RegularizedLDLT::compute(lhs) with a caller-assembled matrix (regularized_ldlt.hpp:72):

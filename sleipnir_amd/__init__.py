@@ -962,7 +962,7 @@ class System:
 
     def get(self, which: str) -> np.ndarray:
         sel = {"V": 0, "lhs": 1, "rhs": 2, "p": 3, "p_s": 4, "p_z": 5, "D": 6, "Lx": 7, "x": 8, "s": 9,
-               "y": 10, "z": 11}[which]
+               "y": 10, "z": 11, "zv": 12, "update_blocks": 13}[which]
         count = _check(lib().slpx_system_get(self._h, sel, None))
         out = np.zeros(max(count, 1))
         _check(lib().slpx_system_get(self._h, sel, out.ctypes.data))

@@ -991,6 +991,13 @@ int64_t slpx_system_get(slpx_system* s, int which, double* out) {
       case 9: src = dev.d_s(); count = B * st.m_i; break;
       case 10: src = dev.d_y(); count = B * st.m_e; break;
       case 11: src = dev.d_z(); count = B * st.m_i; break;
+      case 12:
+      case 13: {  // what a factorization leaves besides L and D, batch-major (DeviceNlp::download_factor_scratch)
+        std::vector<double> scratch;
+        count = B * static_cast<int64_t>(dev.download_factor_scratch(which - 12, scratch));
+        if (out) std::copy(scratch.begin(), scratch.end(), out);
+        return;
+      }
       default: throw std::runtime_error("slpx_system_get: bad selector");
     }
     if (out && count > 0) dev.download(src, out, static_cast<size_t>(count));

@@ -707,6 +707,10 @@ class DeviceNlp {
   double* d_pz() { return m_pz.p; }
   double* d_D() { return m_D.p; }
   double* d_Lx() { return m_Lx.p; }
+  // For tests of the masked launches (slpx_system_get 12 / 13): what the factorization leaves besides L and D —
+  // which 0: z = D⁻¹L⁻¹Pb of the right-hand side that rode in it, [batch][n]; 1: the update blocks handed from round
+  // to round, [batch][n_contrib] — batch-major whichever kernels wrote them.  Returns the count per problem.
+  size_t download_factor_scratch(int which, std::vector<double>& out);
   int in_stride() const { return m_s_ref.n_inputs(); }
   int v_stride() const { return m_s_ref.nV; }
 

@@ -1955,6 +1955,24 @@ void DeviceNlp::materialize_factor() {
   m_il_outputs_stale = false;
 }
 
+size_t DeviceNlp::download_factor_scratch(int which, std::vector<double>& out) {
+  const LdltPlan& l = m_l_ref;
+  const size_t B = static_cast<size_t>(m_batch);
+  const size_t count = which == 0 ? static_cast<size_t>(l.n) : std::max<uint32_t>(1, l.n_contrib);
+  out.assign(B * count, 0.0);
+  if (!m_il) {
+    download(which == 0 ? m_zv.p : m_contrib.p, out.data(), B * count);
+    return count;
+  }
+  // [group of kIlW problems][index][problem of the group] -> [problem][index]
+  const DevBuf<double>& src = which == 0 ? m_zv_il : m_contrib_il;
+  std::vector<double> raw(src.n);
+  download(src.p, raw.data(), raw.size());
+  for (size_t b = 0; b < B; ++b)
+    for (size_t i = 0; i < count; ++i) out[b * count + i] = raw[((b / kIlW) * count + i) * kIlW + b % kIlW];
+  return count;
+}
+
 // Lane-per-problem pays from one 64-problem chunk per task on (r02: from ~200 problems — the backward
 // solve was one wave per task and chunk, a chain of columns; with the columns of a level dealt to four
 // waves, 64 x N=500: 251 k steps/s against 224-238 k for the per-task kernels,
