@@ -37,6 +37,10 @@ def cases():
     for N in (500, 1000):
         for entries in (1024, 512, 384):
             out.append((f"cart_pole{N}/columns/task_entries_{entries}", "cart_pole", N, {"SLPX_HOSTCHECK_COLUMN_PLAN": str(entries)}, []))
+    # ... and what the product's own rules give a batch (choose_ldlt_options): 64 is the 512-entry column plan above, 512
+    # the 384-entry one (tests/test_system_choice_cpu.py asserts both)
+    for batch in (1, 16, 64, 512):
+        out.append((f"cart_pole500/product/batch_{batch}", "cart_pole", 500, {}, ["--product-batch", str(batch)]))
     out.append(("cart_pole24/task_entries_64", "cart_pole", 24, {}, ["--task-entries", "64", "--small-lds", str(24 * 1024)]))
     for kind, N in (("cart_pole", 37), ("flywheel", 50)):
         for var, values in (("SLPX_SN_MIN_WIDTH", (2, 3)), ("SLPX_SN_DEEPEST", (0, 1, 2)), ("SLPX_RELAX_ZEROS", (0, 4, 32)),
@@ -69,7 +73,7 @@ def cases():
     return out
 
 
-KNOBS = ("SLPX_LDLT_MF", "SLPX_HOSTCHECK_SINGLE_PROBLEM_RULES", "SLPX_HOSTCHECK_COLUMN_PLAN", "SLPX_HOSTCHECK_SN_MAX_WIDTH",
+KNOBS = ("SLPX_LDLT_MF", "SLPX_HOSTCHECK_PRODUCT_BATCH", "SLPX_HOSTCHECK_SINGLE_PROBLEM_RULES", "SLPX_HOSTCHECK_COLUMN_PLAN", "SLPX_HOSTCHECK_SN_MAX_WIDTH",
          "SLPX_MFMA_MIN_ENTRIES", "SLPX_SN_MIN_WIDTH", "SLPX_SN_MAX_WIDTH", "SLPX_SN_BALANCE", "SLPX_SN_DEEPEST", "SLPX_RELAX_ZEROS",
          "SLPX_SUPERNODAL", "SLPX_DENSE", "SLPX_SETUP_THREADS", "SLPX_TASK_ENTRIES", "SLPX_LDLT_VERBOSE", "SLPX_SETUP_TIMING")
 
@@ -97,13 +101,16 @@ def compare(path_a, path_b):
     print("\nbranch:")
     print("\n".join(b))
     rows_a, rows_b = ({r["case"]: r for r in map(json.loads, lines)} for lines in (a, b))
-    different = sorted(k for k in set(rows_a) | set(rows_b) if rows_a.get(k) != rows_b.get(k))
+    different = sorted(k for k in rows_a if rows_a[k] != rows_b.get(k))
+    added = sorted(k for k in rows_b if k not in rows_a)
     failed = sorted(k for k, r in rows_a.items() if "error" in r)
     print()
     for k in different:
         print(f"DIFFERENT: {k}")
     for k in failed:
         print(f"NOT BUILT AT THE PARENT: {k}")
+    for k in added:
+        print(f"NEW IN THE BRANCH: {k}")
     print(f"{len(rows_a)} rows compared")
     print("identical" if not different else f"{len(different)} DIFFERENT")
     return 1 if different else 0

@@ -25,6 +25,7 @@
 #include "kkt_plan.hpp"
 #include "ldlt_symbolic.hpp"
 #include "nlp.hpp"
+#include "system_choice.hpp"
 
 namespace slpx {
 
@@ -442,7 +443,7 @@ inline void spin_on_published(Done done, hipStream_t stream, const char* what) {
 
 class DeviceNlp {
  public:
-  DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l, int batch, int device);
+  DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l, int batch, int device, const Switches& sw);
   ~DeviceNlp();
 
   int batch() const { return m_batch; }
@@ -508,9 +509,9 @@ class DeviceNlp {
   void read_stats(std::vector<LdltStats>& out);     // synchronizes
   void solve();                                     // rhs -> p (dim per batch item)
   void solve_after_factor();                        // p for the rhs that was in place at factor()
-  bool step_is_one_launch() const { return m_fuse_solve && m_fuse_kkt; }
-  bool step_is_multifrontal() const { return m_mf; }
-  bool factorization_is_dense() const { return m_dense; }
+  bool step_is_one_launch() const { return m_mode.fuse_solve && m_mode.fuse_kkt; }
+  bool step_is_multifrontal() const { return m_mode.mf; }
+  bool factorization_is_dense() const { return m_mode.dense; }
   void solve_backsub_publish();                     // solve_after_factor() + backsub_publish(), one launch where possible
   // factor() + solve_backsub_publish(): ONE launch where every task's workgroup fits on the device at once
   void factor_solve_publish(const std::vector<double>& delta, const std::vector<double>& gamma,
@@ -560,7 +561,6 @@ class DeviceNlp {
   void backsub_and_publish(const LdltStats* stats_src);
   void backsub_publish();
   void materialize_factor();                // batch-interleaved mode: refresh the batch-major L, D copies
-  static bool interleaved_for(int batch);   // batches this large factor with one lane per problem
   // Twin attempt (ldlt_mf_twin_kernel): the policy loop's attempt (delta0, gamma0) and the one it would make
   // next (delta1, gamma1) in ONE launch; `mode` as IpmTwin::mode.  false: not possible now (the caller makes a
   // single attempt).  read_stats() then has the first attempt's counters, read_twin_stats() the second's;
@@ -725,15 +725,14 @@ class DeviceNlp {
                  const std::vector<uint8_t>& active);
   void enqueue_factor(int parity, hipStream_t stream);
   // the constructor's phases, in its order (kernels.hip)
-  void choose_chain_mode();
+  void choose_initial_modes();
   void upload_tapes();
   void raise_lds_limits();
   void upload_kkt_plan();
   void upload_ldlt_plan();
-  void choose_launch_modes();
   void upload_inline_kkt(const struct InlineKkt& ik);
   void upload_inline_backsub(const struct InlineBacksub& ib);
-  void upload_mf(const struct MfImages& im);  // the multifrontal step where every task is resident at once; sets m_mf
+  void upload_mf(const struct MfImages& im);  // the multifrontal step where every task is resident at once
   void alloc_dense_buffers();
   void alloc_value_buffers();
   void arm_handover_buffers();
@@ -746,6 +745,13 @@ class DeviceNlp {
   const LdltPlan& m_l_ref;
   int m_batch;
   int m_device;
+  // Which kernels serve this system: written by the stages of system_choice.hpp only, from what this class measures
+  const Switches m_sw;
+  LaunchModes m_mode;
+  PlanFacts m_plan;  // what those stages read of m_l_ref
+  int m_cus = 0;  // compute units of the device
+  // workgroups of (kernel, threads, dynamic LDS) one CU holds at once; static_lds: the larger of what is there and the kernel's
+  int workgroups_per_cu(const void* kernel, int threads, size_t lds, size_t* static_lds = nullptr);
   TrackedStream m_stream;
 
   TapeDevice m_full, m_values;
@@ -757,7 +763,6 @@ class DeviceNlp {
   LdltDev m_ldev{};
   DevBuf<int32_t> m_lhs_colptr, m_lhs_rowidx, m_lhs_rowptr, m_lhs_rowent, m_lhs_rowcol;  // refine_solution (uploaded on first use)
   // the dense branch (LdltPlan::dense, ldlt_dense_kernels.h): the factors of every problem as a dim x dim matrix
-  bool m_dense = false, m_dense_pivoted = false;
   DevBuf<int32_t> m_dense_trans;  // the transpositions of the pivoted factorization (LdltPlan::dense_pivoted)
   DevBuf<double> m_dense_A;
   DevBuf<int32_t> m_dense_colptr, m_dense_rowidx;
@@ -803,35 +808,25 @@ class DeviceNlp {
   DevBuf<unsigned long long> m_seq_dev;
   unsigned long long m_seq_expected = 0;  // publishing launches enqueued so far
   unsigned long long m_stats_seq = 0;     // the one that carries the current inertia counters
-  bool m_fuse_kkt_store = false;
-  bool m_fuse_kkt = false, m_fuse_backsub = false;  // the two halves of it (SLPX_FUSE_KKT, SLPX_FUSE_BACKSUB)
-  bool m_fuse_launches = false;       // KKT assembly inside the factorization launch, back-substitution inside the solve's
   bool m_defer_kkt = false;           // build_kkt() only notes the request ...
   int m_kkt_pending = 0;              // ... for enqueue_factor (1: lhs + rhs, 2: + the tape's sums)
-  bool m_fuse_solve = false;          // factorization and solve of a step in one launch (ldlt_mf_step_kernel)
   // backward solve: x of finished columns handed to the descendants through the values (two
   // buffers, the solves alternate)
-  bool m_xg_by_data = false;
   int m_xg_parity = 0;
   DevBuf<double> m_xg2;
-  double* xg_now() { return (m_xg_by_data && m_xg_parity) ? m_xg2.p : m_xg.p; }
+  double* xg_now() { return (m_mode.xg_by_data && m_xg_parity) ? m_xg2.p : m_xg.p; }
   double* xg_other() {
-    if (!m_xg_by_data) return nullptr;
+    if (!m_mode.xg_by_data) return nullptr;
     return m_xg_parity ? m_xg.p : m_xg2.p;
   }
   void xg_flip() {
-    if (m_xg_by_data) m_xg_parity ^= 1;
+    if (m_mode.xg_by_data) m_xg_parity ^= 1;
   }
   DevBuf<unsigned int> m_exit_cnt;
   void enqueue_factor_solve(int parity);
   KktFuse take_kkt_fuse();
   BacksubFuse backsub_fuse(const LdltStats* publish);
   // multifrontal step (ldlt_mf_kernels.h: ldlt_mf_step_kernel; SLPX_LDLT_MF=0: the pair lists)
-  bool m_mf = false;
-  bool m_mf_solve = false;  // a new right-hand side goes through the fronts too (ldlt_mf_solve_kernel; SLPX_MF_SOLVE=0: the pair lists)
-  bool m_mf_mfma = false;             // the plan has fronts on the matrix cores: the kernel variant with that path
-  int m_mf_threads = 1024;            // 512 where the 1024-thread workgroups of every task are not resident at once
-  int m_twin_threads = 1024;          // ... of a launch of two attempts (twin_available)
   uint32_t m_mf_lds = 0;
   DevBuf<LdltMfTask> m_mf_tasks;
   DevBuf<LdltFront> m_mf_fronts;
@@ -846,7 +841,6 @@ class DeviceNlp {
                       const double* rhs2 = nullptr);
   void book_mf_step(int twin_mode, bool chained);
   IpmLookaheadArgs lookahead_args(double tau, int twin_mode);
-  int m_twin_state = 0;  // 0: not looked at yet, 1: available, -1: not (not resident at once, SLPX_TWIN=0, ...)
   int m_twin_mode = 0;   // of the step launch in flight (IpmTwin::mode; 0: a single attempt)
   DevBuf<double> m_Lx_tw, m_D_tw, m_zv_tw, m_p_tw, m_ps_tw, m_pz_tw, m_mf_contrib_tw, m_xg_tw, m_xg2_tw;
   DevBuf<LdltStats> m_stats_tw;
@@ -861,11 +855,8 @@ class DeviceNlp {
   uint32_t m_factor_lds_inline = 0;   // dynamic LDS of the factorization with the terms staged
   bool m_lhs_stale = false, m_rhs_stale = false;  // memory does not hold the system of the current state
   void solve_after_factor_impl(const LdltStats* publish);
-  // all rounds of a factorization / backward solve in one launch (device-side round
-  // counters, double-buffered like the inertia counters); SLPX_SINGLE_LAUNCH=0 disables
-  bool m_single_launch = true;
   // batch-interleaved LDLT (ldlt_il_kernels.h)
-  bool m_il = false, m_il_outputs_stale = false;
+  bool m_il_outputs_stale = false;
   // the assembly kernels write the interleaved lhs / rhs themselves; *_in_il: the current system is in the
   // interleaved arrays only (a caller that wrote its own batch-major system: il_gather_kernel transposes it)
   bool m_lhs_in_il = false, m_rhs_in_il = false;
@@ -873,7 +864,6 @@ class DeviceNlp {
   DevBuf<LdltStats> m_stats_part;  // [task][problem]
   DevBuf<uint32_t> m_il_meta, m_il_meta_off;  // per task: the plan slices the factor kernel stages
   uint32_t m_il_factor_lds = 0, m_il_solve_lds = 0;
-  bool m_slot_handoff = false;        // factorization rounds hand over through the update block slots
   DevBuf<unsigned int> m_fround_cnt, m_bround_cnt;  // [2][batch][n_rounds]
   std::vector<double> m_V_static;  // scaled static values (host copy)
   // interior-point iteration state (ipm_enable)
@@ -892,14 +882,11 @@ class DeviceNlp {
   int m_ride_slot = 0;
   double m_ride_ticket = 1.0;       // of the last riding launch (2, 3, ...: never a plain launch's 0 / 1 in IpmHost::go)
   DevBuf<double> m_ipm_ride_verdict;
-  int m_ride_lds_ok = -1;           // the riding kernels' dynamic LDS was raised / fits (-1: not asked yet)
   bool m_errors_decide = false;
   bool m_tape_reduce = true;       // launch_tape runs the separable-sum reductions itself
   // chained steps (sweep_full_for_step): words 0 / 16 / 32 / 48 of m_chain = workgroups of the sweep
   // through, last step whose sweep is complete, workgroups of the step kernel through, last step whose
   // kernel is complete
-  bool m_chain_on = false;
-  int m_chain_mode = 0;               // TapeJitOptions::chain_mode the full tape's kernel was generated with
   bool m_last_step_chained = false;   // the last multifrontal step kernel launched signals its end through the chain words
   hipStream_t m_tape_stream = nullptr;
   hipEvent_t m_chain_ev = nullptr;

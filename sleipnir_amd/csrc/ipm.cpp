@@ -409,8 +409,7 @@ ExitStatus ipm_core_resident(NewtonSystem& sys, const Vec& scales,
   int full_step_rejected_counter = 0;
   LineSearch ls;
   const bool identity = scaling_is_identity(st, scales);
-  const char* lookahead_env = std::getenv("SLPX_IPM_LOOKAHEAD");
-  const bool lookahead = lookahead_env == nullptr || lookahead_env[0] != '0';
+  const bool lookahead = sys.switches().ipm_lookahead;
   double E_0 = ipm_E_0(cur, m_e, m_i, identity);  // :361-362
   rep.t_setup = since(t_setup);
 
@@ -425,8 +424,7 @@ ExitStatus ipm_core_resident(NewtonSystem& sys, const Vec& scales,
   // the tasks: the deciding launch in front of the step, which reads the word it leaves and passes if told to.)
   // The host then only follows: one poll per iteration, no launch on the critical path.
   // SLPX_IPM_PIPELINE=0: every iteration decided by the host, as before.
-  const char* pipeline_env = std::getenv("SLPX_IPM_PIPELINE");
-  const bool pipeline_on = lookahead && callbacks.empty() && !options.feasible_ipm && !(pipeline_env && pipeline_env[0] == '0');
+  const bool pipeline_on = lookahead && callbacks.empty() && !options.feasible_ipm && sys.switches().ipm_pipeline;
   const bool ride_on = pipeline_on && dev.ipm_ride_possible();  // (SLPX_IPM_RIDE=0: the error launch in front of the gated step)
   bool ctl_current = false;      // the device's copy of (filter, current iterate's entry, mu) is the host's
   bool filter_on_device = false; // ... and newer than the host's: the device took decisions since
@@ -720,9 +718,7 @@ ExitStatus ipm_core_resident(NewtonSystem& sys, const Vec& scales,
 ExitStatus ipm_core(NewtonSystem& sys, const Vec& scales, const std::vector<IterationCallback>& callbacks,
                     const Options& options, bool in_feasibility_restoration, Vec& x, Vec& s, Vec& y, Vec& z,
                     double& mu, int& iterations, SolveReport& rep, clk::time_point solve_start) {
-  const char* env = std::getenv("SLPX_IPM_RESIDENT");
-  const bool resident = !(env && env[0] == '0');
-  return (resident ? ipm_core_resident : ipm_core_host)(sys, scales, callbacks, options,
+  return (sys.switches().ipm_resident ? ipm_core_resident : ipm_core_host)(sys, scales, callbacks, options,
                                                         in_feasibility_restoration, x, s, y, z, mu, iterations,
                                                         rep, solve_start);
 }

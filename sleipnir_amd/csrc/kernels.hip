@@ -595,8 +595,8 @@ LdltDev LdltPlanDevice::view() const {
 // The phases below run in this order; every upload() of theirs goes into the system's arena — a few allocations, one
 // copy each (commit at the end) — so their order is also the order of the plan arrays in memory.
 DeviceNlp::DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l, int batch,
-                     int device)
-    : m_s_ref(s), m_k_ref(k), m_l_ref(l), m_batch(batch), m_device(device) {
+                     int device, const Switches& sw)
+    : m_s_ref(s), m_k_ref(k), m_l_ref(l), m_batch(batch), m_device(device), m_sw(sw) {
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
     throw std::runtime_error("slpx: no HIP device available (the product path has no CPU fallback)");
@@ -607,7 +607,7 @@ DeviceNlp::DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l,
   } arena_guard;
   DeviceArena::current() = &m_arena;
 
-  choose_chain_mode();
+  choose_initial_modes();
   upload_tapes();
   lap("  upload: tapes (+ code objects)");
   raise_lds_limits();
@@ -615,22 +615,19 @@ DeviceNlp::DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l,
   lap("  upload: kernel attributes, KKT plan");
   upload_ldlt_plan();
   lap("  upload: LDLT plan");
-  choose_launch_modes();
   // (the host copies of the inline plans live until the task images are packed from them)
-  const InlineKkt inline_kkt = m_fuse_kkt ? build_inline_kkt(s, k, l) : InlineKkt{};
-  if (m_fuse_kkt) upload_inline_kkt(inline_kkt);
+  const InlineKkt inline_kkt = m_mode.fuse_kkt ? build_inline_kkt(s, k, l) : InlineKkt{};
+  if (m_mode.fuse_kkt) upload_inline_kkt(inline_kkt);
   lap("    images: inline KKT terms");
-  const InlineBacksub inline_backsub = m_fuse_backsub ? build_inline_backsub(k, l) : InlineBacksub{};
-  if (m_fuse_backsub) upload_inline_backsub(inline_backsub);
+  const InlineBacksub inline_backsub = m_mode.fuse_backsub ? build_inline_backsub(k, l) : InlineBacksub{};
+  if (m_mode.fuse_backsub) upload_inline_backsub(inline_backsub);
   lap("    images: back-substitution rows");
-  // (one problem's factorization and solve in one launch: the multifrontal step; the pair-list kernels — batches,
-  // plans without fronts — take a launch per round and phase.  SLPX_LDLT_MF=0: the pair lists)
-  const char* mf_env = std::getenv("SLPX_LDLT_MF");
-  if (m_fuse_launches && m_fuse_backsub && m_fuse_kkt && l.mf && !(mf_env && mf_env[0] == '0'))
-    upload_mf(build_mf_images(l, inline_kkt, inline_backsub));
+  note_inline_images(m_mode, inline_kkt.ok, inline_backsub.ok);
+  MfImages mf_images;
+  mf_images.declined = "not asked for";
+  if (wants_multifrontal(m_mode, m_plan, m_sw)) mf_images = build_mf_images(l, inline_kkt, inline_backsub);
+  upload_mf(mf_images);
   lap("    images: multifrontal task images");
-  m_fuse_solve = m_mf;
-  m_chain_on = m_mf && m_chain_mode != 0;
   lap("  upload: inline KKT / back-substitution / multifrontal images");
   alloc_dense_buffers();  // (before the armed buffers, whose uploads follow its pattern arrays in the arena)
   alloc_value_buffers();
@@ -644,22 +641,30 @@ DeviceNlp::DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l,
   lap("  upload: scaling, static V");
 }
 
-// Chained steps (sweep_full_for_step): for one problem whose multifrontal step kernel leaves the sweep
-// room on the chip (at most CUs - 64 workgroups: cart-pole N=5000's 265 do not, and there chaining costs
-// 25 %, profiles/r03_chain_ab.txt).  SLPX_CHAIN_TAPE=0: off.  (Before the tapes: their kernel is generated for it.)
-void DeviceNlp::choose_chain_mode() {
-  const NlpStructure& s = m_s_ref;
+// What system_choice.hpp reads of the plan, and the stage of it that needs nothing measured but the device's size.
+// (Before the tapes: their kernel is generated for the chain mode.)
+void DeviceNlp::choose_initial_modes() {
   const LdltPlan& l = m_l_ref;
-  int cus = 0;
-  SLPX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m_device));
-  if (m_batch == 1 && l.mf && static_cast<int>(l.tasks.size() + s.reduces.size()) + 64 <= cus) m_chain_mode = 1;
-  if (const char* env = std::getenv("SLPX_CHAIN_TAPE"))
-    if (env[0] == '0') m_chain_mode = 0;
+  m_plan = PlanFacts{l.dense, l.dense_pivoted, l.tasks.size(), l.factor_lds_bytes, l.mf, l.mf_n_mfma, update_slots_have_one_reader(l)};
+  SLPX_HIP_CHECK(hipDeviceGetAttribute(&m_cus, hipDeviceAttributeMultiprocessorCount, m_device));
+  m_mode = initial_launch_modes(m_batch, m_plan, m_s_ref.reduces.size(), m_cus, m_sw);
+}
+
+int DeviceNlp::workgroups_per_cu(const void* kernel, int threads, size_t lds, size_t* static_lds) {
+  int per_cu = 0;
+  SLPX_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  if (static_lds != nullptr) {
+    hipFuncAttributes attr{};
+    SLPX_HIP_CHECK(hipFuncGetAttributes(&attr, kernel));
+    *static_lds = std::max(*static_lds, attr.sharedSizeBytes);
+  }
+  SLPX_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds));
+  return per_cu;
 }
 
 void DeviceNlp::upload_tapes() {
   const NlpStructure& s = m_s_ref;
-  m_full.upload(s.full, m_batch, static_cast<uint32_t>(s.n), m_chain_mode);
+  m_full.upload(s.full, m_batch, static_cast<uint32_t>(s.n), m_mode.chain_mode);
   m_values.upload(s.values, m_batch, static_cast<uint32_t>(s.n));
   m_reduces.upload(s.reduces);
 }
@@ -691,37 +696,9 @@ void DeviceNlp::upload_ldlt_plan() {
   m_bround_cnt.upload(zero);
 }
 
-// Which kernels serve this system: from the plans' shape and the batch, and the switches that overrule it.
-void DeviceNlp::choose_launch_modes() {
-  const LdltPlan& l = m_l_ref;
-  const int batch = m_batch;
-  // Rounds in one launch pay off while every task of the launch is resident at once (a
-  // single problem: 137 tasks on 256 CUs).  With a batch the later-round workgroups would
-  // spin on CUs the earlier rounds of other problems are waiting for (measured at batch
-  // 512: factorization 0.93 -> 4.2 ms), so batches keep one launch per round.
-  m_dense = l.dense;
-  m_il = !m_dense && interleaved_for(batch);
-  m_single_launch = !m_il && static_cast<size_t>(batch) * l.tasks.size() <= 1024;
-  if (const char* env = std::getenv("SLPX_SINGLE_LAUNCH")) m_single_launch = env[0] != '0';
-  // launch fusion (device.hpp: KktFuse / BacksubFuse): one problem, single-launch factorization
-  m_fuse_launches = m_single_launch && batch == 1 && l.factor_lds_bytes >= 64 * sizeof(double);
-  if (const char* env = std::getenv("SLPX_FUSE_LAUNCHES")) m_fuse_launches = m_fuse_launches && env[0] != '0';
-  m_fuse_kkt = m_fuse_backsub = m_fuse_launches;
-  if (const char* env = std::getenv("SLPX_FUSE_KKT")) m_fuse_kkt = m_fuse_kkt && env[0] != '0';
-  if (const char* env = std::getenv("SLPX_FUSE_BACKSUB")) m_fuse_backsub = m_fuse_backsub && env[0] != '0';
-  if (const char* env = std::getenv("SLPX_FUSE_KKT_STORE")) m_fuse_kkt_store = env[0] != '0';
-  // hand-overs through the data: the factorization's update slots (ldlt_kernels.h: slot_take) where each has exactly
-  // one reader, the backward solve's x (slot_read)
-  m_slot_handoff = m_single_launch && update_slots_have_one_reader(l);
-  m_xg_by_data = m_single_launch;
-}
-
 void DeviceNlp::upload_inline_kkt(const InlineKkt& ik) {
   m_factor_lds_inline = ik.factor_lds;
-  if (!ik.ok) {
-    m_fuse_kkt = false;  // (the stand-alone assembly kernels then)
-    return;
-  }
+  if (!ik.ok) return;
   m_ent_vsrc.upload(ik.vsrc);
   m_kkt_terms.upload(ik.terms);
   m_task_terms.upload(ik.task_terms);
@@ -729,17 +706,14 @@ void DeviceNlp::upload_inline_kkt(const InlineKkt& ik) {
 
 void DeviceNlp::upload_inline_backsub(const InlineBacksub& ib) {
   m_solve_lds_inline = ib.solve_lds;
-  if (!ib.ok) {
-    m_fuse_backsub = false;  // (the stand-alone back-substitution kernel then)
-    return;
-  }
+  if (!ib.ok) return;
   m_bs_plan.upload(ib.plan);
   m_bs_task_plan.upload(ib.task_plan);
 }
 
 // the dense branch: dim x dim per problem, the pattern of lhs for the scatter; LDS: column k and its scaled copy
 void DeviceNlp::alloc_dense_buffers() {
-  if (!m_dense) return;
+  if (!m_mode.dense) return;
   const KktPlan& k = m_k_ref;
   const LdltPlan& l = m_l_ref;
   const size_t B = static_cast<size_t>(m_batch);
@@ -747,8 +721,7 @@ void DeviceNlp::alloc_dense_buffers() {
   m_dense_colptr.upload(k.lhs.colptr);
   m_dense_rowidx.upload(k.lhs.rowidx);
   m_dense_lds = 16u * static_cast<uint32_t>(l.n) + 320u;
-  m_dense_pivoted = l.dense_pivoted;
-  if (m_dense_pivoted) {
+  if (m_mode.dense_pivoted) {
     m_dense_trans.alloc(B * static_cast<size_t>(l.n));
     m_dense_trans.zero();
     SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_dense_pivoted_factor_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -799,13 +772,13 @@ void DeviceNlp::arm_handover_buffers() {
   const LdltPlan& l = m_l_ref;
   const size_t B = static_cast<size_t>(m_batch);
   const double empty = std::bit_cast<double>(kSlotEmpty);
-  if (m_slot_handoff) {
+  if (m_mode.slot_handoff) {
     const std::vector<double> armed(m_contrib.n, empty);
     SLPX_HIP_CHECK(hipMemcpy(m_contrib.p, armed.data(), armed.size() * sizeof(double), hipMemcpyHostToDevice));
   }
   // the backward solve's hand-over through the data (ldlt_kernels.h: slot_read): two buffers of
   // x, both armed
-  if (m_xg_by_data) {
+  if (m_mode.xg_by_data) {
     const std::vector<double> armed(B * l.n, empty);
     m_xg.upload(armed);
     m_xg2.upload(armed);
@@ -816,7 +789,7 @@ void DeviceNlp::arm_handover_buffers() {
 
 // batch-interleaved LDLT (ldlt_il_kernels.h): [chunk of 64 problems][index][lane]
 void DeviceNlp::alloc_interleaved_buffers() {
-  if (!m_il) return;
+  if (!m_mode.il) return;
   const KktPlan& k = m_k_ref;
   const LdltPlan& l = m_l_ref;
   const size_t B = static_cast<size_t>(m_batch);
@@ -1012,7 +985,7 @@ void DeviceNlp::sweep_full_for_step() {
   // (and its workgroups are single waves: g-fold's sweep, 256-thread workgroups interpreting its packs of
   // rows, shares the chip badly with the step kernel — 13.3 k steps/s chained against 13.6 k)
   const bool one_kernel = t.n_bodies > 0 && t.n_large == 0 && t.n_global == 0 && (t.tmpl_threads == 64 || t.tmpl_wide_for_chain);
-  if (!m_chain_on || !one_kernel || !m_mf || m_batch != 1 || xg_other() == nullptr || !m_fuse_solve) {
+  if (!m_mode.chain_on || !one_kernel || !m_mode.mf || m_batch != 1 || xg_other() == nullptr || !m_mode.fuse_solve) {
     sweep_full(/*with_reduce=*/false);
     return;
   }
@@ -1041,7 +1014,7 @@ void DeviceNlp::sweep_full_for_step() {
     unsigned int verdict = 0;
     SLPX_HIP_CHECK(hipMemcpy(&verdict, m_chain.p + 97, sizeof(verdict), hipMemcpyDeviceToHost));
     if (verdict != 1u) {
-      m_chain_on = false;  // kernels run one at a time here: the sweep stays in the main stream
+      unchain(m_mode);  // kernels run one at a time here: the sweep stays in the main stream
       if (std::getenv("SLPX_LDLT_VERBOSE")) std::fprintf(stderr, "slpx: kernels of two streams do not run at once here: steps are not chained\n");
       sweep_full(/*with_reduce=*/false);
       return;
@@ -1102,7 +1075,7 @@ void DeviceNlp::recover_from_chain_failure() {
   if (m_tape_stream != nullptr) SLPX_HIP_CHECK(hipStreamSynchronize(m_tape_stream));
   SLPX_HIP_CHECK(hipStreamSynchronize(m_stream.raw()));
   if (m_chain.p != nullptr) SLPX_HIP_CHECK(hipMemset(m_chain.p, 0, 64 * sizeof(unsigned int)));
-  m_chain_on = false;
+  unchain(m_mode);
   m_chain_sweep_wgs = m_chain_step_wgs = 0;
   m_last_step_chained = false;
   m_stream.tape_pending = false;
@@ -1130,36 +1103,33 @@ constexpr int kFactorThreadsSingle = 1024;
 // The multifrontal step (ldlt_mf_kernels.h) with the task images of build_mf_images: co-residency of every task's
 // workgroup, then the uploads.
 void DeviceNlp::upload_mf(const MfImages& im) {
-  if (im.declined != nullptr) return;
   const LdltPlan& l = m_l_ref;
-  const uint32_t lds = im.lds;
-  int per_cu = 0, cus = 0;
-  hipFuncAttributes attr{};
-  bool fits = false;
-  if (lds <= 160u * 1024u) {
-    SLPX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m_device));
-    auto resident = [&](auto kernel, int threads) {
-      SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      SLPX_HIP_CHECK(hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kernel)));
-      SLPX_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds));
-      // (the tables hold LDS byte addresses from 0: no static LDS in front of the dynamic block)
-      return attr.sharedSizeBytes == 0 && l.tasks.size() + m_reduces.n <= static_cast<size_t>(per_cu) * cus;
+  MfFit fit;
+  fit.declined = im.declined != nullptr;
+  fit.lds_bytes = im.lds;
+  int per_cu[2] = {0, 0};  // at 1024, at 512 threads
+  if (!fit.declined && im.lds <= 160u * 1024u) {
+    auto fp = [](auto kernel) { return reinterpret_cast<const void*>(kernel); };
+    const bool mfma = l.mf_n_mfma > 0;
+    auto both = [&](const void* chained, const void* plain, int threads) {
+      return std::min(workgroups_per_cu(chained, threads, im.lds, &fit.static_lds_bytes), workgroups_per_cu(plain, threads, im.lds, &fit.static_lds_bytes));
     };
-    m_mf_mfma = l.mf_n_mfma > 0;
-    m_mf_threads = 1024;
-    fits = m_mf_mfma ? resident(&ldlt_mf_step_kernel<1024, true, true>, 1024) && resident(&ldlt_mf_step_kernel<1024, true, false>, 1024)
-                     : resident(&ldlt_mf_step_kernel<1024, false, true>, 1024) && resident(&ldlt_mf_step_kernel<1024, false, false>, 1024);
-    if (const char* env = std::getenv("SLPX_MF_THREADS")) fits = fits && std::atoi(env) == 1024;
-    if (!fits) {
-      m_mf_threads = 512;
-      fits = m_mf_mfma ? resident(&ldlt_mf_step_kernel<512, true, true>, 512) && resident(&ldlt_mf_step_kernel<512, true, false>, 512)
-                       : resident(&ldlt_mf_step_kernel<512, false, true>, 512) && resident(&ldlt_mf_step_kernel<512, false, false>, 512);
-    }
+    per_cu[0] = mfma ? both(fp(&ldlt_mf_step_kernel<1024, true, true>), fp(&ldlt_mf_step_kernel<1024, true, false>), 1024)
+                     : both(fp(&ldlt_mf_step_kernel<1024, false, true>), fp(&ldlt_mf_step_kernel<1024, false, false>), 1024);
+    per_cu[1] = mfma ? both(fp(&ldlt_mf_step_kernel<512, true, true>), fp(&ldlt_mf_step_kernel<512, true, false>), 512)
+                     : both(fp(&ldlt_mf_step_kernel<512, false, true>), fp(&ldlt_mf_step_kernel<512, false, false>), 512);
+    fit.step = Residency{static_cast<size_t>(per_cu[0]) * m_cus, static_cast<size_t>(per_cu[1]) * m_cus};
+    if (m_sw.mf_solve)
+      fit.solve = Residency{static_cast<size_t>(workgroups_per_cu(fp(&ldlt_mf_solve_kernel<1024>), 1024, im.lds)) * m_cus,
+                            static_cast<size_t>(workgroups_per_cu(fp(&ldlt_mf_solve_kernel<512>), 512, im.lds)) * m_cus};
   }
+  choose_multifrontal(m_mode, m_plan, m_reduces.n, fit, m_sw);
+  if (fit.declined) return;
   if (std::getenv("SLPX_LDLT_VERBOSE"))
     std::fprintf(stderr, "ldlt multifrontal step: %zu tasks, LDS %u bytes (static %zu), images %zu bytes, %d workgroup(s) of %d threads per CU x %d CUs%s\n",
-                 l.tasks.size(), lds, attr.sharedSizeBytes, 16 * im.image.size(), per_cu, m_mf_threads, cus, fits ? "" : ": NOT resident at once");
-  if (!fits) return;
+                 l.tasks.size(), im.lds, fit.static_lds_bytes, 16 * im.image.size(), per_cu[m_mode.mf_threads == 1024 ? 0 : 1], m_mode.mf_threads, m_cus,
+                 m_mode.mf ? "" : ": NOT resident at once");
+  if (!m_mode.mf) return;
   m_mf_tasks.upload(l.mf_tasks);
   m_mf_fronts.upload(l.mf_fronts);
   m_mf_image.upload(im.image);
@@ -1167,22 +1137,7 @@ void DeviceNlp::upload_mf(const MfImages& im) {
   m_mf_image_desc.upload(im.desc);
   m_mf_contrib.upload(std::vector<double>(std::max<uint32_t>(1, l.mf_n_contrib), std::bit_cast<double>(kSlotEmpty)));
   if (m_exit_cnt.n == 0) m_exit_cnt.upload(std::vector<unsigned int>(1, 0u));
-  m_mf_lds = lds;
-  m_mf = true;
-  // new right-hand sides through the fronts (one launch: every task resident, as the step kernel's)
-  {
-    const char* env = std::getenv("SLPX_MF_SOLVE");
-    m_mf_solve = env == nullptr || env[0] != '0';
-    if (m_mf_solve) {
-      const void* fn = m_mf_threads == 1024 ? reinterpret_cast<const void*>(&ldlt_mf_solve_kernel<1024>)
-                                            : reinterpret_cast<const void*>(&ldlt_mf_solve_kernel<512>);
-      SLPX_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      int per_cu_solve = 0;
-      if (m_mf_threads == 1024) SLPX_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_solve, &ldlt_mf_solve_kernel<1024>, 1024, lds));
-      else SLPX_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_solve, &ldlt_mf_solve_kernel<512>, 512, lds));
-      m_mf_solve = l.tasks.size() <= static_cast<size_t>(per_cu_solve) * cus;
-    }
-  }
+  m_mf_lds = im.lds;
 }
 
 // lhs / rhs of the CURRENT state into memory, if the last step did without them
@@ -1201,7 +1156,7 @@ void DeviceNlp::materialize_kkt() {
 // out of the interleaved arrays the assembly kernels filled; what the caller does with the pointer
 // is not known, so the next factorization transposes again
 void DeviceNlp::materialize_batch_major() {
-  if (!m_il) return;
+  if (!m_mode.il) return;
   const int C = (m_batch + 63) / 64;
   if (m_lhs_in_il) {
     const int nnz = m_kdev.nnz_lhs;
@@ -1221,7 +1176,7 @@ void DeviceNlp::materialize_batch_major() {
 void DeviceNlp::assemble() {
   m_lhs_stale = false;
   m_lhs_in_il = false;
-  if (m_il) {
+  if (m_mode.il) {
     hipLaunchKernelGGL(kkt_assemble_il_kernel, dim3(grid_for(m_kdev.nnz_lhs, 64), il_groups(m_batch)), dim3(256), 0, m_stream,
                        m_kdev, m_V.p, m_s_ref.nV, m_s.p, m_z.p, m_lhs_il.p, m_batch);
     m_lhs_in_il = true;
@@ -1241,7 +1196,7 @@ void DeviceNlp::assemble() {
 // lhs + rhs (+ the separable-sum reductions a sweep_full(false) left out) in one launch
 void DeviceNlp::build_kkt(bool with_reduce) {
   if (m_batch >= kBatchPerThread) {  // throughput regime: the batch kernels, separately
-    if (m_il) {
+    if (m_mode.il) {
       // (interleaved lhs and rhs: one launch, kkt_build_il_kernel)
       const int na = grid_for(m_kdev.nnz_lhs, 64), nr = (m_kdev.dim + 63) / 64;
       hipLaunchKernelGGL(kkt_build_il_kernel, dim3(na + nr, il_groups(m_batch)), dim3(256), 0, m_stream, m_kdev, m_V.p,
@@ -1275,7 +1230,7 @@ void DeviceNlp::build_kkt(bool with_reduce) {
 // build_kkt() when a factorization attempt is the next thing enqueued (a Newton step): the
 // assembly then rides in that launch (device.hpp: KktFuse)
 void DeviceNlp::build_kkt_for_step(bool with_reduce) {
-  m_defer_kkt = m_fuse_kkt;
+  m_defer_kkt = m_mode.fuse_kkt;
   build_kkt(with_reduce);
   m_defer_kkt = false;
 }
@@ -1375,7 +1330,7 @@ void DeviceNlp::set_parameters(const double* values, bool per_instance) {
 void DeviceNlp::build_rhs() {
   m_rhs_stale = false;
   m_rhs_in_il = false;
-  if (m_il) {
+  if (m_mode.il) {
     hipLaunchKernelGGL(kkt_rhs_il_kernel, dim3((m_kdev.dim + 63) / 64, il_groups(m_batch)), dim3(256), 0, m_stream, m_kdev,
                        m_V.p, m_s_ref.nV, m_s.p, m_y.p, m_z.p, m_mu.p, m_rhs_il.p, m_batch);
     m_rhs_in_il = true;
@@ -1424,7 +1379,7 @@ KktFuse DeviceNlp::kkt_fuse_for(int kkt_mode) const {
     f.terms = reinterpret_cast<const uint4*>(m_kkt_terms.p);
     f.task_terms = m_task_terms.p;
     f.Vw = m_V.p;
-    if (m_fuse_kkt_store) {
+    if (m_mode.fuse_kkt_store) {
       f.store_lhs = m_lhs.p;
       f.store_rhs = m_rhs.p;
     }
@@ -1436,7 +1391,7 @@ KktFuse DeviceNlp::kkt_fuse_for(int kkt_mode) const {
 KktFuse DeviceNlp::take_kkt_fuse() {
   const KktFuse f = kkt_fuse_for(m_kkt_pending);
   if (m_kkt_pending) {
-    if (m_fuse_kkt_store) m_lhs_stale = m_rhs_stale = false;
+    if (m_mode.fuse_kkt_store) m_lhs_stale = m_rhs_stale = false;
     m_kkt_pending = 0;
   }
   return f;
@@ -1481,8 +1436,8 @@ void DeviceNlp::enqueue_factor(int parity, hipStream_t stream) {
     }
     reg = m_reg_dev.p;
   }
-  if (m_dense) {
-    if (m_dense_pivoted)
+  if (m_mode.dense) {
+    if (m_mode.dense_pivoted)
       hipLaunchKernelGGL(ldlt_dense_pivoted_factor_kernel, dim3(m_batch), dim3(kDenseThreads), m_dense_lds, stream, l.n, l.n_dec,
                          m_dense_colptr.p, m_dense_rowidx.p, m_kdev.nnz_lhs, m_lhs.p, reg, m_dense_A.p, m_dense_trans.p, m_D.p, cur, next);
     else
@@ -1491,7 +1446,7 @@ void DeviceNlp::enqueue_factor(int parity, hipStream_t stream) {
     SLPX_HIP_CHECK(hipGetLastError());
     return;
   }
-  if (m_il) {
+  if (m_mode.il) {
     const int C = (m_batch + 63) / 64;
     const int nnz = m_kdev.nnz_lhs;
     // (the assembly kernels wrote the interleaved arrays themselves unless somebody else made lhs / rhs)
@@ -1510,14 +1465,14 @@ void DeviceNlp::enqueue_factor(int parity, hipStream_t stream) {
     hipLaunchKernelGGL(ldlt_stats_il_kernel, dim3(m_batch), dim3(64), 0, stream, m_stats_part.p,
                        static_cast<int>(l.tasks.size()), reg, cur, m_batch);
     m_il_outputs_stale = true;
-  } else if (m_single_launch) {
+  } else if (m_mode.single_launch) {
     KktFuse f = take_kkt_fuse();
     // every round in one launch; tasks wait on device-side round counters
     hipLaunchKernelGGL(ldlt_factor_kernel<kFactorThreadsSingle>,
                        dim3(static_cast<uint32_t>(l.tasks.size()) + static_cast<uint32_t>(f.n_blocks), m_batch),
                        dim3(kFactorThreadsSingle), f.inline_kkt ? m_factor_lds_inline : l.factor_lds_bytes, stream,
                        m_ldev, 0u, m_lhs.p, m_kdev.nnz_lhs, reg, m_Lx.p, lxs, m_D.p, l.n, m_contrib.p, cs, cur, next,
-                       m_rhs.p, m_zv.p, m_fround_cnt.p, m_slot_handoff ? 1 : 0, f);
+                       m_rhs.p, m_zv.p, m_fround_cnt.p, m_mode.slot_handoff ? 1 : 0, f);
   } else {
     for (int r = 0; r < l.n_rounds; ++r) {
       const uint32_t nt = l.round_ptr[r + 1] - l.round_ptr[r];
@@ -1541,8 +1496,8 @@ void DeviceNlp::factor(const std::vector<double>& delta, const std::vector<doubl
 
 void DeviceNlp::factor_solve_publish(const std::vector<double>& delta, const std::vector<double>& gamma,
                                      const std::vector<uint8_t>& active) {
-  const bool mf_now = m_mf && xg_other() != nullptr;
-  if (!m_fuse_solve || !mf_now) {
+  const bool mf_now = m_mode.mf && xg_other() != nullptr;
+  if (!m_mode.fuse_solve || !mf_now) {
     factor(delta, gamma, active);
     solve_backsub_publish();
     return;
@@ -1557,33 +1512,20 @@ void DeviceNlp::factor_solve_publish(const std::vector<double>& delta, const std
 
 // ---- twin attempt (ldlt_mf_twin_kernel) ----
 bool DeviceNlp::twin_available() {
-  if (m_twin_state != 0) return m_twin_state > 0 && m_mf && xg_other() != nullptr;
-  m_twin_state = -1;
-  const char* env = std::getenv("SLPX_TWIN");
-  if (env != nullptr && env[0] == '0') return false;
-  if (!m_mf || m_mf_mfma || m_batch != 1 || xg_other() == nullptr || !m_fuse_solve) return false;
+  if (m_mode.twin != 0) return m_mode.twin > 0 && m_mode.mf && xg_other() != nullptr;
   const LdltPlan& l = m_l_ref;
-  // both attempts' workgroups resident at once (their tasks wait for each other inside the launch)
-  int cus = 0, per_cu = 0;
-  SLPX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m_device));
-  auto resident = [&](auto kernel, int threads) {
-    SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    SLPX_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, m_mf_lds));
-    return 2 * l.tasks.size() + m_reduces.n <= static_cast<size_t>(per_cu) * cus;
-  };
-  // (a 1024-thread workgroup of the step kernels is alone on its CU — 98 VGPRs x 16 waves; cart-pole N=1000 has 137
-  // tasks, twice that is more than the 256 CUs.  Workgroups of 512 threads fit two to a CU and run the same image
-  // 0.5 us slower at that horizon, to the same bits: a launch of two attempts takes those where the wide ones do not fit)
-  m_twin_threads = m_mf_threads;
-  bool fits = m_mf_threads == 1024 ? resident(&ldlt_mf_twin_kernel<1024, false>, 1024) : resident(&ldlt_mf_twin_kernel<512, false>, 512);
-  if (!fits && m_mf_threads == 1024) {
-    m_twin_threads = 512;
-    fits = resident(&ldlt_mf_twin_kernel<512, false>, 512);
+  auto fp = [](auto kernel) { return reinterpret_cast<const void*>(kernel); };
+  int per_cu[2] = {0, 0};  // at 1024, at 512 threads
+  const bool measure = twin_worth_measuring(m_mode, m_batch, m_sw);
+  if (measure) {
+    if (m_mode.mf_threads == 1024) per_cu[0] = workgroups_per_cu(fp(&ldlt_mf_twin_kernel<1024, false>), 1024, m_mf_lds);
+    per_cu[1] = workgroups_per_cu(fp(&ldlt_mf_twin_kernel<512, false>), 512, m_mf_lds);
   }
-  if (std::getenv("SLPX_LDLT_VERBOSE"))
-    std::fprintf(stderr, "ldlt twin attempt: 2 x %zu tasks, %d workgroup(s) of %d threads per CU x %d CUs%s\n", l.tasks.size(), per_cu,
-                 m_twin_threads, cus, fits ? "" : ": NOT resident at once");
-  if (!fits) return false;
+  choose_twin(m_mode, m_batch, m_plan, m_reduces.n, Residency{static_cast<size_t>(per_cu[0]) * m_cus, static_cast<size_t>(per_cu[1]) * m_cus}, m_sw);
+  if (measure && std::getenv("SLPX_LDLT_VERBOSE"))
+    std::fprintf(stderr, "ldlt twin attempt: 2 x %zu tasks, %d workgroup(s) of %d threads per CU x %d CUs%s\n", l.tasks.size(),
+                 per_cu[m_mode.twin_threads == 1024 ? 0 : 1], m_mode.twin_threads, m_cus, m_mode.twin > 0 ? "" : ": NOT resident at once");
+  if (m_mode.twin < 0) return false;
   for (auto [tw, first] : {std::pair{&m_Lx_tw, &m_Lx}, {&m_D_tw, &m_D}, {&m_zv_tw, &m_zv}, {&m_p_tw, &m_p}, {&m_ps_tw, &m_ps}, {&m_pz_tw, &m_pz}}) {
     tw->alloc(std::max<size_t>(1, first->n));
     tw->zero();
@@ -1594,7 +1536,6 @@ bool DeviceNlp::twin_available() {
   m_xg2_tw.upload(armed);
   m_stats_tw.upload(std::vector<LdltStats>(2, LdltStats{0, 0, 0, 0, 0x7ff0000000000000ull}));
   SLPX_HIP_CHECK(hipDeviceSynchronize());  // (the memsets ran on the null stream)
-  m_twin_state = 1;
   return true;
 }
 
@@ -1695,10 +1636,10 @@ void DeviceNlp::launch_mf_step(int twin_mode, const double* reg, const KktFuse& 
                          m_mf_contrib.p, cur, next, m_zv.p, f, xg_now(), xg_other(), m_p.p, bf, tw, ride);
     };
     if (ride.n_blocks != 0) {
-      if (m_twin_threads == 1024) launch(&ldlt_mf_twin_kernel<1024, true>, 1024);
+      if (m_mode.twin_threads == 1024) launch(&ldlt_mf_twin_kernel<1024, true>, 1024);
       else launch(&ldlt_mf_twin_kernel<512, true>, 512);
     } else {
-      if (m_twin_threads == 1024) launch(&ldlt_mf_twin_kernel<1024, false>, 1024);
+      if (m_mode.twin_threads == 1024) launch(&ldlt_mf_twin_kernel<1024, false>, 1024);
       else launch(&ldlt_mf_twin_kernel<512, false>, 512);
     }
   } else {
@@ -1708,12 +1649,12 @@ void DeviceNlp::launch_mf_step(int twin_mode, const double* reg, const KktFuse& 
       hipLaunchKernelGGL(kernel, grid, dim3(threads), m_mf_lds, m_stream.raw(), m_ldev, md, m_lhs.p, m_rhs.p, reg_by_value, m_Lx.p, m_D.p,
                          l.n, m_mf_contrib.p, cur, next, m_zv.p, f, xg_now(), xg_other(), m_p.p, bf);
     };
-    if (m_mf_threads == 1024) {
-      if (chained) m_mf_mfma ? launch(&ldlt_mf_step_kernel<1024, true, true>, 1024) : launch(&ldlt_mf_step_kernel<1024, false, true>, 1024);
-      else m_mf_mfma ? launch(&ldlt_mf_step_kernel<1024, true, false>, 1024) : launch(&ldlt_mf_step_kernel<1024, false, false>, 1024);
+    if (m_mode.mf_threads == 1024) {
+      if (chained) m_mode.mf_mfma ? launch(&ldlt_mf_step_kernel<1024, true, true>, 1024) : launch(&ldlt_mf_step_kernel<1024, false, true>, 1024);
+      else m_mode.mf_mfma ? launch(&ldlt_mf_step_kernel<1024, true, false>, 1024) : launch(&ldlt_mf_step_kernel<1024, false, false>, 1024);
     } else {
-      if (chained) m_mf_mfma ? launch(&ldlt_mf_step_kernel<512, true, true>, 512) : launch(&ldlt_mf_step_kernel<512, false, true>, 512);
-      else m_mf_mfma ? launch(&ldlt_mf_step_kernel<512, true, false>, 512) : launch(&ldlt_mf_step_kernel<512, false, false>, 512);
+      if (chained) m_mode.mf_mfma ? launch(&ldlt_mf_step_kernel<512, true, true>, 512) : launch(&ldlt_mf_step_kernel<512, false, true>, 512);
+      else m_mode.mf_mfma ? launch(&ldlt_mf_step_kernel<512, true, false>, 512) : launch(&ldlt_mf_step_kernel<512, false, false>, 512);
     }
     if (chained) m_chain_step_wgs += md.n_workgroups;  // (what the next chained sweep waits for in chain[48])
   }
@@ -1784,7 +1725,7 @@ void DeviceNlp::adopt_twin() {
 }
 
 void DeviceNlp::enqueue_factor_solve(int parity) {
-  if (!(m_mf && xg_other() != nullptr)) throw std::logic_error("slpx: a one-launch step without the multifrontal plan");
+  if (!(m_mode.mf && xg_other() != nullptr)) throw std::logic_error("slpx: a one-launch step without the multifrontal plan");
   if (!m_kkt_pending) materialize_kkt();
   KktFuse f = take_kkt_fuse();
   const bool chained = m_stream.tape_pending;
@@ -1830,11 +1771,11 @@ void DeviceNlp::solve() {
   if (m_rhs_stale) build_rhs();
   m_solution_valid = true;
   const LdltPlan& l = m_l_ref;
-  if (m_dense) {
+  if (m_mode.dense) {
     solve_after_factor();
     return;
   }
-  if (m_mf && m_mf_solve && m_batch == 1 && xg_other() != nullptr) {
+  if (m_mode.mf && m_mode.mf_solve && m_batch == 1 && xg_other() != nullptr) {
     MfDev md;
     md.tasks = m_mf_tasks.p;
     md.fronts = m_mf_fronts.p;
@@ -1843,7 +1784,7 @@ void DeviceNlp::solve() {
     md.image_desc = m_mf_image_desc.p;
     md.n_tasks = static_cast<unsigned int>(l.tasks.size());
     const dim3 grid(static_cast<uint32_t>(l.tasks.size()));
-    if (m_mf_threads == 1024)
+    if (m_mode.mf_threads == 1024)
       hipLaunchKernelGGL(ldlt_mf_solve_kernel<1024>, grid, dim3(1024), m_mf_lds, m_stream, m_ldev, md, m_Lx.p, m_D.p, m_rhs.p,
                          m_mf_contrib.p, xg_now(), xg_other(), m_p.p);
     else
@@ -1855,7 +1796,7 @@ void DeviceNlp::solve() {
   }
   const long long lxs = static_cast<long long>(std::max<int64_t>(1, l.nnzL));
   const int scs = static_cast<int>(std::max<uint32_t>(1, l.n_scontrib));
-  if (m_il) {
+  if (m_mode.il) {
     const int C = (m_batch + 63) / 64;
     if (!m_rhs_in_il)
       hipLaunchKernelGGL(il_gather_kernel, dim3((l.n + 63) / 64, C), dim3(256), 0, m_stream, m_rhs.p,
@@ -1869,7 +1810,7 @@ void DeviceNlp::solve() {
     solve_after_factor();
     return;
   }
-  if (m_single_launch && m_batch == 1) {
+  if (m_mode.single_launch && m_batch == 1) {
     // one problem: every round in ONE launch (the tasks order themselves through the round counters)
     hipLaunchKernelGGL(ldlt_fwd_kernel, dim3(static_cast<uint32_t>(l.tasks.size()), 1), dim3(256), l.solve_lds_bytes, m_stream,
                        m_ldev, 0u, m_rhs.p, l.n, m_Lx.p, lxs, m_D.p, m_scontrib.p, scs, m_zv.p, m_fround_cnt.p);
@@ -1892,7 +1833,7 @@ void DeviceNlp::solve_after_factor() { solve_after_factor_impl(nullptr); }
 // host: one launch where the back-substitution can ride along (device.hpp: BacksubFuse)
 void DeviceNlp::solve_backsub_publish() {
   const LdltStats* src = m_stats.p + static_cast<size_t>(m_stats_cur) * m_batch;
-  if (m_fuse_backsub) {
+  if (m_mode.fuse_backsub) {
     solve_after_factor_impl(src);
     if (m_batch == 1) m_stats_seq = ++m_seq_expected;
   } else {
@@ -1906,14 +1847,14 @@ void DeviceNlp::solve_after_factor_impl(const LdltStats* publish) {
   const LdltPlan& l = m_l_ref;
   m_solution_valid = true;
   const long long lxs = static_cast<long long>(std::max<int64_t>(1, l.nnzL));
-  if (m_dense) {  // (nothing rides in a dense factorization: forward and backward substitution from the rhs in memory)
+  if (m_mode.dense) {  // (nothing rides in a dense factorization: forward and backward substitution from the rhs in memory)
     if (m_rhs_stale) build_rhs();
     hipLaunchKernelGGL(ldlt_dense_solve_kernel, dim3(m_batch), dim3(kDenseThreads), 8u * static_cast<uint32_t>(l.n) + 16u, m_stream, l.n,
-                       m_dense_A.p, m_rhs.p, m_p.p, m_dense_pivoted ? m_dense_trans.p : nullptr);
+                       m_dense_A.p, m_rhs.p, m_p.p, m_mode.dense_pivoted ? m_dense_trans.p : nullptr);
     SLPX_HIP_CHECK(hipGetLastError());
     return;
   }
-  if (m_il) {
+  if (m_mode.il) {
     const int C = (m_batch + 63) / 64;
     for (int r = l.n_rounds - 1; r >= 0; --r) {
       const uint32_t nt = l.round_ptr[r + 1] - l.round_ptr[r];
@@ -1923,7 +1864,7 @@ void DeviceNlp::solve_after_factor_impl(const LdltStats* publish) {
     SLPX_HIP_CHECK(hipGetLastError());
     return;
   }
-  if (m_single_launch) {
+  if (m_mode.single_launch) {
     const uint32_t nt = static_cast<uint32_t>(l.tasks.size());
     const BacksubFuse f = publish != nullptr ? backsub_fuse(publish) : BacksubFuse{};
     hipLaunchKernelGGL(ldlt_bwd_kernel, dim3(nt, m_batch), dim3(256), f.on ? m_solve_lds_inline : l.solve_lds_bytes,
@@ -1943,7 +1884,7 @@ void DeviceNlp::solve_after_factor_impl(const LdltStats* publish) {
 // Batch-interleaved mode keeps L and D as [chunk][index][lane]; the batch-major copies that
 // slpx_system_get hands out are made on demand.
 void DeviceNlp::materialize_factor() {
-  if (!m_il || !m_il_outputs_stale) return;
+  if (!m_mode.il || !m_il_outputs_stale) return;
   const LdltPlan& l = m_l_ref;
   const int C = (m_batch + 63) / 64;
   const int nl = static_cast<int>(std::max<int64_t>(1, l.nnzL));
@@ -1960,7 +1901,7 @@ size_t DeviceNlp::download_factor_scratch(int which, std::vector<double>& out) {
   const size_t B = static_cast<size_t>(m_batch);
   const size_t count = which == 0 ? static_cast<size_t>(l.n) : std::max<uint32_t>(1, l.n_contrib);
   out.assign(B * count, 0.0);
-  if (!m_il) {
+  if (!m_mode.il) {
     download(which == 0 ? m_zv.p : m_contrib.p, out.data(), B * count);
     return count;
   }
@@ -1971,19 +1912,6 @@ size_t DeviceNlp::download_factor_scratch(int which, std::vector<double>& out) {
   for (size_t b = 0; b < B; ++b)
     for (size_t i = 0; i < count; ++i) out[b * count + i] = raw[((b / kIlW) * count + i) * kIlW + b % kIlW];
   return count;
-}
-
-// Lane-per-problem pays from one 64-problem chunk per task on (r02: from ~200 problems — the backward
-// solve was one wave per task and chunk, a chain of columns; with the columns of a level dealt to four
-// waves, 64 x N=500: 251 k steps/s against 224-238 k for the per-task kernels,
-// profiles/r03_b64_probe.txt; 512 x N=1000: 508 k vs 171 k).  SLPX_LDLT_IL=0 turns it off,
-// SLPX_IL_MIN_BATCH moves the threshold.
-bool DeviceNlp::interleaved_for(int batch) {
-  if (const char* env = std::getenv("SLPX_LDLT_IL"))
-    if (env[0] == '0') return false;
-  int min_batch = 64;
-  if (const char* env = std::getenv("SLPX_IL_MIN_BATCH")) min_batch = std::atoi(env);
-  return batch >= min_batch;
 }
 
 // p <- p + K_reg^-1 (b - K p), `iters` times: b = the right-hand side now in m_rhs, p = the
@@ -2244,31 +2172,21 @@ bool DeviceNlp::ipm_ride_errors_in_next_step(int slot_out) {
 
 bool DeviceNlp::ipm_ride_possible() {
   if (!twin_available()) return false;
-  if (m_ride_lds_ok < 0) {
+  if (m_mode.ride < 0) {
     // the riding workgroups' LDS (ipm_error_block) beside the tasks': the launch takes the larger of the two
-    const char* env = std::getenv("SLPX_IPM_RIDE");
-    m_ride_lds_ok = (env == nullptr || env[0] != '0') ? 1 : 0;
-    if (m_ride_lds_ok) {
-      int cus = 0, per_cu = 0;
-      SLPX_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m_device));
+    int per_cu = 0;
+    if (m_sw.ipm_ride) {
       const size_t lds = std::max<size_t>(m_mf_lds, sizeof(double) * kIpmErrLdsDoubles);
-      const size_t wgs = 2 * m_l_ref.tasks.size() + 64 + m_reduces.n;
-      auto resident = [&](auto kernel, int threads) {
-        SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        SLPX_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds));
-        return wgs <= static_cast<size_t>(per_cu) * cus;
-      };
-      // (the tasks of both attempts AND the riding workgroups resident at once: a task that asks for the verdict must
-      // never keep a riding workgroup from being dispatched)
-      const bool fits = m_twin_threads == 1024 ? resident(&ldlt_mf_twin_kernel<1024, true>, 1024) : resident(&ldlt_mf_twin_kernel<512, true>, 512);
-      if (!fits) m_ride_lds_ok = 0;
+      per_cu = m_mode.twin_threads == 1024 ? workgroups_per_cu(reinterpret_cast<const void*>(&ldlt_mf_twin_kernel<1024, true>), 1024, lds)
+                                           : workgroups_per_cu(reinterpret_cast<const void*>(&ldlt_mf_twin_kernel<512, true>), 512, lds);
       if (m_ipm_ride_verdict.n == 0) m_ipm_ride_verdict.upload(std::vector<double>(1, 0.0));
-      if (std::getenv("SLPX_LDLT_VERBOSE"))
-        std::fprintf(stderr, "ldlt riding error launch: %zu workgroups, %d of %d threads per CU x %d CUs%s\n", wgs, per_cu, m_twin_threads, cus,
-                     fits ? "" : ": NOT resident at once");
     }
+    choose_ride(m_mode, m_plan, m_reduces.n, static_cast<size_t>(per_cu) * m_cus, m_sw);
+    if (m_sw.ipm_ride && std::getenv("SLPX_LDLT_VERBOSE"))
+      std::fprintf(stderr, "ldlt riding error launch: %zu workgroups, %d of %d threads per CU x %d CUs%s\n", riding_workgroups(m_plan, m_reduces.n),
+                   per_cu, m_mode.twin_threads, m_cus, m_mode.ride ? "" : ": NOT resident at once");
   }
-  return m_ride_lds_ok != 0;
+  return m_mode.ride != 0;
 }
 
 bool DeviceNlp::ipm_ride_wait(int slot_out) {

@@ -18,7 +18,7 @@
 // The symbolic phase is run with small tasks in this mode (newton.cpp).  The per-task
 // kernels of ldlt_kernels.h (one workgroup per task and problem, eight lanes per entry)
 // remain the path of a single problem, where latency rules; this is the throughput path
-// (DeviceNlp::interleaved_for: batches of about 200 problems and more).
+// (interleaved_for, system_choice.hpp: batches of about 200 problems and more).
 //
 // Arithmetic per entry is the same left-looking gather
 //   U(i,j) = A(i,j) [+delta | -gamma] - sum(update blocks of child tasks) - sum_k U(i,k) U(j,k) / d_k

@@ -13,40 +13,25 @@
 #include <cstring>
 #include <limits>
 #include <stdexcept>
+#include <string>
 
 namespace slpx {
 
-// The sparse plan, or — where a column of L does not fit the LDS of a task (a Hessian dense in hundreds of
-// variables: single shooting), or SLPX_DENSE=1 asks for it — the dense one: the reference's dense branch
-// (util/dense_regularized_ldlt.hpp, chosen there by density: interior_point.hpp:340-352) instead of a refusal.
-static LdltPlan plan_or_dense(const CscPattern& lhs, int n_dec, const LdltOptions& lopt, const std::vector<int32_t>* user_perm,
-                              const std::vector<uint8_t>* diag_has_source, int batch) {
-  constexpr int kDenseMaxOrder = 8192;  // 512 MB of factors per problem, two columns in LDS
-  // (and the whole batch's factors, batch x n x n doubles, within reach of one device: 64 GB)
-  auto dense_plan = [&] {
-    const double bytes = 8.0 * static_cast<double>(std::max(1, batch)) * lhs.cols * lhs.cols;
-    if (bytes > 64.0 * (1u << 30))
-      throw std::runtime_error("slpx: the dense factorization of " + std::to_string(batch) + " systems of order " + std::to_string(lhs.cols) +
-                               " needs " + std::to_string(static_cast<long long>(bytes / (1u << 30))) +
-                               " GB of factors; SLPX_DENSE=0 keeps the sparse plan (or refuses the model), a smaller batch fits");
-    return build_dense_ldlt_plan(lhs, n_dec);
-  };
-  const char* env = std::getenv("SLPX_DENSE");
-  if (env != nullptr && env[0] == '1' && lhs.cols <= kDenseMaxOrder) return dense_plan();
-  try {
-    return build_ldlt_plan(lhs, n_dec, lopt, user_perm, diag_has_source);
-  } catch (const std::runtime_error& e) {
-    if (!ldlt_plan_error_is_too_big(e) || lhs.cols > kDenseMaxOrder || (env != nullptr && env[0] == '0')) throw;
-    if (std::getenv("SLPX_LDLT_VERBOSE"))
-      std::fprintf(stderr, "ldlt: %s — the system of order %d is factored as a dense matrix\n", e.what(), lhs.cols);
-    return dense_plan();
-  }
+// The plan of choose_ldlt_plan (system_choice.cpp), with its one diagnostic
+static LdltPlan plan_for(const KktPlan& k, int n_dec, bool reference_takes_dense, const std::vector<int32_t>* user_perm,
+                         const std::vector<uint8_t>& diag_has_source, int batch, const LdltOptions& lopt, const LdltOptions* pair_retry,
+                         const Switches& sw) {
+  std::string dense_because;
+  LdltPlan l = choose_ldlt_plan(k.lhs, n_dec, reference_takes_dense, user_perm, &diag_has_source, batch, lopt, pair_retry, sw, &dense_because);
+  if (!dense_because.empty() && std::getenv("SLPX_LDLT_VERBOSE"))
+    std::fprintf(stderr, "ldlt: %s — the system of order %d is factored as a dense matrix\n", dense_because.c_str(), k.lhs.cols);
+  return l;
 }
 
 NewtonSystem::NewtonSystem(Graph& g, const std::vector<NodeId>& x, NodeId f,
                            const std::vector<NodeId>& c_e, const std::vector<NodeId>& c_i,
                            const NewtonOptions& opt, const std::vector<int32_t>* user_perm, bool defer_device)
-    : m_opt(opt), m_graph(&g), m_x_nodes(x), m_ce_nodes(c_e), m_ci_nodes(c_i) {
+    : m_opt(opt), m_sw(Switches::from_environment()), m_graph(&g), m_x_nodes(x), m_ce_nodes(c_e), m_ci_nodes(c_i) {
   SetupLap lap;
   // the HIP runtime comes up (context, first allocation: 50-700 ms in a fresh process) while the
   // host compiles the model
@@ -65,78 +50,9 @@ NewtonSystem::NewtonSystem(Graph& g, const std::vector<NodeId>& x, NodeId f,
       for (int p = m_k.lhs.colptr[c]; p < m_k.lhs.colptr[c + 1]; ++p)
         if (m_k.lhs.rowidx[p] == c)
           diag_has_source[c] = (m_k.dptr[p + 1] > m_k.dptr[p]) || (m_k.pptr[p + 1] > m_k.pptr[p]);
-    // One problem: big tasks = few rounds and levels (latency).  A batch is throughput bound
-    // by how many tasks fit a CU's LDS at once: half-size tasks (~30 KB instead of ~60 KB)
-    // put five instead of two workgroups on a CU and have fewer levels each.
-    LdltOptions lopt = opt.ldlt;
-    if (opt.batch >= 16 && lopt.task_entries == LdltOptions{}.task_entries) lopt.task_entries = 1024;
-    // one lane per problem (ldlt_il_kernels.h): a task's values x 64 problems must fit LDS
-    // (measured at 512 x N=1000, ms per factorization: 192 -> 0.55 but some problems then need a
-    // second attempt, 384 -> 0.67, 768 -> 0.79, 1024 -> 1.25)
-    // (below ~200 problems the rounds, not the chip, bound a factorization: fewer, bigger tasks — 64 x N=500:
-    // 384 entries 242 k steps/s, 512: 251 k, 768: 247 k)
-    if (DeviceNlp::interleaved_for(opt.batch) && lopt.task_entries >= 1024) lopt.task_entries = opt.batch < 192 ? 512 : 384;
-    // the interleaved kernels walk column levels; supernodal levels are the per-task kernels'
-    if (DeviceNlp::interleaved_for(opt.batch)) lopt.supernodal = false;
-    // one problem: the multifrontal step (ldlt_mf_kernels.h) — every supernode a dense front, so a chain
-    // of two columns already saves a level (the pair-list kernels' chain pass only paid from four)
-    if (opt.batch == 1 && lopt.supernodal) {
-      const char* env = std::getenv("SLPX_LDLT_MF");
-      if (env == nullptr || env[0] != '0') {
-        lopt.multifrontal = true;
-        lopt.min_supernode_width = 2;
-        lopt.relax_zeros = 8;
-        lopt.balance_supernode_cuts = true;
-        lopt.chain_from_deepest_child = true;
-        lopt.chain_from_deepest_min_round = 0;
-      }
-    }
-    if (const char* env = std::getenv("SLPX_RELAX_ZEROS")) lopt.relax_zeros = std::atoi(env);
-    if (const char* env = std::getenv("SLPX_SN_MIN_WIDTH")) lopt.min_supernode_width = std::atoi(env);
-    if (const char* env = std::getenv("SLPX_MFMA_MIN_ENTRIES")) lopt.mfma_min_entries = static_cast<uint32_t>(std::atoi(env));
-    // One problem (or a handful: the same plan, so that a small batch and single problems agree to
-    // the bit), smaller than the BASELINE horizon: smaller tasks (less plan to stage per
-    // task, shorter level passes, more of the chip in the leaf round) — task size with the square
-    // root of the system's order.  Measured (fused kernel, us): cart-pole N=300 1024 entries 47.9
-    // vs 2048 54.6; N=500 1536 52.3 vs 2048 53.8; N=1000 2048 56.2 vs 1792 59.4.
-    if (opt.batch < 16 && lopt.task_entries == LdltOptions{}.task_entries && m_k.dim < 9000) {
-      const double scaled = 2048.0 * std::sqrt(static_cast<double>(m_k.dim) / 9000.0);
-      lopt.task_entries = std::clamp<uint32_t>(256u * static_cast<uint32_t>(std::lround(scaled / 256.0)), 1024u, 2048u);
-    }
-    if (const char* env = std::getenv("SLPX_TASK_ENTRIES")) lopt.task_entries = static_cast<uint32_t>(std::atoi(env));
-    // One problem, all rounds in one launch: about 512 of the 1024-thread task workgroups are
-    // resident at a time (two per CU).  A plan with more tasks than that serializes its tail
-    // and usually has a round more than necessary; twice the task size fixes both (cart-pole
-    // N=5000: 547 tasks / 4 rounds -> 265 / 3, factorization 73 -> 62 us, backward solve 42 -> 38;
-    // at N=1000 the 137 tasks of the default are the better choice: 39 vs 45 us).
-    // (more than ~250 tasks take two workgroups per CU, 80 KB of LDS each: there the chains-from-the-deepest-
-    // child rule stays out of the leaf tasks, where it only adds fronts — tables, arena — to full levels:
-    // cart-pole N=5000 58.6 us against 62.1 without the rule and 96 (not resident: two launches) with it everywhere)
-    // Both rules are applied inside the build, after its first task partition (LdltOptions::single_problem_task_rules).
-    lopt.single_problem_task_rules = opt.batch == 1 && std::getenv("SLPX_TASK_ENTRIES") == nullptr;
-    // The reference's own choice (interior_point.hpp:340-352, sqp.hpp:238-240, newton.hpp:133-135): a system whose lower
-    // triangle fills a quarter of it or more — the small problems of its unit tests, single shooting — is factored
-    // dense, with Eigen::LDLT's diagonal pivoting (ldlt_dense_pivoted_factor_kernel).  SLPX_DENSE=0: the sparse plan
-    // whatever the fill (the sparse kernels do not pivot: D, and with it the regularization the policy settles on, may
-    // then differ from the reference's on such a system); a caller's elimination order asks for the sparse plan too.
-    {
-      const char* denv = std::getenv("SLPX_DENSE");
-      if (m_k.reference_takes_dense(st.Ae.nnz()) && user_perm == nullptr && (denv == nullptr || denv[0] != '0') && m_k.dim <= 2048) {
-        m_l = build_dense_ldlt_plan(m_k.lhs, st.n);
-        m_l.dense_pivoted = denv == nullptr || denv[0] != '1';  // (SLPX_DENSE=1 keeps meaning the plain dense kernel)
-        return;
-      }
-    }
-    m_l = plan_or_dense(m_k.lhs, st.n, lopt, user_perm, &diag_has_source, opt.batch);
-    if (lopt.multifrontal && !m_l.mf && !m_l.dense) {
-      // the fronts were not built (a limit of their addressing, or a refused plan): the pair-list kernels run this
-      // system, with THEIR tuning — chains from four columns, exact structures — not the fronts'
-      LdltOptions pair = opt.ldlt;
-      pair.task_entries = lopt.task_entries;
-      pair.supernodal = lopt.supernodal;
-      pair.single_problem_task_rules = false;
-      m_l = plan_or_dense(m_k.lhs, st.n, pair, user_perm, &diag_has_source, opt.batch);
-    }
+    const LdltOptions lopt = choose_ldlt_options(opt.ldlt, opt.batch, m_k.dim, /*compiled_model=*/true, m_sw);
+    const LdltOptions pair = pair_list_options(opt.ldlt, lopt);
+    m_l = plan_for(m_k, st.n, m_k.reference_takes_dense(st.Ae.nnz()), user_perm, diag_has_source, opt.batch, lopt, &pair, m_sw);
   };
   m_s = build_nlp_structure(g, x, f, c_e, c_i, opt.tape, plan_linear_algebra);
   lap("= AD structure + tape compile, KKT plan, LDLT symbolic");
@@ -156,12 +72,12 @@ FrDevice& NewtonSystem::restoration_device() {
 void NewtonSystem::finish_device() {
   if (m_dev) return;
   SetupLap lap;
-  m_dev = std::make_unique<DeviceNlp>(m_s, m_k, m_l, m_opt.batch, m_opt.device);
+  m_dev = std::make_unique<DeviceNlp>(m_s, m_k, m_l, m_opt.batch, m_opt.device, m_sw);
   lap("= device upload + tape JIT");
 }
 
 NewtonSystem::NewtonSystem(const CscPattern& lower, int n_dec, int m_e, const NewtonOptions& opt)
-    : m_opt(opt) {
+    : m_opt(opt), m_sw(Switches::from_environment()) {
   if (lower.cols != n_dec + m_e || lower.rows != lower.cols)
     throw std::runtime_error("slpx: the matrix must be square of order n + m_e");
   m_opt.batch = std::max(1, opt.batch);
@@ -200,12 +116,9 @@ NewtonSystem::NewtonSystem(const CscPattern& lower, int n_dec, int m_e, const Ne
   m_k.g_src.assign(n_dec, -1);
   m_k.ai_rowptr.assign(1, 0);
   m_k.ae_rowptr.assign(m_e + 1, 0);
-  LdltOptions lopt = opt.ldlt;
-  if (opt.batch >= 16 && lopt.task_entries == LdltOptions{}.task_entries) lopt.task_entries = 1024;
-  if (DeviceNlp::interleaved_for(opt.batch) && lopt.task_entries >= 1024) lopt.task_entries = opt.batch < 192 ? 512 : 384;
-  if (DeviceNlp::interleaved_for(opt.batch)) lopt.supernodal = false;
-  m_l = plan_or_dense(m_k.lhs, n_dec, lopt, nullptr, &diag_has_source, m_opt.batch);
-  m_dev = std::make_unique<DeviceNlp>(m_s, m_k, m_l, m_opt.batch, opt.device);
+  const LdltOptions lopt = choose_ldlt_options(opt.ldlt, opt.batch, dim, /*compiled_model=*/false, m_sw);
+  m_l = plan_for(m_k, n_dec, /*reference_takes_dense=*/false, nullptr, diag_has_source, m_opt.batch, lopt, nullptr, m_sw);
+  m_dev = std::make_unique<DeviceNlp>(m_s, m_k, m_l, m_opt.batch, opt.device, m_sw);
   m_dev->set_scaling(std::vector<double>(m_s.n_scales(), 1.0));
   reset_regularization();
 }

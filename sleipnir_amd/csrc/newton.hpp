@@ -21,6 +21,8 @@
 #include "ldlt_policy.hpp"
 #include "ldlt_symbolic.hpp"
 #include "nlp.hpp"
+#include "switches.hpp"
+#include "system_choice.hpp"
 
 namespace slpx {
 
@@ -61,6 +63,7 @@ class NewtonSystem {
   const std::vector<NodeId>& c_e_nodes() const { return m_ce_nodes; }
   const std::vector<NodeId>& c_i_nodes() const { return m_ci_nodes; }
   const NewtonOptions& options() const { return m_opt; }
+  const Switches& switches() const { return m_sw; }  // the environment as it was when this system was made
 
   // Feasibility restoration runs on THIS system (restoration.hpp): the device state of the restoration iterate
   // beyond (x, s, y, z), made when a solve first enters restoration
@@ -198,6 +201,7 @@ class NewtonSystem {
 
  private:
   NewtonOptions m_opt;
+  Switches m_sw;
   Graph* m_graph = nullptr;
   std::vector<NodeId> m_x_nodes, m_ce_nodes, m_ci_nodes;
   std::unique_ptr<FrDevice> m_fr;

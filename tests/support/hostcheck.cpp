@@ -166,21 +166,27 @@ static void hc_build(hc_handle* h, slpx_problem* p, const int32_t* perm, int32_t
     lopt.supernodal = false;
     lopt.task_entries = static_cast<uint32_t>(std::atoi(env));
   }
-  // (the product's rule, newton.cpp: plan_or_dense)
-  const char* dense_env = std::getenv("SLPX_DENSE");
-  if (h->k.reference_takes_dense(h->s.Ae.nnz()) && up.empty() && (dense_env == nullptr || dense_env[0] != '0') && h->k.dim <= 2048) {
-    h->l = build_dense_ldlt_plan(h->k.lhs, h->s.n);
-    h->l.dense_pivoted = dense_env == nullptr || dense_env[0] != '1';
-  } else if (dense_env != nullptr && dense_env[0] == '1') {
-    h->l = build_dense_ldlt_plan(h->k.lhs, h->s.n);
-  } else {
-    try {
-      h->l = build_ldlt_plan(h->k.lhs, h->s.n, lopt, up.empty() ? nullptr : &up, &diag_has_source);
-    } catch (const std::runtime_error& e) {
-      if (!ldlt_plan_error_is_too_big(e)) throw;
-      h->l = build_dense_ldlt_plan(h->k.lhs, h->s.n);
-    }
+  // The product's route to a plan (csrc/system_choice.cpp).  Here SLPX_DENSE=0 only keeps the reference's density rule
+  // out: a model whose columns fit no task still gets its dense plan (the product refuses it then).
+  Switches sw = Switches::from_environment();
+  bool by_density = h->k.reference_takes_dense(h->s.Ae.nnz());
+  if (sw.dense && !*sw.dense) {
+    by_density = false;
+    sw.dense.reset();
   }
+  // SLPX_HOSTCHECK_PRODUCT_BATCH=B: the options NewtonSystem gives a compiled model in a batch of B, instead of the knobs above
+  int batch = 1;
+  LdltOptions pair;
+  const char* product_batch = std::getenv("SLPX_HOSTCHECK_PRODUCT_BATCH");
+  if (product_batch != nullptr) {
+    batch = std::atoi(product_batch);
+    LdltOptions base;
+    if (task_entries > 0) base.task_entries = task_entries;
+    lopt = choose_ldlt_options(base, batch, h->k.dim, /*compiled_model=*/true, sw);
+    pair = pair_list_options(base, lopt);
+  }
+  h->l = choose_ldlt_plan(h->k.lhs, h->s.n, by_density, up.empty() ? nullptr : &up, &diag_has_source, batch, lopt,
+                          product_batch != nullptr ? &pair : nullptr, sw);
   h->scales.assign(h->s.n_scales(), 1.0);
   h->in_scale.assign(h->s.n_inputs(), 1.0);
   h->V = h->s.V_static_raw;

@@ -8,6 +8,8 @@ eq_only, chain<n>; N ignored).  Options, for profiles/plan_hash_matrix.py:
     --small-lds B      the tape compiler's small-task LDS, bytes
     --user-perm        build once, then again with the first build's own permutation as `user_perm`: hashes of the second
     --info             a JSON object {"hash", "tasks", "rounds", "mf", "mfma", "dense"} instead of the list of hashes
+    --product-batch B  the options the product gives this model in a batch of B (csrc/system_choice.cpp:
+                       choose_ldlt_options and the plan route of NewtonSystem) instead of hostcheck's own knobs
     --first-pass       with --info: also "tasks_first_pass", the tasks of the same build without
                        SLPX_HOSTCHECK_SINGLE_PROBLEM_RULES (another count: the partition was redone with bigger tasks)"""
 import argparse
@@ -55,7 +57,10 @@ def main(argv=None) -> None:
     ap.add_argument("--user-perm", action="store_true")
     ap.add_argument("--info", action="store_true")
     ap.add_argument("--first-pass", action="store_true")
+    ap.add_argument("--product-batch", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.product_batch > 0:
+        os.environ["SLPX_HOSTCHECK_PRODUCT_BATCH"] = str(a.product_batch)
     sa.lib().slpx_graph_reset()
     pp = problem(a.kind, a.N)
     kw = {"task_entries": a.task_entries, "small_lds_bytes": a.small_lds}

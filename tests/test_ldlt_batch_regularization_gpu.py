@@ -63,7 +63,7 @@ def _switches(env):
 
 
 def _interleaved_rule(B):
-    """DeviceNlp::interleaved_for, from the switches it honours."""
+    """interleaved_for (csrc/system_choice.hpp), from the switches it honours."""
     if os.environ.get("SLPX_LDLT_IL", "1")[0] == "0":
         return False
     return B >= int(os.environ.get("SLPX_IL_MIN_BATCH", "64"))
