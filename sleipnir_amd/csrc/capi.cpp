@@ -832,7 +832,7 @@ int slpx_ldlt_factor(slpx_system* s, const double* delta, const double* gamma, d
     std::vector<uint8_t> active(B, 1);
     dev.factor(d, g, active);
     std::vector<slpx::LdltStats> st;
-    dev.read_stats(st);
+    dev.ldlt().read_stats(st);
     for (int b = 0; b < B; ++b) {
       stats[5 * b + 0] = st[b].n_pos;
       stats[5 * b + 1] = st[b].n_neg;
@@ -982,19 +982,19 @@ int64_t slpx_system_get(slpx_system* s, int which, double* out) {
       case 0: src = dev.d_V(); count = B * st.nV; break;
       case 1: src = dev.d_lhs(); count = B * k.lhs.nnz(); break;
       case 2: src = dev.d_rhs(); count = B * k.dim; break;
-      case 3: src = dev.d_p(); count = B * k.dim; break;
+      case 3: src = dev.ldlt().d_p(); count = B * k.dim; break;
       case 4: src = dev.d_ps(); count = B * st.m_i; break;
       case 5: src = dev.d_pz(); count = B * st.m_i; break;
-      case 6: dev.materialize_factor(); src = dev.d_D(); count = B * l.n; break;
-      case 7: dev.materialize_factor(); src = dev.d_Lx(); count = B * l.nnzL; break;
+      case 6: dev.ldlt().materialize_factor(); src = dev.ldlt().d_D(); count = B * l.n; break;
+      case 7: dev.ldlt().materialize_factor(); src = dev.ldlt().d_Lx(); count = B * l.nnzL; break;
       case 8: src = dev.d_x(); count = st.n; if (B != 1) throw std::runtime_error("slpx_system_get: x of a batch is strided"); break;
       case 9: src = dev.d_s(); count = B * st.m_i; break;
       case 10: src = dev.d_y(); count = B * st.m_e; break;
       case 11: src = dev.d_z(); count = B * st.m_i; break;
       case 12:
-      case 13: {  // what a factorization leaves besides L and D, batch-major (DeviceNlp::download_factor_scratch)
+      case 13: {  // what a factorization leaves besides L and D, batch-major (DeviceLdlt::download_factor_scratch)
         std::vector<double> scratch;
-        count = B * static_cast<int64_t>(dev.download_factor_scratch(which - 12, scratch));
+        count = B * static_cast<int64_t>(dev.ldlt().download_factor_scratch(which - 12, scratch));
         if (out) std::copy(scratch.begin(), scratch.end(), out);
         return;
       }
@@ -1116,7 +1116,7 @@ int slpx_debug_tmpl_clocks(slpx_system* s, uint64_t* out, int32_t blocks) {
 int slpx_debug_ldlt_clocks(slpx_system* s, uint32_t next_round, uint64_t* out24) {
   return guard([&] {
     unsigned long long t[24];
-    s->get().device().debug_ldlt_clocks(next_round, t);
+    s->get().device().ldlt().debug_clocks(next_round, t);
     for (int i = 0; i < 24; ++i) out24[i] = t[i];
   });
 }

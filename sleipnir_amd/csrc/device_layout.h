@@ -46,6 +46,8 @@ constexpr unsigned long long kSlotEmpty = 0x7ff8dead0badbeefull;
 constexpr int kIlWShift = 4;  // (measured: 8-wide rows 0.74 ms per factorization of 512 x N=1000, 16-wide 0.67)
 constexpr int kIlW = 1 << kIlWShift;  // problems per interleaved row
 constexpr int kIlRowsPerChunk = 64 / kIlW;  // rows groups covering a 64-problem chunk
+// number of 16-problem rows groups a batch occupies (padded to whole waves of 64 problems)
+__host__ __device__ inline int il_groups(int batch) { return kIlRowsPerChunk * ((batch + 63) / 64); }
 constexpr int kIlFactorThreads = 512;  // (ldlt_il_kernels.h has the measurements)
 constexpr int kIlSlots = kIlFactorThreads / kIlW;  // entries of a level a factorization workgroup works on at a time
 

@@ -169,7 +169,7 @@ void BatchFrDevice::fill(FrBatchArgs& G) {
   G.active = m_active.p;
   G.lhs = dev.lhs_raw();
   G.rhs = dev.rhs_raw();
-  G.p_sys = dev.d_p();
+  G.p_sys = dev.ldlt().d_p();
   G.keep_p = m_keep_p.p;
   G.keep_ps0 = m_keep_ps0.p;
   G.keep_pz0 = m_keep_pz0.p;

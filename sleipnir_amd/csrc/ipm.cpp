@@ -152,7 +152,7 @@ ExitStatus ipm_core_host(NewtonSystem& sys, const Vec& scales,
     rep.gamma = sys.constraint_jacobian_regularization()[0];
 
     auto download_step = [&](Vec& px, Vec& py, Vec& ps, Vec& pz) {
-      dev.download(dev.d_p(), p.data(), dim);
+      dev.download(dev.ldlt().d_p(), p.data(), dim);
       std::copy(p.begin(), p.begin() + n, px.begin());
       for (int j = 0; j < m_e; ++j) py[j] = -p[n + j];
       if (m_i) {
@@ -225,7 +225,7 @@ ExitStatus ipm_core_host(NewtonSystem& sys, const Vec& scales,
                                       hipMemcpyHostToDevice, dev.stream()));
         dev.solve();
         ++rep.solves;
-        dev.download(dev.d_p(), p.data(), dim);
+        dev.download(dev.ldlt().d_p(), p.data(), dim);
         std::copy(p.begin(), p.begin() + n, soc_px.begin());
         for (int j = 0; j < m_e; ++j) soc_py[j] = -p[n + j];
         {  // p_s, p_z with the corrected c_i - s (:479-480)
@@ -628,7 +628,7 @@ ExitStatus ipm_core_resident(NewtonSystem& sys, const Vec& scales,
         const Vec g = cv.g_dense();
         const double current_kkt = kkt_error_impl<ErrType::ONE_NORM>(st, g, cv.Ae(), cv.c_e(), cv.Ai(),
                                                                      cv.c_i(), s, y, z, mu, nullptr);
-        dev.download(dev.d_p(), p.data(), dim);
+        dev.download(dev.ldlt().d_p(), p.data(), dim);
         std::copy(p.begin(), p.begin() + n, p_x.begin());
         for (int j = 0; j < m_e; ++j) p_y[j] = -p[n + j];
         if (m_i) {
@@ -837,7 +837,7 @@ bool lagrange_multiplier_estimate(NewtonSystem& sys, const Vec& V, const Vec& s,
     rep.solves += 3;
   }
   Vec p(dim);
-  dev.download(dev.d_p(), p.data(), dim);
+  dev.download(dev.ldlt().d_p(), p.data(), dim);
   y.assign(m_e, 0.0);
   for (int j = 0; j < m_e; ++j) y[j] = -p[n + j];
   Vec aid(m_i, 0.0);
@@ -1129,7 +1129,7 @@ ExitStatus restoration_core(NewtonSystem& sys, FrDevice& fr, const std::vector<I
         dev.download_V(Vo.data());
         const double current_kkt = restoration_kkt_error_one_norm(st, Vo, X, S, y, Z, x_r, w, rho, mu);
         Vec p(dim), ps0(m_i), pz0(m_i), dpn(M), psx(M), pzx(M);
-        dev.download(dev.d_p(), p.data(), dim);
+        dev.download(dev.ldlt().d_p(), p.data(), dim);
         if (m_i) {
           dev.download(dev.d_ps(), ps0.data(), m_i);
           dev.download(dev.d_pz(), pz0.data(), m_i);
@@ -1323,7 +1323,7 @@ ExitStatus sqp_core(NewtonSystem& sys, const Vec& scales, const std::vector<Iter
     return IpmTrialOut{trial_f, norm_1(trial_c_e.data(), m_e), 0.0, finite ? 1.0 : 0.0};
   };
   auto solve_step = [&](Vec& px, Vec& py) {
-    dev.download(dev.d_p(), p.data(), dim);
+    dev.download(dev.ldlt().d_p(), p.data(), dim);
     std::copy(p.begin(), p.begin() + n, px.begin());
     for (int j = 0; j < m_e; ++j) py[j] = -p[n + j];
   };
@@ -1509,7 +1509,7 @@ ExitStatus newton_core(NewtonSystem& sys, const Vec& scales, const std::vector<I
     rep.t_kkt_decomp += since(t0);
     if (info[0] != FactorInfo::Success) return ExitStatus::FACTORIZATION_FAILED;
     rep.delta = sys.hessian_regularization()[0];
-    dev.download(dev.d_p(), p_x.data(), n);
+    dev.download(dev.ldlt().d_p(), p_x.data(), n);
 
     t0 = clk::now();
     double D_phi = 0.0;

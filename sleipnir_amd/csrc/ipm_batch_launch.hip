@@ -249,7 +249,7 @@ void BatchIpmDevice::upload() {
 void BatchIpmDevice::newton_direction(std::vector<double>& dir) {
   DeviceNlp& dev = sys.device();
   hipStream_t st = dev.stream();
-  SLPX_HIP_CHECK(hipMemcpyAsync(m_p.p, dev.d_p(), m_p.n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  SLPX_HIP_CHECK(hipMemcpyAsync(m_p.p, dev.ldlt().d_p(), m_p.n * sizeof(double), hipMemcpyDeviceToDevice, st));
   if (m_i) {
     SLPX_HIP_CHECK(hipMemcpyAsync(m_ps.p, dev.d_ps(), static_cast<size_t>(B) * m_i * sizeof(double), hipMemcpyDeviceToDevice, st));
     SLPX_HIP_CHECK(hipMemcpyAsync(m_pz.p, dev.d_pz(), static_cast<size_t>(B) * m_i * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -313,7 +313,7 @@ void BatchIpmDevice::soc_step(std::vector<double>& sd) {
   hipLaunchKernelGGL(batch_soc_rhs_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), A, m_active.p);
   SLPX_HIP_CHECK(hipGetLastError());
   dev.solve();  // (every instance's factor; the slices of the others are not read)
-  hipLaunchKernelGGL(batch_soc_direction_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), m_Vcur.p, nV, dev.d_p(),
+  hipLaunchKernelGGL(batch_soc_direction_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), m_Vcur.p, nV, dev.ldlt().d_p(),
                      m_cur, m_scims.p, m_mu.p, m_tau.p, BatchIter{m_sx.p, m_ss.p, m_sy.p, m_sz.p},
                      m_active.p, m_out.p);
   SLPX_HIP_CHECK(hipGetLastError());
@@ -354,7 +354,7 @@ BatchEqDevice::BatchEqDevice(NewtonSystem& sys_) : BatchDevice(sys_) {
 
 void BatchEqDevice::direction(std::vector<double>& dphi) {
   DeviceNlp& dev = sys.device();
-  hipLaunchKernelGGL(eq_direction_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(), m_Vcur.p, nV, dev.d_p(),
+  hipLaunchKernelGGL(eq_direction_kernel, dim3(B), dim3(kBatchThreads), 0, dev.stream(), dev.kdev(), m_Vcur.p, nV, dev.ldlt().d_p(),
                      EqIter{m_px.p, m_py.p}, m_active.p, m_out.p);
   SLPX_HIP_CHECK(hipGetLastError());
   download_out(1, dphi);
@@ -404,7 +404,7 @@ void BatchEqDevice::soc_step() {
   hipLaunchKernelGGL(eq_soc_rhs_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), A, m_active.p);
   SLPX_HIP_CHECK(hipGetLastError());
   dev.solve();  // (every instance's factor; the slices of the others are not read)
-  hipLaunchKernelGGL(eq_direction_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), m_Vcur.p, nV, dev.d_p(),
+  hipLaunchKernelGGL(eq_direction_kernel, dim3(B), dim3(kBatchThreads), 0, st, dev.kdev(), m_Vcur.p, nV, dev.ldlt().d_p(),
                      EqIter{m_sx.p, m_sy.p}, m_active.p, static_cast<double*>(nullptr));
   SLPX_HIP_CHECK(hipGetLastError());
 }

@@ -7,10 +7,8 @@
 //                  (expression_graph.hpp:86-153, jacobian.hpp:134-156, hessian.hpp:132-157)
 //   kkt_assemble   lhs values by gather   (interior_point.hpp:426-440)
 //   kkt_rhs        rhs by column gathers  (interior_point.hpp:444-448)
-//   ldlt_factor    (ldlt_kernels.h) one round of the task-parallel left-looking LDLᵀ
-//                  + inertia (sparse_regularized_ldlt.hpp:74-83,105-109, inertia.hpp:40-50)
-//   ldlt_fwd/bwd   (ldlt_kernels.h) triangular solves (sparse_regularized_ldlt.hpp:159-161)
 //   step_backsub   pˢ, pᶻ                 (interior_point.hpp:479-480)
+// The factorization and the solves between them: DeviceLdlt, device_ldlt.hip.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -25,14 +23,10 @@
 #include "device.hpp"
 #include "device_images.hpp"
 #include "kkt_kernels.h"
-#include "ldlt_kernels.h"
-#include "ldlt_mf_kernels.h"
-#include "ldlt_dense_kernels.h"
 #include "setup_threads.hpp"
-#include "ldlt_il_kernels.h"
 #include "tape_jit.hpp"
 #include "ipm_decide.h"
-#include "ipm_kernels.h"
+#include "ipm_launch_kernels.h"
 #include "tape_kernels.h"
 #include "tape_ops.h"
 #include "setup_timing.hpp"
@@ -520,83 +514,12 @@ KktDev KktPlanDevice::view() const {
   return K;
 }
 
-void LdltPlanDevice::upload(const LdltPlan& l) {
-  tasks.upload(l.tasks);
-  ent_src.upload(l.ent_src);
-  ent_flags.upload(l.ent_flags);
-  ent_col.upload(l.ent_col);
-  ent_out.upload(l.ent_out);
-  ent_pair_ptr.upload(l.ent_pair_ptr);
-  ent_contrib_ptr.upload(l.ent_contrib_ptr);
-  contrib_idx.upload(l.contrib_idx);
-  ext_dst.upload(l.ext_dst);
-  lvl_ptr.upload(l.lvl_ptr);
-  pairs.upload(l.pairs);
-  col_perm.upload(l.col_perm);
-  col_lvl_ptr.upload(l.col_lvl_ptr);
-  fwd_ptr.upload(l.fwd_ptr);
-  fwd_contrib_ptr.upload(l.fwd_contrib_ptr);
-  scontrib_idx.upload(l.scontrib_idx);
-  fwd_items.upload(l.fwd_items);
-  sext_ptr.upload(l.sext_ptr);
-  sext_dst.upload(l.sext_dst);
-  sext_items.upload(l.sext_items);
-  bwd_ptr.upload(l.bwd_ptr);
-  bwd_items.upload(l.bwd_items);
-  perm.upload(l.perm);
-  round_ptr.upload(l.round_ptr);
-  sn_desc.upload(l.sn_desc);
-  sn_lvl_ptr.upload(l.sn_lvl_ptr);
-  col_sn.upload(l.col_sn);
-  const LdltLevelTables lt = pack_ldlt_level_tables(l);
-  lvl_pack.upload(lt.lvl_pack);
-  col_lvl_pack.upload(lt.col_lvl_pack);
-  bwd_range.upload(lt.bwd_range);
-  n_rounds = l.n_rounds;
-}
-
-LdltDev LdltPlanDevice::view() const {
-  LdltDev L{};
-  L.tasks = tasks.p;
-  L.ent_src = ent_src.p;
-  L.ent_flags = ent_flags.p;
-  L.ent_col = ent_col.p;
-  L.ent_out = ent_out.p;
-  L.ent_pair_ptr = ent_pair_ptr.p;
-  L.ent_contrib_ptr = ent_contrib_ptr.p;
-  L.contrib_idx = contrib_idx.p;
-  L.ext_dst = ext_dst.p;
-  L.lvl_ptr = lvl_ptr.p;
-  L.pairs = pairs.p;
-  L.col_perm = col_perm.p;
-  L.col_lvl_ptr = col_lvl_ptr.p;
-  L.fwd_ptr = fwd_ptr.p;
-  L.fwd_contrib_ptr = fwd_contrib_ptr.p;
-  L.scontrib_idx = scontrib_idx.p;
-  L.fwd_items = fwd_items.p;
-  L.sext_ptr = sext_ptr.p;
-  L.sext_dst = sext_dst.p;
-  L.sext_items = sext_items.p;
-  L.bwd_ptr = bwd_ptr.p;
-  L.bwd_items = bwd_items.p;
-  L.perm = perm.p;
-  L.round_ptr = round_ptr.p;
-  L.n_rounds = n_rounds;
-  L.sn_desc = sn_desc.p;
-  L.sn_lvl_ptr = sn_lvl_ptr.p;
-  L.col_sn = col_sn.p;
-  L.lvl_pack = lvl_pack.p;
-  L.col_lvl_pack = col_lvl_pack.p;
-  L.bwd_range = bwd_range.p;
-  L.clock_task = 0xffffffffu;
-  return L;
-}
-
 // The phases below run in this order; every upload() of theirs goes into the system's arena — a few allocations, one
 // copy each (commit at the end) — so their order is also the order of the plan arrays in memory.
 DeviceNlp::DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l, int batch,
                      int device, const Switches& sw)
-    : m_s_ref(s), m_k_ref(k), m_l_ref(l), m_batch(batch), m_device(device), m_sw(sw) {
+    : m_s_ref(s), m_k_ref(k), m_l_ref(l), m_batch(batch), m_device(device), m_sw(sw),
+      m_ldlt(l, k, batch, DeviceLdlt::Shared{m_stream, m_mode, m_plan, m_sw, m_cus, m_h_seq, s.reduces.size()}) {
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
     throw std::runtime_error("slpx: no HIP device available (the product path has no CPU fallback)");
@@ -611,9 +534,10 @@ DeviceNlp::DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l,
   upload_tapes();
   lap("  upload: tapes (+ code objects)");
   raise_lds_limits();
+  m_ldlt.raise_lds_limits();
   upload_kkt_plan();
   lap("  upload: kernel attributes, KKT plan");
-  upload_ldlt_plan();
+  m_ldlt.upload_plan();
   lap("  upload: LDLT plan");
   // (the host copies of the inline plans live until the task images are packed from them)
   const InlineKkt inline_kkt = m_mode.fuse_kkt ? build_inline_kkt(s, k, l) : InlineKkt{};
@@ -626,12 +550,12 @@ DeviceNlp::DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l,
   MfImages mf_images;
   mf_images.declined = "not asked for";
   if (wants_multifrontal(m_mode, m_plan, m_sw)) mf_images = build_mf_images(l, inline_kkt, inline_backsub);
-  upload_mf(mf_images);
+  m_ldlt.upload_mf(mf_images);
   lap("    images: multifrontal task images");
   lap("  upload: inline KKT / back-substitution / multifrontal images");
-  alloc_dense_buffers();  // (before the armed buffers, whose uploads follow its pattern arrays in the arena)
+  m_ldlt.alloc_dense_buffers();  // (before the armed buffers, whose uploads follow its pattern arrays in the arena)
   alloc_value_buffers();
-  arm_handover_buffers();
+  m_ldlt.arm_handover_buffers();
   alloc_interleaved_buffers();
   alloc_pinned();
   DeviceArena::current() = nullptr;
@@ -650,18 +574,6 @@ void DeviceNlp::choose_initial_modes() {
   m_mode = initial_launch_modes(m_batch, m_plan, m_s_ref.reduces.size(), m_cus, m_sw);
 }
 
-int DeviceNlp::workgroups_per_cu(const void* kernel, int threads, size_t lds, size_t* static_lds) {
-  int per_cu = 0;
-  SLPX_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  if (static_lds != nullptr) {
-    hipFuncAttributes attr{};
-    SLPX_HIP_CHECK(hipFuncGetAttributes(&attr, kernel));
-    *static_lds = std::max(*static_lds, attr.sharedSizeBytes);
-  }
-  SLPX_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds));
-  return per_cu;
-}
-
 void DeviceNlp::upload_tapes() {
   const NlpStructure& s = m_s_ref;
   m_full.upload(s.full, m_batch, static_cast<uint32_t>(s.n), m_mode.chain_mode);
@@ -674,11 +586,7 @@ void DeviceNlp::raise_lds_limits() {
   for (const void* fn : {reinterpret_cast<const void*>(&tape_sweep_lds_kernel<256, true>),
                          reinterpret_cast<const void*>(&tape_sweep_lds_kernel<256, false>),
                          reinterpret_cast<const void*>(&tape_sweep_lds_kernel<64, true>),
-                         reinterpret_cast<const void*>(&tape_sweep_lds_kernel<64, false>),
-                         reinterpret_cast<const void*>(&ldlt_factor_kernel<256>),
-                         reinterpret_cast<const void*>(&ldlt_factor_kernel<1024>),
-                         reinterpret_cast<const void*>(&ldlt_fwd_kernel),
-                         reinterpret_cast<const void*>(&ldlt_bwd_kernel)})
+                         reinterpret_cast<const void*>(&tape_sweep_lds_kernel<64, false>)})
     SLPX_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 }
 
@@ -687,17 +595,8 @@ void DeviceNlp::upload_kkt_plan() {
   m_kdev = m_kplan.view();
 }
 
-void DeviceNlp::upload_ldlt_plan() {
-  m_lplan.upload(m_l_ref);
-  m_ldev = m_lplan.view();
-  // the round counters of the single-launch kernels ([2][batch][n_rounds]), cleared once here
-  std::vector<unsigned int> zero(2 * static_cast<size_t>(m_batch) * std::max(1, m_l_ref.n_rounds), 0u);
-  m_fround_cnt.upload(zero);
-  m_bround_cnt.upload(zero);
-}
-
 void DeviceNlp::upload_inline_kkt(const InlineKkt& ik) {
-  m_factor_lds_inline = ik.factor_lds;
+  m_ldlt.set_factor_lds_inline(ik.factor_lds);
   if (!ik.ok) return;
   m_ent_vsrc.upload(ik.vsrc);
   m_kkt_terms.upload(ik.terms);
@@ -705,36 +604,15 @@ void DeviceNlp::upload_inline_kkt(const InlineKkt& ik) {
 }
 
 void DeviceNlp::upload_inline_backsub(const InlineBacksub& ib) {
-  m_solve_lds_inline = ib.solve_lds;
+  m_ldlt.set_solve_lds_inline(ib.solve_lds);
   if (!ib.ok) return;
   m_bs_plan.upload(ib.plan);
   m_bs_task_plan.upload(ib.task_plan);
 }
 
-// the dense branch: dim x dim per problem, the pattern of lhs for the scatter; LDS: column k and its scaled copy
-void DeviceNlp::alloc_dense_buffers() {
-  if (!m_mode.dense) return;
-  const KktPlan& k = m_k_ref;
-  const LdltPlan& l = m_l_ref;
-  const size_t B = static_cast<size_t>(m_batch);
-  m_dense_A.alloc(B * static_cast<size_t>(l.n) * l.n);
-  m_dense_colptr.upload(k.lhs.colptr);
-  m_dense_rowidx.upload(k.lhs.rowidx);
-  m_dense_lds = 16u * static_cast<uint32_t>(l.n) + 320u;
-  if (m_mode.dense_pivoted) {
-    m_dense_trans.alloc(B * static_cast<size_t>(l.n));
-    m_dense_trans.zero();
-    SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_dense_pivoted_factor_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  }
-  if (m_dense_lds > 160u * 1024u) throw std::runtime_error("slpx: the dense factorization holds two columns in LDS: at most 10 000 rows");
-  SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_dense_factor_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_dense_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-}
-
 void DeviceNlp::alloc_value_buffers() {
   const NlpStructure& s = m_s_ref;
   const KktPlan& k = m_k_ref;
-  const LdltPlan& l = m_l_ref;
   const size_t B = static_cast<size_t>(m_batch);
   m_in.alloc(B * s.n_inputs());
   m_in.zero();
@@ -745,83 +623,28 @@ void DeviceNlp::alloc_value_buffers() {
   m_mu.alloc(B);
   m_lhs.alloc(B * k.lhs.nnz());
   m_rhs.alloc(B * k.dim);
-  m_p.alloc(B * k.dim);
   m_ps.alloc(B * std::max(1, s.m_i));
   m_pz.alloc(B * std::max(1, s.m_i));
-  m_D.alloc(B * l.n);
-  m_Lx.alloc(B * std::max<int64_t>(1, l.nnzL));
-  m_contrib.alloc(B * std::max<uint32_t>(1, l.n_contrib));
-  m_scontrib.alloc(B * std::max<uint32_t>(1, l.n_scontrib));
-  m_zv.alloc(B * l.n);
-  m_xg.alloc(B * l.n);
   const uint64_t scratch = std::max(s.full.global_scratch_doubles, s.values.global_scratch_doubles);
   m_scratch.alloc(B * std::max<uint64_t>(1, scratch));
-  // Every value buffer starts at zero, not at whatever the allocator hands back: the right-hand
-  // side rides in the factorization as an extra row, and compute() may come before any rhs was
-  // set (RegularizedLDLT::compute(lhs), regularized_ldlt.hpp:72) — recycled memory of an earlier
-  // system can hold the hand-over sentinel (a NaN pattern: the armed slots below), a NaN keeps
-  // its payload through arithmetic, and an update block that IS the sentinel is never taken
-  // (seen on the pair-list kernels: the fourth solver of a process spinning to its time-out).
-  for (DevBuf<double>* buf : {&m_V, &m_s, &m_y, &m_z, &m_mu, &m_lhs, &m_rhs, &m_p, &m_ps, &m_pz, &m_D, &m_Lx, &m_scontrib, &m_zv})
-    buf->zero();
+  // every value buffer starts at zero, the solver's too (DeviceLdlt::alloc_value_buffers says why)
+  for (DevBuf<double>* buf : {&m_V, &m_s, &m_y, &m_z, &m_mu, &m_lhs, &m_rhs, &m_ps, &m_pz}) buf->zero();
+  m_ldlt.alloc_value_buffers();
   SLPX_HIP_CHECK(hipDeviceSynchronize());  // (the memsets ran on the null stream, the kernels will not)
 }
 
-// What the kernels hand over through the data starts out armed (kSlotEmpty), the counters cleared.
-void DeviceNlp::arm_handover_buffers() {
-  const LdltPlan& l = m_l_ref;
-  const size_t B = static_cast<size_t>(m_batch);
-  const double empty = std::bit_cast<double>(kSlotEmpty);
-  if (m_mode.slot_handoff) {
-    const std::vector<double> armed(m_contrib.n, empty);
-    SLPX_HIP_CHECK(hipMemcpy(m_contrib.p, armed.data(), armed.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
-  // the backward solve's hand-over through the data (ldlt_kernels.h: slot_read): two buffers of
-  // x, both armed
-  if (m_mode.xg_by_data) {
-    const std::vector<double> armed(B * l.n, empty);
-    m_xg.upload(armed);
-    m_xg2.upload(armed);
-  }
-  // two inertia-counter buffers (see factor()), both cleared once here
-  m_stats.upload(std::vector<LdltStats>(2 * B, LdltStats{0, 0, 0, 0, 0x7ff0000000000000ull}));
-}
-
-// batch-interleaved LDLT (ldlt_il_kernels.h): [chunk of 64 problems][index][lane]
+// batch-interleaved LDLT: the system where its kernels read it, [chunk of 64 problems][index][lane]
 void DeviceNlp::alloc_interleaved_buffers() {
   if (!m_mode.il) return;
-  const KktPlan& k = m_k_ref;
-  const LdltPlan& l = m_l_ref;
-  const size_t B = static_cast<size_t>(m_batch);
-  const size_t C = (B + 63) / 64, W = 64;
-  m_lhs_il.alloc(C * k.lhs.nnz() * W);
-  m_rhs_il.alloc(C * l.n * W);
-  m_Lx_il.alloc(C * std::max<int64_t>(1, l.nnzL) * W);
-  m_D_il.alloc(C * l.n * W);
-  m_contrib_il.alloc(C * std::max<uint32_t>(1, l.n_contrib) * W);
-  m_scontrib_il.alloc(C * std::max<uint32_t>(1, l.n_scontrib) * W);
-  m_zv_il.alloc(C * l.n * W);
-  m_xg_il.alloc(C * l.n * W);
-  m_stats_part.alloc(l.tasks.size() * B);
-  for (auto* buf : {&m_Lx_il, &m_D_il, &m_zv_il, &m_xg_il, &m_contrib_il, &m_scontrib_il}) buf->zero();
-  const IlMeta im = pack_il_meta(l);
-  m_il_meta.upload(im.meta);
-  m_il_meta_off.upload(im.meta_off);
-  m_il_factor_lds = im.factor_lds;
-  m_il_solve_lds = im.solve_lds;
-  if (m_il_factor_lds > 160u * 1024u)
-    throw std::runtime_error("slpx: an LDLT task does not fit the interleaved kernel's LDS (LdltOptions::task_entries)");
-  SLPX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ldlt_factor_il_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  SLPX_HIP_CHECK(hipDeviceSynchronize());
+  const size_t C = (static_cast<size_t>(m_batch) + 63) / 64, W = 64;
+  m_lhs_il.alloc(C * m_k_ref.lhs.nnz() * W);
+  m_rhs_il.alloc(C * m_l_ref.n * W);
+  m_ldlt.alloc_interleaved_buffers();
 }
 
-// what the host and the kernels pass each other through pinned memory: (delta, gamma), the counters, the sequence word
+// the sequence word the publishing kernels bump and the host spins on (after the solver's pinned words)
 void DeviceNlp::alloc_pinned() {
-  const size_t B = static_cast<size_t>(m_batch);
-  SLPX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&m_h_reg), 2 * static_cast<size_t>(std::max<int>(B, 6)) * sizeof(double)));  // (B = 1: a twin attempt's second pair)
-  if (B > 8) m_reg_dev.alloc(2 * B);
-  SLPX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&m_h_stats), static_cast<size_t>(std::max<int>(B, 2)) * sizeof(LdltStats)));
+  m_ldlt.alloc_pinned();
   unsigned long long* seq = nullptr;
   SLPX_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&seq), sizeof(unsigned long long)));
   *seq = 0;
@@ -831,8 +654,6 @@ void DeviceNlp::alloc_pinned() {
 }
 
 DeviceNlp::~DeviceNlp() {
-  if (m_h_reg) (void)hipHostFree(m_h_reg);
-  if (m_h_stats) (void)hipHostFree(m_h_stats);
   if (m_h_seq) (void)hipHostFree(const_cast<unsigned long long*>(m_h_seq));
   if (m_ipm_host) (void)hipHostFree(m_ipm_host);
   if (m_ipm_ctl_host) (void)hipHostFree(m_ipm_ctl_host);
@@ -985,7 +806,7 @@ void DeviceNlp::sweep_full_for_step() {
   // (and its workgroups are single waves: g-fold's sweep, 256-thread workgroups interpreting its packs of
   // rows, shares the chip badly with the step kernel — 13.3 k steps/s chained against 13.6 k)
   const bool one_kernel = t.n_bodies > 0 && t.n_large == 0 && t.n_global == 0 && (t.tmpl_threads == 64 || t.tmpl_wide_for_chain);
-  if (!m_mode.chain_on || !one_kernel || !m_mode.mf || m_batch != 1 || xg_other() == nullptr || !m_mode.fuse_solve) {
+  if (!m_mode.chain_on || !one_kernel || m_batch != 1 || !m_ldlt.step_possible() || !m_mode.fuse_solve) {
     sweep_full(/*with_reduce=*/false);
     return;
   }
@@ -1099,47 +920,6 @@ static inline int grid_for(int work, int block, int cap = 2048) {
   return std::max(1, std::min((work + block - 1) / block, cap));
 }
 
-constexpr int kFactorThreadsSingle = 1024;
-// The multifrontal step (ldlt_mf_kernels.h) with the task images of build_mf_images: co-residency of every task's
-// workgroup, then the uploads.
-void DeviceNlp::upload_mf(const MfImages& im) {
-  const LdltPlan& l = m_l_ref;
-  MfFit fit;
-  fit.declined = im.declined != nullptr;
-  fit.lds_bytes = im.lds;
-  int per_cu[2] = {0, 0};  // at 1024, at 512 threads
-  if (!fit.declined && im.lds <= 160u * 1024u) {
-    auto fp = [](auto kernel) { return reinterpret_cast<const void*>(kernel); };
-    const bool mfma = l.mf_n_mfma > 0;
-    auto both = [&](const void* chained, const void* plain, int threads) {
-      return std::min(workgroups_per_cu(chained, threads, im.lds, &fit.static_lds_bytes), workgroups_per_cu(plain, threads, im.lds, &fit.static_lds_bytes));
-    };
-    per_cu[0] = mfma ? both(fp(&ldlt_mf_step_kernel<1024, true, true>), fp(&ldlt_mf_step_kernel<1024, true, false>), 1024)
-                     : both(fp(&ldlt_mf_step_kernel<1024, false, true>), fp(&ldlt_mf_step_kernel<1024, false, false>), 1024);
-    per_cu[1] = mfma ? both(fp(&ldlt_mf_step_kernel<512, true, true>), fp(&ldlt_mf_step_kernel<512, true, false>), 512)
-                     : both(fp(&ldlt_mf_step_kernel<512, false, true>), fp(&ldlt_mf_step_kernel<512, false, false>), 512);
-    fit.step = Residency{static_cast<size_t>(per_cu[0]) * m_cus, static_cast<size_t>(per_cu[1]) * m_cus};
-    if (m_sw.mf_solve)
-      fit.solve = Residency{static_cast<size_t>(workgroups_per_cu(fp(&ldlt_mf_solve_kernel<1024>), 1024, im.lds)) * m_cus,
-                            static_cast<size_t>(workgroups_per_cu(fp(&ldlt_mf_solve_kernel<512>), 512, im.lds)) * m_cus};
-  }
-  choose_multifrontal(m_mode, m_plan, m_reduces.n, fit, m_sw);
-  if (fit.declined) return;
-  if (std::getenv("SLPX_LDLT_VERBOSE"))
-    std::fprintf(stderr, "ldlt multifrontal step: %zu tasks, LDS %u bytes (static %zu), images %zu bytes, %d workgroup(s) of %d threads per CU x %d CUs%s\n",
-                 l.tasks.size(), im.lds, fit.static_lds_bytes, 16 * im.image.size(), per_cu[m_mode.mf_threads == 1024 ? 0 : 1], m_mode.mf_threads, m_cus,
-                 m_mode.mf ? "" : ": NOT resident at once");
-  if (!m_mode.mf) return;
-  m_mf_tasks.upload(l.mf_tasks);
-  m_mf_fronts.upload(l.mf_fronts);
-  m_mf_image.upload(im.image);
-  m_mf_image_stride16 = im.stride16;
-  m_mf_image_desc.upload(im.desc);
-  m_mf_contrib.upload(std::vector<double>(std::max<uint32_t>(1, l.mf_n_contrib), std::bit_cast<double>(kSlotEmpty)));
-  if (m_exit_cnt.n == 0) m_exit_cnt.upload(std::vector<unsigned int>(1, 0u));
-  m_mf_lds = im.lds;
-}
-
 // lhs / rhs of the CURRENT state into memory, if the last step did without them
 void DeviceNlp::materialize_kkt() {
   if (m_kkt_pending) {  // the factorization that was to evaluate the system never came
@@ -1157,17 +937,12 @@ void DeviceNlp::materialize_kkt() {
 // is not known, so the next factorization transposes again
 void DeviceNlp::materialize_batch_major() {
   if (!m_mode.il) return;
-  const int C = (m_batch + 63) / 64;
   if (m_lhs_in_il) {
-    const int nnz = m_kdev.nnz_lhs;
-    hipLaunchKernelGGL(il_scatter_kernel, dim3((nnz + 63) / 64, C), dim3(256), 0, m_stream, m_lhs_il.p, nnz, m_lhs.p,
-                       static_cast<long long>(nnz), m_batch);
+    m_ldlt.to_batch_major(m_lhs_il.p, m_kdev.nnz_lhs, m_lhs.p);
     m_lhs_in_il = false;
   }
   if (m_rhs_in_il) {
-    const int n = m_kdev.dim;
-    hipLaunchKernelGGL(il_scatter_kernel, dim3((n + 63) / 64, C), dim3(256), 0, m_stream, m_rhs_il.p, n, m_rhs.p,
-                       static_cast<long long>(n), m_batch);
+    m_ldlt.to_batch_major(m_rhs_il.p, m_kdev.dim, m_rhs.p);
     m_rhs_in_il = false;
   }
   SLPX_HIP_CHECK(hipGetLastError());
@@ -1213,7 +988,7 @@ void DeviceNlp::build_kkt(bool with_reduce) {
     SLPX_HIP_CHECK(hipGetLastError());
     return;
   }
-  if (m_defer_kkt) {  // evaluated inside the factorization's launch (enqueue_factor)
+  if (m_defer_kkt) {  // evaluated inside the factorization's launch (take_kkt_fuse)
     m_kkt_pending = with_reduce ? 2 : 1;
     m_lhs_stale = m_rhs_stale = true;
     return;
@@ -1261,23 +1036,6 @@ int DeviceNlp::debug_tmpl_clocks(unsigned long long* out, int blocks) {
 void DeviceNlp::debug_tape_clocks(unsigned long long* out16) {
   SLPX_HIP_CHECK(hipStreamSynchronize(m_stream));
   SLPX_HIP_CHECK(hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_tape_clocks), 16 * sizeof(unsigned long long)));
-}
-
-void DeviceNlp::debug_ldlt_clocks(unsigned int next_round, unsigned long long* out24) {
-  SLPX_HIP_CHECK(hipStreamSynchronize(m_stream));
-#ifdef SLPX_MF_CLOCKS
-  if ((next_round >> 16) == 0xffffu) {  // (the instrumented build: the slots of task (next_round & 0xffff) in the last launch)
-    SLPX_HIP_CHECK(hipMemcpyFromSymbol(out24, HIP_SYMBOL(g_mf_clocks), 24 * sizeof(unsigned long long),
-                                       24 * sizeof(unsigned long long) * (next_round & 0xffffu)));
-    return;
-  }
-#endif
-  SLPX_HIP_CHECK(hipMemcpyFromSymbol(out24, HIP_SYMBOL(g_ldlt_clocks), 24 * sizeof(unsigned long long)));
-  // (bits 8 and up: which task of the round, 0 = its first)
-  const unsigned int round = next_round & 0xffu, within = next_round >> 8;
-  m_ldev.clock_task = 0xffffffffu;
-  if (round < static_cast<unsigned int>(m_l_ref.n_rounds) && m_l_ref.round_ptr[round] + within < m_l_ref.round_ptr[round + 1])
-    m_ldev.clock_task = m_l_ref.round_ptr[round] + within;
 }
 
 void DeviceNlp::refresh_params(const Graph& g) {
@@ -1345,25 +1103,6 @@ void DeviceNlp::build_rhs() {
   SLPX_HIP_CHECK(hipGetLastError());
 }
 
-// Control traffic of one factorization attempt is kept off the critical path: (δ, γ) of
-// every problem travel in ONE async copy from pinned memory (δ = NaN marks a problem the
-// policy loop is done with), and the inertia counters are double-buffered — the launch of
-// attempt k clears the buffer attempt k+1 will accumulate into — so no reset kernel runs.
-// Control traffic of one factorization attempt is kept off the critical path: the kernels
-// read (δ, γ) straight from pinned host memory (δ = NaN marks a problem the policy loop is
-// done with), and the inertia counters are double-buffered — the launch of attempt k
-// clears the buffer attempt k+1 will accumulate into — so no copy and no reset kernel run.
-// The host only rewrites m_h_reg after read_stats() has synchronized.
-void DeviceNlp::write_reg(const std::vector<double>& delta, const std::vector<double>& gamma,
-                          const std::vector<uint8_t>& active) {
-  for (int b = 0; b < m_batch; ++b) {
-    m_h_reg[2 * b] = active[b] ? delta[b] : std::numeric_limits<double>::quiet_NaN();
-    m_h_reg[2 * b + 1] = gamma[b];
-    if (active[b]) note_factored(b, delta[b], gamma[b]);
-  }
-}
-
-
 // the system evaluated inside the factorization's launch, if a build_kkt_for_step() asked for it
 KktFuse DeviceNlp::kkt_fuse_for(int kkt_mode) const {
   KktFuse f;
@@ -1397,7 +1136,7 @@ KktFuse DeviceNlp::take_kkt_fuse() {
   return f;
 }
 
-BacksubFuse DeviceNlp::backsub_fuse(const LdltStats* publish) {
+BacksubFuse DeviceNlp::backsub_fuse() {
   BacksubFuse f;
   f.on = 1;
   f.V = m_V.p;
@@ -1409,509 +1148,133 @@ BacksubFuse DeviceNlp::backsub_fuse(const LdltStats* publish) {
   f.off_ci = m_kdev.off_ci;
   f.plan = reinterpret_cast<const uint4*>(m_bs_plan.p);
   f.task_plan = m_bs_task_plan.p;
-  f.stats_src = publish;
-  f.stats_host = m_h_stats;
   f.seq_dev = m_seq_dev.p;
   f.seq_host = m_h_seq;
   return f;
 }
 
-void DeviceNlp::enqueue_factor(int parity, hipStream_t stream) {
-  const LdltPlan& l = m_l_ref;
-  if (!m_kkt_pending) materialize_kkt();  // e.g. a second attempt after one that evaluated the system in place
-  LdltStats* cur = m_stats.p + static_cast<size_t>(parity) * m_batch;
-  LdltStats* next = m_stats.p + static_cast<size_t>(parity ^ 1) * m_batch;
-  const long long lxs = static_cast<long long>(std::max<int64_t>(1, l.nnzL));
-  const int cs = static_cast<int>(std::max<uint32_t>(1, l.n_contrib));
-  // a handful of workgroups read (δ, γ) straight from pinned host memory; the tens of
-  // thousands of a big batch would each pay a PCIe round trip, so those get a device copy
-  const double* reg = m_h_reg;
-  if (m_batch > 8) {
-    // (only when the values changed: consecutive steps of a batch mostly make the same first attempt, and the copy is a
-    // launch of its own in front of every factorization — 6 us of a 64-problem step's 280, 21 us of a 512-problem step's)
-    const size_t count = 2 * static_cast<size_t>(m_batch);
-    if (m_reg_shadow.size() != count || std::memcmp(m_reg_shadow.data(), m_h_reg, count * sizeof(double)) != 0) {
-      m_reg_shadow.assign(m_h_reg, m_h_reg + count);
-      SLPX_HIP_CHECK(hipMemcpyAsync(m_reg_dev.p, m_h_reg, count * sizeof(double), hipMemcpyHostToDevice, stream));
-    }
-    reg = m_reg_dev.p;
-  }
-  if (m_mode.dense) {
-    if (m_mode.dense_pivoted)
-      hipLaunchKernelGGL(ldlt_dense_pivoted_factor_kernel, dim3(m_batch), dim3(kDenseThreads), m_dense_lds, stream, l.n, l.n_dec,
-                         m_dense_colptr.p, m_dense_rowidx.p, m_kdev.nnz_lhs, m_lhs.p, reg, m_dense_A.p, m_dense_trans.p, m_D.p, cur, next);
-    else
-    hipLaunchKernelGGL(ldlt_dense_factor_kernel, dim3(m_batch), dim3(kDenseThreads), m_dense_lds, stream, l.n, l.n_dec,
-                       m_dense_colptr.p, m_dense_rowidx.p, m_kdev.nnz_lhs, m_lhs.p, reg, m_dense_A.p, m_D.p, m_Lx.p, lxs, cur, next);
-    SLPX_HIP_CHECK(hipGetLastError());
-    return;
-  }
-  if (m_mode.il) {
-    const int C = (m_batch + 63) / 64;
-    const int nnz = m_kdev.nnz_lhs;
-    // (the assembly kernels wrote the interleaved arrays themselves unless somebody else made lhs / rhs)
-    if (!m_lhs_in_il)
-      hipLaunchKernelGGL(il_gather_kernel, dim3((nnz + 63) / 64, C), dim3(256), 0, stream, m_lhs.p,
-                         static_cast<long long>(nnz), nnz, m_lhs_il.p, m_batch);
-    if (!m_rhs_in_il)
-      hipLaunchKernelGGL(il_gather_kernel, dim3((l.n + 63) / 64, C), dim3(256), 0, stream, m_rhs.p,
-                         static_cast<long long>(l.n), l.n, m_rhs_il.p, m_batch);
-    for (int r = 0; r < l.n_rounds; ++r) {
-      const uint32_t nt = l.round_ptr[r + 1] - l.round_ptr[r];
-      hipLaunchKernelGGL(ldlt_factor_il_kernel, dim3(nt, kIlRowsPerChunk * C), dim3(kIlFactorThreads), m_il_factor_lds, stream, m_ldev,
-                         l.round_ptr[r], m_lhs_il.p, nnz, m_rhs_il.p, l.n, reg, m_Lx_il.p, lxs, m_D_il.p,
-                         m_contrib_il.p, cs, m_zv_il.p, m_stats_part.p, m_batch, m_il_meta.p, m_il_meta_off.p);
-    }
-    hipLaunchKernelGGL(ldlt_stats_il_kernel, dim3(m_batch), dim3(64), 0, stream, m_stats_part.p,
-                       static_cast<int>(l.tasks.size()), reg, cur, m_batch);
-    m_il_outputs_stale = true;
-  } else if (m_mode.single_launch) {
-    KktFuse f = take_kkt_fuse();
-    // every round in one launch; tasks wait on device-side round counters
-    hipLaunchKernelGGL(ldlt_factor_kernel<kFactorThreadsSingle>,
-                       dim3(static_cast<uint32_t>(l.tasks.size()) + static_cast<uint32_t>(f.n_blocks), m_batch),
-                       dim3(kFactorThreadsSingle), f.inline_kkt ? m_factor_lds_inline : l.factor_lds_bytes, stream,
-                       m_ldev, 0u, m_lhs.p, m_kdev.nnz_lhs, reg, m_Lx.p, lxs, m_D.p, l.n, m_contrib.p, cs, cur, next,
-                       m_rhs.p, m_zv.p, m_fround_cnt.p, m_mode.slot_handoff ? 1 : 0, f);
-  } else {
-    for (int r = 0; r < l.n_rounds; ++r) {
-      const uint32_t nt = l.round_ptr[r + 1] - l.round_ptr[r];
-      hipLaunchKernelGGL(ldlt_factor_kernel<256>, dim3(nt, m_batch), dim3(256), l.factor_lds_bytes, stream,
-                         m_ldev, l.round_ptr[r], m_lhs.p, m_kdev.nnz_lhs, reg, m_Lx.p, lxs, m_D.p,
-                         l.n, m_contrib.p, cs, cur, r == 0 ? next : nullptr, m_rhs.p, m_zv.p,
-                         static_cast<unsigned int*>(nullptr), 0, KktFuse{});
-    }
-  }
-  SLPX_HIP_CHECK(hipGetLastError());
-}
-
 void DeviceNlp::factor(const std::vector<double>& delta, const std::vector<double>& gamma,
                        const std::vector<uint8_t>& active) {
-  write_reg(delta, gamma, active);
-  m_twin_mode = 0;
-  m_stats_cur ^= 1;
-  m_stats_in_host = false;
-  enqueue_factor(m_stats_cur, m_stream);
+  if (!m_kkt_pending) materialize_kkt();  // e.g. a second attempt after one that evaluated the system in place
+  m_ldlt.factor(delta, gamma, active, system(), m_ldlt.factor_evaluates_inline() ? take_kkt_fuse() : KktFuse{});
+}
+
+// What rides in a launch of the step kernel made now: the system or its evaluation in place, the back-substitution,
+// the chain link of a chained step (sweep_full_for_step) and the gate of a step enqueued ahead.
+LdltStepRiders DeviceNlp::step_riders(const KktFuse& f, bool chained) {
+  LdltStepRiders r;
+  r.kkt = f;
+  r.backsub = backsub_fuse();
+  r.lhs = m_lhs.p;
+  r.rhs = m_rhs.p;
+  if (chained) {
+    r.chain = m_chain.p;
+    r.wait_step = m_chain_sweep_wgs;  // (every workgroup of the chained sweeps so far, this step's included)
+  }
+  r.this_step = m_chain_seq;
+  if (m_gate_next_step) {  // (one launch: the step enqueued before the iteration in front of it was decided)
+    r.gate = m_ipm_gate.p;
+    m_gate_next_step = false;
+  }
+  return r;
 }
 
 void DeviceNlp::factor_solve_publish(const std::vector<double>& delta, const std::vector<double>& gamma,
                                      const std::vector<uint8_t>& active) {
-  const bool mf_now = m_mode.mf && xg_other() != nullptr;
-  if (!m_mode.fuse_solve || !mf_now) {
+  if (!m_mode.fuse_solve || !m_ldlt.step_possible()) {
     factor(delta, gamma, active);
     solve_backsub_publish();
     return;
   }
-  write_reg(delta, gamma, active);
-  m_twin_mode = 0;
-  m_stats_cur ^= 1;
-  enqueue_factor_solve(m_stats_cur);
-  m_stats_seq = ++m_seq_expected;
-  m_stats_in_host = true;
+  if (!m_kkt_pending) materialize_kkt();
+  const KktFuse f = take_kkt_fuse();
+  // a chained step: the kernel variant that waits for its sweep itself and whose last workgroup tells the next step's
+  // sweep; the main stream stays "untouched" by a step's own launches
+  const bool chained = m_stream.tape_pending;
+  const unsigned int workgroups = m_ldlt.step(delta, gamma, active, step_riders(f, chained));
+  if (chained) m_chain_step_wgs += workgroups;  // (what the next chained sweep waits for in chain[48])
+  m_stream.tape_pending = false;
+  m_last_step_chained = chained;
+  m_ldlt.stats_handed_to_host(++m_seq_expected);
 }
 
-// ---- twin attempt (ldlt_mf_twin_kernel) ----
-bool DeviceNlp::twin_available() {
-  if (m_mode.twin != 0) return m_mode.twin > 0 && m_mode.mf && xg_other() != nullptr;
-  const LdltPlan& l = m_l_ref;
-  auto fp = [](auto kernel) { return reinterpret_cast<const void*>(kernel); };
-  int per_cu[2] = {0, 0};  // at 1024, at 512 threads
-  const bool measure = twin_worth_measuring(m_mode, m_batch, m_sw);
-  if (measure) {
-    if (m_mode.mf_threads == 1024) per_cu[0] = workgroups_per_cu(fp(&ldlt_mf_twin_kernel<1024, false>), 1024, m_mf_lds);
-    per_cu[1] = workgroups_per_cu(fp(&ldlt_mf_twin_kernel<512, false>), 512, m_mf_lds);
+// ---- twin attempt (DeviceLdlt::step_twin) ----
+bool DeviceNlp::twin_ready() {
+  if (!m_ldlt.twin_available()) return false;
+  if (m_ps_tw.n == 0) {
+    for (auto [tw, first] : {std::pair{&m_ps_tw, &m_ps}, {&m_pz_tw, &m_pz}}) {
+      tw->alloc(std::max<size_t>(1, first->n));
+      tw->zero();
+    }
+    SLPX_HIP_CHECK(hipDeviceSynchronize());  // (the memsets ran on the null stream)
   }
-  choose_twin(m_mode, m_batch, m_plan, m_reduces.n, Residency{static_cast<size_t>(per_cu[0]) * m_cus, static_cast<size_t>(per_cu[1]) * m_cus}, m_sw);
-  if (measure && std::getenv("SLPX_LDLT_VERBOSE"))
-    std::fprintf(stderr, "ldlt twin attempt: 2 x %zu tasks, %d workgroup(s) of %d threads per CU x %d CUs%s\n", l.tasks.size(),
-                 per_cu[m_mode.twin_threads == 1024 ? 0 : 1], m_mode.twin_threads, m_cus, m_mode.twin > 0 ? "" : ": NOT resident at once");
-  if (m_mode.twin < 0) return false;
-  for (auto [tw, first] : {std::pair{&m_Lx_tw, &m_Lx}, {&m_D_tw, &m_D}, {&m_zv_tw, &m_zv}, {&m_p_tw, &m_p}, {&m_ps_tw, &m_ps}, {&m_pz_tw, &m_pz}}) {
-    tw->alloc(std::max<size_t>(1, first->n));
-    tw->zero();
-  }
-  m_mf_contrib_tw.upload(std::vector<double>(std::max<size_t>(1, m_mf_contrib.n), std::bit_cast<double>(kSlotEmpty)));
-  const std::vector<double> armed(static_cast<size_t>(l.n), std::bit_cast<double>(kSlotEmpty));
-  m_xg_tw.upload(armed);
-  m_xg2_tw.upload(armed);
-  m_stats_tw.upload(std::vector<LdltStats>(2, LdltStats{0, 0, 0, 0, 0x7ff0000000000000ull}));
-  SLPX_HIP_CHECK(hipDeviceSynchronize());  // (the memsets ran on the null stream)
   return true;
 }
 
-// One launch of the multifrontal step kernel (twin_mode != 0: two attempts, ldlt_mf_twin_kernel) with the buffer
-// roles, parities and chain numbers of this moment; book_mf_step() is what the launch changes on the host.
-void DeviceNlp::launch_mf_step(int twin_mode, const double* reg, const KktFuse& f, bool chained, const double* lhs2, const double* rhs2) {
-  const LdltPlan& l = m_l_ref;
-  m_solution_valid = true;
-  const int parity = m_stats_cur ^ 1;
-  LdltStats* cur = m_stats.p + static_cast<size_t>(parity);
-  LdltStats* next = m_stats.p + static_cast<size_t>(parity ^ 1);
-  BacksubFuse bf = backsub_fuse(cur);
-  MfDev md;
-  md.tasks = m_mf_tasks.p;
-  md.fronts = m_mf_fronts.p;
-  md.image = m_mf_image.p;
-  md.image_stride16 = m_mf_image_stride16;
-  md.image_desc = m_mf_image_desc.p;
-  md.n_tasks = static_cast<unsigned int>(l.tasks.size());
-  md.exit_cnt = m_exit_cnt.p;
-  // a chained step (sweep_full_for_step): the kernel variant that waits for its sweep itself and whose last
-  // workgroup tells the next step's sweep; the main stream stays "untouched" by a step's own launches
-  md.chain = chained ? m_chain.p : nullptr;
-  md.wait_step = chained ? m_chain_sweep_wgs : 0u;  // (every workgroup of the chained sweeps so far, this step's included)
-  md.this_step = m_chain_seq;
-  md.delta = reg[0];  // (by value: MfDev)
-  md.gamma = reg[1];
-  if (m_gate_next_step) {  // (one launch: the step enqueued before the iteration in front of it was decided)
-    md.gate = m_ipm_gate.p;
-    m_gate_next_step = false;
+void DeviceNlp::launch_twin(double delta0, double gamma0, double delta1, double gamma1, int mode, const KktFuse& f, const double* lhs2,
+                            const double* rhs2) {
+  LdltStepRiders r = step_riders(f, false);
+  r.ps2 = m_ps_tw.p;
+  r.pz2 = m_pz_tw.p;
+  r.lhs2 = lhs2;
+  r.rhs2 = rhs2;
+  MfRide ride;
+  if (m_ride_next) {
+    ride = ipm_take_ride();
+    r.ride = &ride;
+    r.gate = nullptr;  // (nothing in front of this launch is undecided: its own riding workgroups decide)
   }
-  const double* const reg_by_value = nullptr;
-  if (twin_mode != 0) {
-    const int tw_parity = m_stats_tw_cur ^ 1;
-    MfTwin tw;
-    tw.first_end = md.n_tasks + static_cast<unsigned int>(f.n_blocks);
-    tw.delta = reg[2];
-    tw.gamma = reg[3];
-    tw.Lx = m_Lx_tw.p;
-    tw.D = m_D_tw.p;
-    tw.contrib = m_mf_contrib_tw.p;
-    tw.zv = m_zv_tw.p;
-    tw.xg = m_xg_tw_parity ? m_xg2_tw.p : m_xg_tw.p;
-    tw.xg_next = m_xg_tw_parity ? m_xg_tw.p : m_xg2_tw.p;
-    tw.out = m_p_tw.p;
-    tw.ps = m_ps_tw.p;
-    tw.pz = m_pz_tw.p;
-    tw.stats = m_stats_tw.p + static_cast<size_t>(tw_parity);
-    tw.stats_next = m_stats_tw.p + static_cast<size_t>(tw_parity ^ 1);
-    tw.lhs = lhs2;
-    tw.rhs = rhs2;
-    MfRide ride;
-    size_t lds = m_mf_lds;
-    if (m_ride_next) {
-      // the error launch of the iteration before this step (ipm_ride_errors_in_next_step): its workgroups in front of
-      // the tasks, on the CURRENT buffers — the look-ahead iterate has been made current —, the tape's sums with them
-      m_ride_next = false;
-      const int work = std::max({m_kdev.n, m_kdev.m_e, m_kdev.m_i, 1});
-      const int blocks = grid_for(8 * work, kIpmErrThreads, 64);
-      if (m_ipm_partial.n < static_cast<size_t>(blocks) * kIpmErrQ) m_ipm_partial.alloc(static_cast<size_t>(256) * kIpmErrQ);
-      if (m_ipm_err_done.n == 0) m_ipm_err_done.upload(std::vector<unsigned int>(1, 0u));
-      const int n_sums = static_cast<int>(m_reduces.n);
-      m_ride_ticket += 1.0;
-      md.ride_verdict = m_ipm_ride_verdict.p;
-      md.ride_ticket = m_ride_ticket;
-      md.gate = nullptr;  // (nothing in front of this launch is undecided: its own riding workgroups decide)
-      ride.n_blocks = static_cast<uint32_t>(blocks + n_sums);
-      ride.K = m_kdev;
-      ride.V = m_V.p;
-      ride.x = m_in.p;
-      ride.s = m_s.p;
-      ride.y = m_y.p;
-      ride.z = m_z.p;
-      ride.scales = m_ipm_scales.p;
-      ride.nV = m_s_ref.nV;
-      ride.partial = m_ipm_partial.p;
-      IpmErrFinish& fin = ride.fin;
-      fin.n_err_blocks = blocks;
-      fin.n_total_blocks = blocks + n_sums;
-      fin.red = m_reduces.p;
-      fin.tape_scales = m_scales.p;
-      fin.Vw = m_V.p;
-      fin.done = m_ipm_err_done.p;
-      fin.out = &m_ipm_host[m_ride_slot].err_ahead;
-      fin.ctl = static_cast<IpmCtl*>(m_ipm_ctl_dev);
-      fin.dir = m_ipm_alpha.p;
-      fin.gate = m_ipm_gate.p;
-      fin.go_host = &m_ipm_host[m_ride_slot].go;
-      fin.check_host = &m_ipm_host[m_ride_slot].check;
-      fin.ride_verdict = m_ipm_ride_verdict.p;
-      fin.ride_ticket = m_ride_ticket;
-      lds = std::max<size_t>(lds, sizeof(double) * kIpmErrLdsDoubles);
-    }
-    const dim3 grid(2u * md.n_tasks + static_cast<uint32_t>(f.n_blocks) + ride.n_blocks);
-    md.n_workgroups = grid.x;
-    auto launch = [&](auto kernel, int threads) {
-      hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, m_stream.raw(), m_ldev, md, m_lhs.p, m_rhs.p, reg_by_value, m_Lx.p, m_D.p, l.n,
-                         m_mf_contrib.p, cur, next, m_zv.p, f, xg_now(), xg_other(), m_p.p, bf, tw, ride);
-    };
-    if (ride.n_blocks != 0) {
-      if (m_mode.twin_threads == 1024) launch(&ldlt_mf_twin_kernel<1024, true>, 1024);
-      else launch(&ldlt_mf_twin_kernel<512, true>, 512);
-    } else {
-      if (m_mode.twin_threads == 1024) launch(&ldlt_mf_twin_kernel<1024, false>, 1024);
-      else launch(&ldlt_mf_twin_kernel<512, false>, 512);
-    }
-  } else {
-    const dim3 grid(static_cast<uint32_t>(l.tasks.size()) + static_cast<uint32_t>(f.n_blocks));
-    md.n_workgroups = grid.x;
-    auto launch = [&](auto kernel, int threads) {
-      hipLaunchKernelGGL(kernel, grid, dim3(threads), m_mf_lds, m_stream.raw(), m_ldev, md, m_lhs.p, m_rhs.p, reg_by_value, m_Lx.p, m_D.p,
-                         l.n, m_mf_contrib.p, cur, next, m_zv.p, f, xg_now(), xg_other(), m_p.p, bf);
-    };
-    if (m_mode.mf_threads == 1024) {
-      if (chained) m_mode.mf_mfma ? launch(&ldlt_mf_step_kernel<1024, true, true>, 1024) : launch(&ldlt_mf_step_kernel<1024, false, true>, 1024);
-      else m_mode.mf_mfma ? launch(&ldlt_mf_step_kernel<1024, true, false>, 1024) : launch(&ldlt_mf_step_kernel<1024, false, false>, 1024);
-    } else {
-      if (chained) m_mode.mf_mfma ? launch(&ldlt_mf_step_kernel<512, true, true>, 512) : launch(&ldlt_mf_step_kernel<512, false, true>, 512);
-      else m_mode.mf_mfma ? launch(&ldlt_mf_step_kernel<512, true, false>, 512) : launch(&ldlt_mf_step_kernel<512, false, false>, 512);
-    }
-    if (chained) m_chain_step_wgs += md.n_workgroups;  // (what the next chained sweep waits for in chain[48])
-  }
-  SLPX_HIP_CHECK(hipGetLastError());
-}
-
-void DeviceNlp::book_mf_step(int twin_mode, bool chained) {
-  m_stats_cur ^= 1;
-  if (twin_mode != 0) {
-    m_stats_tw_cur ^= 1;
-    m_xg_tw_parity ^= 1;
-  }
-  xg_flip();
+  m_ldlt.step_twin(delta0, gamma0, delta1, gamma1, mode, r);
   m_stream.tape_pending = false;
-  m_last_step_chained = chained;
-  m_twin_mode = twin_mode;
+  m_last_step_chained = false;
+  m_ldlt.stats_handed_to_host(++m_seq_expected);
 }
 
 bool DeviceNlp::factor_solve_publish_twin(double delta0, double gamma0, double delta1, double gamma1, int mode) {
-  if (!twin_available() || m_stream.tape_pending) return false;
-  m_h_reg[0] = delta0;
-  m_h_reg[1] = gamma0;
-  m_h_reg[2] = delta1;
-  m_h_reg[3] = gamma1;
-  note_factored(0, delta0, gamma0);
-  m_fact_tw[0] = delta1;
-  m_fact_tw[1] = gamma1;
+  if (!twin_ready() || m_stream.tape_pending) return false;
   if (!m_kkt_pending) materialize_kkt();
-  const KktFuse f = take_kkt_fuse();
-  launch_mf_step(mode, m_h_reg, f, false);
-  book_mf_step(mode, false);
-  m_stats_seq = ++m_seq_expected;
-  m_stats_in_host = true;
+  launch_twin(delta0, gamma0, delta1, gamma1, mode, take_kkt_fuse(), nullptr, nullptr);
   return true;
 }
 
 bool DeviceNlp::factor_solve_publish_twin_written(double delta0, double gamma0, double delta1, double gamma1, int mode, const double* lhs2,
                                                   const double* rhs2) {
-  if (!twin_available() || m_stream.tape_pending || m_kkt_pending || m_lhs_stale || m_rhs_stale) return false;
-  m_h_reg[0] = delta0;
-  m_h_reg[1] = gamma0;
-  m_h_reg[2] = delta1;
-  m_h_reg[3] = gamma1;
-  note_factored(0, delta0, gamma0);
-  m_fact_tw[0] = delta1;
-  m_fact_tw[1] = gamma1;
-  launch_mf_step(mode, m_h_reg, KktFuse{}, false, lhs2, rhs2);
-  book_mf_step(mode, false);
-  m_stats_seq = ++m_seq_expected;
-  m_stats_in_host = true;
+  if (!twin_ready() || m_stream.tape_pending || m_kkt_pending || m_lhs_stale || m_rhs_stale) return false;
+  launch_twin(delta0, gamma0, delta1, gamma1, mode, KktFuse{}, lhs2, rhs2);
   return true;
 }
 
 void DeviceNlp::adopt_twin() {
-  // every launch takes these pointers when it is made (ipm_accept_lookahead): later solves with this factorization,
-  // the committed direction and the counters are the second attempt's
-  m_Lx.swap(m_Lx_tw);
-  m_D.swap(m_D_tw);
-  m_zv.swap(m_zv_tw);
-  m_p.swap(m_p_tw);
+  m_ldlt.adopt_twin();
   m_ps.swap(m_ps_tw);
   m_pz.swap(m_pz_tw);
-  m_stats.swap(m_stats_tw);
-  std::swap(m_stats_cur, m_stats_tw_cur);
-  m_h_stats[0] = m_h_stats[1];
-  m_twin_mode = 0;
-  note_factored(0, m_fact_tw[0], m_fact_tw[1]);
-}
-
-void DeviceNlp::enqueue_factor_solve(int parity) {
-  if (!(m_mode.mf && xg_other() != nullptr)) throw std::logic_error("slpx: a one-launch step without the multifrontal plan");
-  if (!m_kkt_pending) materialize_kkt();
-  KktFuse f = take_kkt_fuse();
-  const bool chained = m_stream.tape_pending;
-  m_stats_cur = parity ^ 1;  // (the callers flipped it already; launch_mf_step / book_mf_step do it themselves)
-  launch_mf_step(0, m_h_reg, f, chained);
-  book_mf_step(0, chained);
-}
-
-void DeviceNlp::read_stats(std::vector<LdltStats>& out) {
-  out.resize(m_batch);
-  if (!m_stats_in_host)
-    SLPX_HIP_CHECK(hipMemcpyAsync(m_h_stats, m_stats.p + static_cast<size_t>(m_stats_cur) * m_batch,
-                                  m_batch * sizeof(LdltStats), hipMemcpyDeviceToHost, m_stream));
-  // Busy-poll instead of a blocking wait: the interrupt-driven wake-up of
-  // hipStreamSynchronize costs tens of microseconds, a tenth of a whole Newton step.
-  if (m_stats_in_host && m_batch == 1) {
-    // the publishing kernel's sequence number (see step_backsub_kernel); the stream is
-    // consulted now and then so that a failed launch cannot hang the host
-    spin_on_published([&] { return *m_h_seq >= m_stats_seq; }, m_stream.raw(), "slpx: step finished without publishing its counters");
-  } else {
-    hipError_t st;
-    while ((st = hipStreamQuery(m_stream.raw())) == hipErrorNotReady) {
-    }
-    SLPX_HIP_CHECK(st);
-  }
-  std::copy(m_h_stats, m_h_stats + m_batch, out.begin());
-  // (an experiment's knob: the host sits on the verdict for so many nanoseconds — how much of its reaction a step
-  // hides: profiles/host_slack.sh)
-  static const long delay_ns = [] {
-    const char* env = std::getenv("SLPX_DEBUG_STATS_DELAY_NS");
-    return env ? std::atol(env) : 0L;
-  }();
-  if (delay_ns > 0) {
-    const auto until = std::chrono::steady_clock::now() + std::chrono::nanoseconds(delay_ns);
-    while (std::chrono::steady_clock::now() < until) {
-    }
-  }
 }
 
 // Full solve for a right-hand side that arrived AFTER the factorization (second-order
-// corrections, multiplier estimate, slpx_ldlt_solve): forward, then backward.
+// corrections, multiplier estimate, slpx_ldlt_solve)
 void DeviceNlp::solve() {
   if (m_rhs_stale) build_rhs();
-  m_solution_valid = true;
-  const LdltPlan& l = m_l_ref;
-  if (m_mode.dense) {
-    solve_after_factor();
-    return;
-  }
-  if (m_mode.mf && m_mode.mf_solve && m_batch == 1 && xg_other() != nullptr) {
-    MfDev md;
-    md.tasks = m_mf_tasks.p;
-    md.fronts = m_mf_fronts.p;
-    md.image = m_mf_image.p;
-    md.image_stride16 = m_mf_image_stride16;
-    md.image_desc = m_mf_image_desc.p;
-    md.n_tasks = static_cast<unsigned int>(l.tasks.size());
-    const dim3 grid(static_cast<uint32_t>(l.tasks.size()));
-    if (m_mode.mf_threads == 1024)
-      hipLaunchKernelGGL(ldlt_mf_solve_kernel<1024>, grid, dim3(1024), m_mf_lds, m_stream, m_ldev, md, m_Lx.p, m_D.p, m_rhs.p,
-                         m_mf_contrib.p, xg_now(), xg_other(), m_p.p);
-    else
-      hipLaunchKernelGGL(ldlt_mf_solve_kernel<512>, grid, dim3(512), m_mf_lds, m_stream, m_ldev, md, m_Lx.p, m_D.p, m_rhs.p,
-                         m_mf_contrib.p, xg_now(), xg_other(), m_p.p);
-    xg_flip();
-    SLPX_HIP_CHECK(hipGetLastError());
-    return;
-  }
-  const long long lxs = static_cast<long long>(std::max<int64_t>(1, l.nnzL));
-  const int scs = static_cast<int>(std::max<uint32_t>(1, l.n_scontrib));
-  if (m_mode.il) {
-    const int C = (m_batch + 63) / 64;
-    if (!m_rhs_in_il)
-      hipLaunchKernelGGL(il_gather_kernel, dim3((l.n + 63) / 64, C), dim3(256), 0, m_stream, m_rhs.p,
-                         static_cast<long long>(l.n), l.n, m_rhs_il.p, m_batch);
-    for (int r = 0; r < l.n_rounds; ++r) {
-      const uint32_t nt = l.round_ptr[r + 1] - l.round_ptr[r];
-      hipLaunchKernelGGL(ldlt_fwd_il_kernel, dim3(nt, C), dim3(kIlLanes), m_il_solve_lds, m_stream, m_ldev,
-                         l.round_ptr[r], m_rhs_il.p, l.n, m_Lx_il.p, lxs, m_D_il.p, m_scontrib_il.p, scs,
-                         m_zv_il.p);
-    }
-    solve_after_factor();
-    return;
-  }
-  if (m_mode.single_launch && m_batch == 1) {
-    // one problem: every round in ONE launch (the tasks order themselves through the round counters)
-    hipLaunchKernelGGL(ldlt_fwd_kernel, dim3(static_cast<uint32_t>(l.tasks.size()), 1), dim3(256), l.solve_lds_bytes, m_stream,
-                       m_ldev, 0u, m_rhs.p, l.n, m_Lx.p, lxs, m_D.p, m_scontrib.p, scs, m_zv.p, m_fround_cnt.p);
-  } else {
-    for (int r = 0; r < l.n_rounds; ++r) {
-      const uint32_t nt = l.round_ptr[r + 1] - l.round_ptr[r];
-      hipLaunchKernelGGL(ldlt_fwd_kernel, dim3(nt, m_batch), dim3(256), l.solve_lds_bytes, m_stream,
-                         m_ldev, l.round_ptr[r], m_rhs.p, l.n, m_Lx.p, lxs, m_D.p, m_scontrib.p, scs,
-                         m_zv.p, static_cast<unsigned int*>(nullptr));
-    }
-  }
-  solve_after_factor();
+  m_ldlt.solve(system());
 }
 
-// The factorization carried the rhs along as an extra row and left z = D⁻¹L⁻¹Pb behind
-// (ldlt_symbolic.cpp), so only the backward substitution remains.
-void DeviceNlp::solve_after_factor() { solve_after_factor_impl(nullptr); }
+void DeviceNlp::solve_after_factor() {
+  if (m_mode.dense && m_rhs_stale) build_rhs();  // (nothing rides in a dense factorization: it solves from the rhs in memory)
+  m_ldlt.solve_after_factor(system());
+}
 
 // backward solve, back-substitution and the hand-over of the current attempt's counters to the
-// host: one launch where the back-substitution can ride along (device.hpp: BacksubFuse)
+// host: one launch where the back-substitution can ride along (device_base.hpp: BacksubFuse)
 void DeviceNlp::solve_backsub_publish() {
-  const LdltStats* src = m_stats.p + static_cast<size_t>(m_stats_cur) * m_batch;
   if (m_mode.fuse_backsub) {
-    solve_after_factor_impl(src);
-    if (m_batch == 1) m_stats_seq = ++m_seq_expected;
+    if (m_mode.dense && m_rhs_stale) build_rhs();
+    const BacksubFuse f = backsub_fuse();
+    m_ldlt.solve_after_factor(system(), &f);
+    if (m_batch == 1) m_ldlt.stats_handed_to_host(++m_seq_expected);
+    else m_ldlt.stats_handed_to_host();
   } else {
-    solve_after_factor_impl(nullptr);
-    backsub_and_publish(src);
+    solve_after_factor();
+    backsub_and_publish(true);
   }
-  m_stats_in_host = true;
-}
-
-void DeviceNlp::solve_after_factor_impl(const LdltStats* publish) {
-  const LdltPlan& l = m_l_ref;
-  m_solution_valid = true;
-  const long long lxs = static_cast<long long>(std::max<int64_t>(1, l.nnzL));
-  if (m_mode.dense) {  // (nothing rides in a dense factorization: forward and backward substitution from the rhs in memory)
-    if (m_rhs_stale) build_rhs();
-    hipLaunchKernelGGL(ldlt_dense_solve_kernel, dim3(m_batch), dim3(kDenseThreads), 8u * static_cast<uint32_t>(l.n) + 16u, m_stream, l.n,
-                       m_dense_A.p, m_rhs.p, m_p.p, m_mode.dense_pivoted ? m_dense_trans.p : nullptr);
-    SLPX_HIP_CHECK(hipGetLastError());
-    return;
-  }
-  if (m_mode.il) {
-    const int C = (m_batch + 63) / 64;
-    for (int r = l.n_rounds - 1; r >= 0; --r) {
-      const uint32_t nt = l.round_ptr[r + 1] - l.round_ptr[r];
-      hipLaunchKernelGGL(ldlt_bwd_il_kernel, dim3(nt, C), dim3(kIlLanes * kIlBwdWaves), m_il_solve_lds, m_stream, m_ldev,
-                         l.round_ptr[r], l.n, m_Lx_il.p, lxs, m_zv_il.p, m_xg_il.p, m_p.p, m_batch);
-    }
-    SLPX_HIP_CHECK(hipGetLastError());
-    return;
-  }
-  if (m_mode.single_launch) {
-    const uint32_t nt = static_cast<uint32_t>(l.tasks.size());
-    const BacksubFuse f = publish != nullptr ? backsub_fuse(publish) : BacksubFuse{};
-    hipLaunchKernelGGL(ldlt_bwd_kernel, dim3(nt, m_batch), dim3(256), f.on ? m_solve_lds_inline : l.solve_lds_bytes,
-                       m_stream, m_ldev, nt - 1, l.n, m_Lx.p, lxs, m_zv.p, xg_now(), xg_other(), m_p.p, m_bround_cnt.p, f);
-    xg_flip();
-  } else {
-    for (int r = l.n_rounds - 1; r >= 0; --r) {
-      const uint32_t nt = l.round_ptr[r + 1] - l.round_ptr[r];
-      hipLaunchKernelGGL(ldlt_bwd_kernel, dim3(nt, m_batch), dim3(256), l.solve_lds_bytes, m_stream,
-                         m_ldev, l.round_ptr[r], l.n, m_Lx.p, lxs, m_zv.p, m_xg.p, static_cast<double*>(nullptr), m_p.p,
-                         static_cast<unsigned int*>(nullptr), BacksubFuse{});
-    }
-  }
-  SLPX_HIP_CHECK(hipGetLastError());
-}
-
-// Batch-interleaved mode keeps L and D as [chunk][index][lane]; the batch-major copies that
-// slpx_system_get hands out are made on demand.
-void DeviceNlp::materialize_factor() {
-  if (!m_mode.il || !m_il_outputs_stale) return;
-  const LdltPlan& l = m_l_ref;
-  const int C = (m_batch + 63) / 64;
-  const int nl = static_cast<int>(std::max<int64_t>(1, l.nnzL));
-  hipLaunchKernelGGL(il_scatter_kernel, dim3((nl + 63) / 64, C), dim3(256), 0, m_stream, m_Lx_il.p, nl, m_Lx.p,
-                     static_cast<long long>(nl), m_batch);
-  hipLaunchKernelGGL(il_scatter_kernel, dim3((l.n + 63) / 64, C), dim3(256), 0, m_stream, m_D_il.p, l.n, m_D.p,
-                     static_cast<long long>(l.n), m_batch);
-  SLPX_HIP_CHECK(hipGetLastError());
-  m_il_outputs_stale = false;
-}
-
-size_t DeviceNlp::download_factor_scratch(int which, std::vector<double>& out) {
-  const LdltPlan& l = m_l_ref;
-  const size_t B = static_cast<size_t>(m_batch);
-  const size_t count = which == 0 ? static_cast<size_t>(l.n) : std::max<uint32_t>(1, l.n_contrib);
-  out.assign(B * count, 0.0);
-  if (!m_mode.il) {
-    download(which == 0 ? m_zv.p : m_contrib.p, out.data(), B * count);
-    return count;
-  }
-  // [group of kIlW problems][index][problem of the group] -> [problem][index]
-  const DevBuf<double>& src = which == 0 ? m_zv_il : m_contrib_il;
-  std::vector<double> raw(src.n);
-  download(src.p, raw.data(), raw.size());
-  for (size_t b = 0; b < B; ++b)
-    for (size_t i = 0; i < count; ++i) out[b * count + i] = raw[((b / kIlW) * count + i) * kIlW + b % kIlW];
-  return count;
 }
 
 // p <- p + K_reg^-1 (b - K p), `iters` times: b = the right-hand side now in m_rhs, p = the
@@ -1950,36 +1313,36 @@ void DeviceNlp::refine_solution(int iters) {
     m_p_acc.alloc(dim);
   }
   SLPX_HIP_CHECK(hipMemcpyAsync(m_rhs0.p, m_rhs.p, dim * sizeof(double), hipMemcpyDeviceToDevice, m_stream));
-  SLPX_HIP_CHECK(hipMemcpyAsync(m_p_acc.p, m_p.p, dim * sizeof(double), hipMemcpyDeviceToDevice, m_stream));
+  SLPX_HIP_CHECK(hipMemcpyAsync(m_p_acc.p, m_ldlt.d_p(), dim * sizeof(double), hipMemcpyDeviceToDevice, m_stream));
   for (int it = 0; it < iters; ++it) {
     SLPX_HIP_CHECK(hipMemcpyAsync(m_rhs.p, m_rhs0.p, dim * sizeof(double), hipMemcpyDeviceToDevice, m_stream));
     hipLaunchKernelGGL(sym_residual_kernel, dim3(grid_for(dim, 256)), dim3(256), 0, m_stream, dim, m_lhs_colptr.p,
                        m_lhs_rowidx.p, m_lhs_rowptr.p, m_lhs_rowent.p, m_lhs_rowcol.p, m_lhs.p, m_p_acc.p, m_rhs.p);
     solve();  // m_rhs -> m_p
-    hipLaunchKernelGGL(axpy_kernel, dim3(grid_for(dim, 256)), dim3(256), 0, m_stream, dim, m_p.p, m_p_acc.p);
+    hipLaunchKernelGGL(axpy_kernel, dim3(grid_for(dim, 256)), dim3(256), 0, m_stream, dim, m_ldlt.d_p(), m_p_acc.p);
   }
-  SLPX_HIP_CHECK(hipMemcpyAsync(m_p.p, m_p_acc.p, dim * sizeof(double), hipMemcpyDeviceToDevice, m_stream));
+  SLPX_HIP_CHECK(hipMemcpyAsync(m_ldlt.d_p(), m_p_acc.p, dim * sizeof(double), hipMemcpyDeviceToDevice, m_stream));
   SLPX_HIP_CHECK(hipMemcpyAsync(m_rhs.p, m_rhs0.p, dim * sizeof(double), hipMemcpyDeviceToDevice, m_stream));
   SLPX_HIP_CHECK(hipGetLastError());
 }
 
-void DeviceNlp::backsub() { backsub_and_publish(nullptr); }
+void DeviceNlp::backsub() { backsub_and_publish(false); }
 
 // back-substitution that also hands the counters of the factorization just enqueued to the
 // host (read_stats() then needs no copy)
-void DeviceNlp::backsub_publish() {
-  backsub_and_publish(m_stats.p + static_cast<size_t>(m_stats_cur) * m_batch);
-  m_stats_in_host = true;
-}
+void DeviceNlp::backsub_publish() { backsub_and_publish(true); }
 
-// stats_src != nullptr: also copy those counters to the pinned host buffer
-void DeviceNlp::backsub_and_publish(const LdltStats* stats_src) {
-  if (m_kdev.m_i == 0 && stats_src == nullptr) return;
+// publish: also copy the current attempt's counters to the pinned host buffer
+void DeviceNlp::backsub_and_publish(bool publish) {
+  if (m_kdev.m_i == 0 && !publish) return;
   hipLaunchKernelGGL(step_backsub_kernel, dim3(grid_for(std::max(1, m_kdev.m_i), 256), m_batch),
-                     dim3(256), 0, m_stream, m_kdev, m_V.p, m_s_ref.nV, m_p.p, m_s.p, m_z.p, m_mu.p,
-                     m_ps.p, m_pz.p, stats_src, stats_src ? m_h_stats : nullptr, m_seq_dev.p,
-                     (stats_src && m_batch == 1) ? m_h_seq : nullptr);
-  if (stats_src && m_batch == 1) m_stats_seq = ++m_seq_expected;
+                     dim3(256), 0, m_stream, m_kdev, m_V.p, m_s_ref.nV, m_ldlt.d_p(), m_s.p, m_z.p, m_mu.p,
+                     m_ps.p, m_pz.p, publish ? m_ldlt.stats_now() : nullptr, publish ? m_ldlt.stats_host() : nullptr, m_seq_dev.p,
+                     (publish && m_batch == 1) ? m_h_seq : nullptr);
+  if (publish) {
+    if (m_batch == 1) m_ldlt.stats_handed_to_host(++m_seq_expected);
+    else m_ldlt.stats_handed_to_host();
+  }
   SLPX_HIP_CHECK(hipGetLastError());
 }
 
@@ -2039,7 +1402,7 @@ void DeviceNlp::wait() {
 
 void DeviceNlp::ipm_direction(double tau) {
   hipLaunchKernelGGL(ipm_direction_kernel, dim3(1), dim3(kIpmThreads), 0, m_stream, m_kdev, m_V.p, m_in.p, m_s.p,
-                     m_z.p, m_p.p, m_ps.p, m_pz.p, m_mu.p, tau, m_trial_in.p, m_ipm_alpha.p, &m_ipm_host[m_ipm_slot].dir);
+                     m_z.p, m_ldlt.d_p(), m_ps.p, m_pz.p, m_mu.p, tau, m_trial_in.p, m_ipm_alpha.p, &m_ipm_host[m_ipm_slot].dir);
   SLPX_HIP_CHECK(hipGetLastError());
 }
 
@@ -2054,7 +1417,7 @@ IpmLookaheadArgs DeviceNlp::lookahead_args(double tau, int twin_mode) {
   a.s = m_s.p;
   a.y = m_y.p;
   a.z = m_z.p;
-  a.p = m_p.p;
+  a.p = m_ldlt.d_p();
   a.ps = m_ps.p;
   a.pz = m_pz.p;
   a.mu = m_mu.p;
@@ -2065,19 +1428,19 @@ IpmLookaheadArgs DeviceNlp::lookahead_args(double tau, int twin_mode) {
   a.z_t = m_z_ahead.p;
   a.alpha_dev = m_ipm_alpha.p;
   a.out = &m_ipm_host[m_ipm_slot].dir;
-  a.stats = m_stats.p + static_cast<size_t>(m_stats_cur) * m_batch;
+  a.stats = m_ldlt.stats_now();
   if (twin_mode != 0) {  // (a twin launch: the kernel takes the direction of the attempt the policy takes)
     a.tw.mode = twin_mode;
-    a.tw.p = m_p_tw.p;
+    a.tw.p = m_ldlt.d_p_twin();
     a.tw.ps = m_ps_tw.p;
     a.tw.pz = m_pz_tw.p;
-    a.tw.stats = m_stats_tw.p + static_cast<size_t>(m_stats_tw_cur);
+    a.tw.stats = m_ldlt.twin_stats_now();
   }
   return a;
 }
 
 void DeviceNlp::ipm_lookahead(double tau) {
-  hipLaunchKernelGGL(ipm_lookahead_kernel, dim3(1), dim3(kIpmThreads), 0, m_stream, lookahead_args(tau, m_twin_mode));
+  hipLaunchKernelGGL(ipm_lookahead_kernel, dim3(1), dim3(kIpmThreads), 0, m_stream, lookahead_args(tau, m_ldlt.twin_mode()));
   SLPX_HIP_CHECK(hipGetLastError());
 }
 
@@ -2110,7 +1473,7 @@ void DeviceNlp::ipm_accept_lookahead() {
 
 void DeviceNlp::ipm_trial_point(double alpha) {
   hipLaunchKernelGGL(ipm_trial_point_kernel, dim3(grid_for(m_kdev.n, 256)), dim3(256), 0, m_stream, m_kdev.n,
-                     m_in.p, m_p.p, alpha, m_trial_in.p);
+                     m_in.p, m_ldlt.d_p(), alpha, m_trial_in.p);
   SLPX_HIP_CHECK(hipGetLastError());
 }
 
@@ -2125,7 +1488,7 @@ void DeviceNlp::ipm_trial_metrics(double alpha, bool s_from_ci) {
 void DeviceNlp::ipm_commit(double alpha, double alpha_z, bool s_from_ci) {
   const int work = std::max({m_kdev.n, m_kdev.m_e, m_kdev.m_i, 1});
   hipLaunchKernelGGL(ipm_commit_kernel, dim3(grid_for(work, 256)), dim3(256), 0, m_stream, m_kdev, m_V_trial.p,
-                     m_p.p, m_ps.p, m_pz.p, alpha, alpha_z, m_mu.p, s_from_ci ? 1 : 0, m_in.p, m_s.p, m_y.p,
+                     m_ldlt.d_p(), m_ps.p, m_pz.p, alpha, alpha_z, m_mu.p, s_from_ci ? 1 : 0, m_in.p, m_s.p, m_y.p,
                      m_z.p);
   SLPX_HIP_CHECK(hipGetLastError());
 }
@@ -2171,14 +1534,11 @@ bool DeviceNlp::ipm_ride_errors_in_next_step(int slot_out) {
 }
 
 bool DeviceNlp::ipm_ride_possible() {
-  if (!twin_available()) return false;
+  if (!twin_ready()) return false;
   if (m_mode.ride < 0) {
-    // the riding workgroups' LDS (ipm_error_block) beside the tasks': the launch takes the larger of the two
     int per_cu = 0;
     if (m_sw.ipm_ride) {
-      const size_t lds = std::max<size_t>(m_mf_lds, sizeof(double) * kIpmErrLdsDoubles);
-      per_cu = m_mode.twin_threads == 1024 ? workgroups_per_cu(reinterpret_cast<const void*>(&ldlt_mf_twin_kernel<1024, true>), 1024, lds)
-                                           : workgroups_per_cu(reinterpret_cast<const void*>(&ldlt_mf_twin_kernel<512, true>), 512, lds);
+      per_cu = m_ldlt.riding_twin_workgroups_per_cu();
       if (m_ipm_ride_verdict.n == 0) m_ipm_ride_verdict.upload(std::vector<double>(1, 0.0));
     }
     choose_ride(m_mode, m_plan, m_reduces.n, static_cast<size_t>(per_cu) * m_cus, m_sw);
@@ -2187,6 +1547,45 @@ bool DeviceNlp::ipm_ride_possible() {
                    per_cu, m_mode.twin_threads, m_cus, m_mode.ride ? "" : ": NOT resident at once");
   }
   return m_mode.ride != 0;
+}
+
+// The armed error launch (ipm_ride_errors_in_next_step) as the next twin launch carries it: its workgroups in front of
+// the tasks, on the CURRENT buffers — the look-ahead iterate has been made current —, the tape's sums with them
+MfRide DeviceNlp::ipm_take_ride() {
+  m_ride_next = false;
+  const int work = std::max({m_kdev.n, m_kdev.m_e, m_kdev.m_i, 1});
+  const int blocks = grid_for(8 * work, kIpmErrThreads, 64);
+  if (m_ipm_partial.n < static_cast<size_t>(blocks) * kIpmErrQ) m_ipm_partial.alloc(static_cast<size_t>(256) * kIpmErrQ);
+  if (m_ipm_err_done.n == 0) m_ipm_err_done.upload(std::vector<unsigned int>(1, 0u));
+  const int n_sums = static_cast<int>(m_reduces.n);
+  m_ride_ticket += 1.0;
+  MfRide ride;
+  ride.n_blocks = static_cast<uint32_t>(blocks + n_sums);
+  ride.K = m_kdev;
+  ride.V = m_V.p;
+  ride.x = m_in.p;
+  ride.s = m_s.p;
+  ride.y = m_y.p;
+  ride.z = m_z.p;
+  ride.scales = m_ipm_scales.p;
+  ride.nV = m_s_ref.nV;
+  ride.partial = m_ipm_partial.p;
+  IpmErrFinish& fin = ride.fin;
+  fin.n_err_blocks = blocks;
+  fin.n_total_blocks = blocks + n_sums;
+  fin.red = m_reduces.p;
+  fin.tape_scales = m_scales.p;
+  fin.Vw = m_V.p;
+  fin.done = m_ipm_err_done.p;
+  fin.out = &m_ipm_host[m_ride_slot].err_ahead;
+  fin.ctl = static_cast<IpmCtl*>(m_ipm_ctl_dev);
+  fin.dir = m_ipm_alpha.p;
+  fin.gate = m_ipm_gate.p;
+  fin.go_host = &m_ipm_host[m_ride_slot].go;
+  fin.check_host = &m_ipm_host[m_ride_slot].check;
+  fin.ride_verdict = m_ipm_ride_verdict.p;
+  fin.ride_ticket = m_ride_ticket;
+  return ride;
 }
 
 bool DeviceNlp::ipm_ride_wait(int slot_out) {
@@ -2258,19 +1657,19 @@ void DeviceNlp::ipm_soc_rhs() {
 void DeviceNlp::ipm_soc_backsub() {
   if (m_kdev.m_i == 0) return;
   hipLaunchKernelGGL(ipm_soc_backsub_kernel, dim3(grid_for(m_kdev.m_i, 256)), dim3(256), 0, m_stream, m_kdev,
-                     m_V.p, m_p.p, m_s.p, m_z.p, m_mu.p, m_soc_cims.p, m_ps.p, m_pz.p);
+                     m_V.p, m_ldlt.d_p(), m_s.p, m_z.p, m_mu.p, m_soc_cims.p, m_ps.p, m_pz.p);
   SLPX_HIP_CHECK(hipGetLastError());
 }
 
 void DeviceNlp::ipm_save_direction() {
   hipLaunchKernelGGL(ipm_copy_direction_kernel, dim3(grid_for(m_kdev.dim, 256)), dim3(256), 0, m_stream, m_kdev.dim, m_kdev.m_i,
-                     m_p.p, m_ps.p, m_pz.p, m_p_keep.p, m_ps_keep.p, m_pz_keep.p);
+                     m_ldlt.d_p(), m_ps.p, m_pz.p, m_p_keep.p, m_ps_keep.p, m_pz_keep.p);
   SLPX_HIP_CHECK(hipGetLastError());
 }
 
 void DeviceNlp::ipm_restore_direction() {
   hipLaunchKernelGGL(ipm_copy_direction_kernel, dim3(grid_for(m_kdev.dim, 256)), dim3(256), 0, m_stream, m_kdev.dim, m_kdev.m_i,
-                     m_p_keep.p, m_ps_keep.p, m_pz_keep.p, m_p.p, m_ps.p, m_pz.p);
+                     m_p_keep.p, m_ps_keep.p, m_pz_keep.p, m_ldlt.d_p(), m_ps.p, m_pz.p);
   SLPX_HIP_CHECK(hipGetLastError());
 }
 

@@ -228,9 +228,9 @@ __global__ __launch_bounds__(64) void est_fold_kernel(int n_part, int batch, con
 
 void DeviceNlp::errbound_require(const std::vector<uint8_t>& mask, const char* what) {
   if (static_cast<int>(mask.size()) != m_batch) throw std::runtime_error(std::string("slpx: ") + what + ": mask length");
-  if (!m_solution_valid) throw std::runtime_error(std::string("slpx: ") + what + ": no solution in memory (factor and solve first)");
+  if (!m_ldlt.solution_valid()) throw std::runtime_error(std::string("slpx: ") + what + ": no solution in memory (factor and solve first)");
   for (int b = 0; b < m_batch; ++b)
-    if (mask[b] && std::isnan(factored_regularization(b).first))
+    if (mask[b] && std::isnan(m_ldlt.factored_regularization(b).first))
       throw std::runtime_error(std::string("slpx: ") + what + ": no factorization in memory (factor and solve first)");
 }
 
@@ -257,14 +257,14 @@ void DeviceNlp::errbound_rows(const std::vector<uint8_t>& mask, bool want_bounds
   std::vector<double> reg(2 * static_cast<size_t>(B), 0.0);
   for (int b = 0; b < B; ++b)
     if (mask[b]) {
-      reg[2 * b] = m_fact_delta[b];
-      reg[2 * b + 1] = m_fact_gamma[b];
+      reg[2 * b] = m_ldlt.factored_regularization(b).first;
+      reg[2 * b + 1] = m_ldlt.factored_regularization(b).second;
     }
   const hipStream_t st = m_stream;
   SLPX_HIP_CHECK(hipMemcpyAsync(m_res_reg.p, reg.data(), reg.size() * sizeof(double), hipMemcpyHostToDevice, st));
   SLPX_HIP_CHECK(hipMemcpyAsync(m_res_mask.p, mask.data(), static_cast<size_t>(B), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(kkt_abs_row_kernel, dim3(n_part, B), dim3(kErrThreads), 0, st, dim, m_kdev.n, nnz, want_bounds ? 1 : 0, m_rm_rowptr.p,
-                     m_rm_ent.p, m_rm_col.p, m_lhs.p, m_rhs.p, m_p.p, m_res.p, m_res_reg.p, m_res_mask.p, m_eb_w.p, m_eb_f.p, m_eb_partial.p);
+                     m_rm_ent.p, m_rm_col.p, m_lhs.p, m_rhs.p, m_ldlt.d_p(), m_res.p, m_res_reg.p, m_res_mask.p, m_eb_w.p, m_eb_f.p, m_eb_partial.p);
   hipLaunchKernelGGL(kkt_abs_fold_kernel, dim3(B), dim3(64), 0, st, n_part, m_eb_partial.p, m_res_mask.p, m_eb_scal.p);
   SLPX_HIP_CHECK(hipGetLastError());
   std::vector<unsigned long long> bits(static_cast<size_t>(B) * 4);
@@ -310,7 +310,7 @@ void DeviceNlp::errbound_round(const std::vector<EstRound>& rounds, std::vector<
   SLPX_HIP_CHECK(hipGetLastError());
   system_written_by_caller(/*lhs=*/false, /*rhs=*/true);  // (batch-major memory holds THE right-hand side now)
   solve();
-  hipLaunchKernelGGL(est_reduce_kernel, dim3(n_part, B), dim3(kErrThreads), 0, st, dim, B, d_cmd, m_eb_f.p, m_p.p, m_eb_sign.p, m_eb_partial.p);
+  hipLaunchKernelGGL(est_reduce_kernel, dim3(n_part, B), dim3(kErrThreads), 0, st, dim, B, d_cmd, m_eb_f.p, m_ldlt.d_p(), m_eb_sign.p, m_eb_partial.p);
   hipLaunchKernelGGL(est_fold_kernel, dim3((B + 63) / 64), dim3(64), 0, st, n_part, B, d_cmd, m_eb_partial.p, m_eb_scal.p);
   SLPX_HIP_CHECK(hipGetLastError());
   std::vector<unsigned long long> bits(static_cast<size_t>(B) * 4);
@@ -329,7 +329,7 @@ void DeviceNlp::errbound_round(const std::vector<EstRound>& rounds, std::vector<
 void DeviceNlp::errbound_restore() {
   const size_t bytes = static_cast<size_t>(m_batch) * m_kdev.dim * sizeof(double);
   const hipStream_t st = m_stream;
-  SLPX_HIP_CHECK(hipMemcpyAsync(m_p.p, m_ref_keep_p.p, bytes, hipMemcpyDeviceToDevice, st));
+  SLPX_HIP_CHECK(hipMemcpyAsync(m_ldlt.d_p(), m_ref_keep_p.p, bytes, hipMemcpyDeviceToDevice, st));
   SLPX_HIP_CHECK(hipMemcpyAsync(m_rhs.p, m_ref_keep_b.p, bytes, hipMemcpyDeviceToDevice, st));
   SLPX_HIP_CHECK(hipStreamSynchronize(st));
 }

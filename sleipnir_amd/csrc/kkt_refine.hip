@@ -100,9 +100,9 @@ void DeviceNlp::residual_buffers() {
 void DeviceNlp::residual(const std::vector<uint8_t>& mask, std::vector<double>& norm) {
   const int dim = m_kdev.dim, nnz = m_kdev.nnz_lhs, B = m_batch;
   if (static_cast<int>(mask.size()) != B) throw std::runtime_error("slpx: residual: mask length");
-  if (!m_solution_valid) throw std::runtime_error("slpx: residual / refine: no solution in memory (factor and solve first)");
+  if (!m_ldlt.solution_valid()) throw std::runtime_error("slpx: residual / refine: no solution in memory (factor and solve first)");
   for (int b = 0; b < B; ++b)
-    if (mask[b] && std::isnan(factored_regularization(b).first))
+    if (mask[b] && std::isnan(m_ldlt.factored_regularization(b).first))
       throw std::runtime_error("slpx: residual / refine: no factorization in memory (factor and solve first)");
   const int n_part = (dim + kResidualThreads - 1) / kResidualThreads;
   residual_buffers();
@@ -113,14 +113,14 @@ void DeviceNlp::residual(const std::vector<uint8_t>& mask, std::vector<double>& 
   std::vector<double> reg(2 * static_cast<size_t>(B), 0.0);
   for (int b = 0; b < B; ++b)
     if (mask[b]) {
-      reg[2 * b] = m_fact_delta[b];
-      reg[2 * b + 1] = m_fact_gamma[b];
+      reg[2 * b] = m_ldlt.factored_regularization(b).first;
+      reg[2 * b + 1] = m_ldlt.factored_regularization(b).second;
     }
   const hipStream_t st = m_stream;
   SLPX_HIP_CHECK(hipMemcpyAsync(m_res_reg.p, reg.data(), reg.size() * sizeof(double), hipMemcpyHostToDevice, st));
   SLPX_HIP_CHECK(hipMemcpyAsync(m_res_mask.p, mask.data(), static_cast<size_t>(B), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(kkt_residual_kernel, dim3(n_part, B), dim3(kResidualThreads), 0, st, dim, m_kdev.n, nnz, m_rm_rowptr.p, m_rm_ent.p,
-                     m_rm_col.p, m_lhs.p, m_rhs.p, m_p.p, m_res_reg.p, m_res_mask.p, m_res.p, m_res_partial.p);
+                     m_rm_col.p, m_lhs.p, m_rhs.p, m_ldlt.d_p(), m_res_reg.p, m_res_mask.p, m_res.p, m_res_partial.p);
   hipLaunchKernelGGL(kkt_residual_norm_kernel, dim3(B), dim3(64), 0, st, n_part, m_res_partial.p, m_res_mask.p, m_res_norm.p);
   SLPX_HIP_CHECK(hipGetLastError());
   std::vector<unsigned long long> bits(B);
@@ -139,7 +139,7 @@ void DeviceNlp::refine_begin() {
     m_ref_d.alloc(count);
   }
   const hipStream_t st = m_stream;
-  SLPX_HIP_CHECK(hipMemcpyAsync(m_ref_keep_p.p, m_p.p, count * sizeof(double), hipMemcpyDeviceToDevice, st));
+  SLPX_HIP_CHECK(hipMemcpyAsync(m_ref_keep_p.p, m_ldlt.d_p(), count * sizeof(double), hipMemcpyDeviceToDevice, st));
   SLPX_HIP_CHECK(hipMemcpyAsync(m_ref_keep_b.p, m_rhs.p, count * sizeof(double), hipMemcpyDeviceToDevice, st));
 }
 
@@ -149,7 +149,7 @@ void DeviceNlp::refine_solve_correction() {
   SLPX_HIP_CHECK(hipMemcpyAsync(m_rhs.p, m_res.p, bytes, hipMemcpyDeviceToDevice, st));
   system_written_by_caller(/*lhs=*/false, /*rhs=*/true);  // (batch-major memory holds THE right-hand side now)
   solve();
-  SLPX_HIP_CHECK(hipMemcpyAsync(m_ref_d.p, m_p.p, bytes, hipMemcpyDeviceToDevice, st));
+  SLPX_HIP_CHECK(hipMemcpyAsync(m_ref_d.p, m_ldlt.d_p(), bytes, hipMemcpyDeviceToDevice, st));
   SLPX_HIP_CHECK(hipMemcpyAsync(m_rhs.p, m_ref_keep_b.p, bytes, hipMemcpyDeviceToDevice, st));
 }
 
@@ -159,14 +159,14 @@ void DeviceNlp::refine_apply(const std::vector<uint8_t>& accept) {
   const hipStream_t st = m_stream;
   SLPX_HIP_CHECK(hipMemcpyAsync(m_res_mask.p, accept.data(), static_cast<size_t>(m_batch), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(refine_accept_kernel, dim3((dim + 255) / 256, m_batch), dim3(256), 0, st, dim, m_ref_keep_p.p, m_ref_d.p, m_res_mask.p,
-                     m_p.p);
+                     m_ldlt.d_p());
   SLPX_HIP_CHECK(hipGetLastError());
   SLPX_HIP_CHECK(hipStreamSynchronize(st));  // (`accept` is the caller's)
 }
 
 void DeviceNlp::refine_keep_solution() {
   const size_t bytes = static_cast<size_t>(m_batch) * m_kdev.dim * sizeof(double);
-  SLPX_HIP_CHECK(hipMemcpyAsync(m_ref_keep_p.p, m_p.p, bytes, hipMemcpyDeviceToDevice, m_stream));
+  SLPX_HIP_CHECK(hipMemcpyAsync(m_ref_keep_p.p, m_ldlt.d_p(), bytes, hipMemcpyDeviceToDevice, m_stream));
 }
 
 }  // namespace slpx

@@ -50,9 +50,6 @@ constexpr int kIlLanes = 64;  // lanes of a wave
 // of 16, and the same LDS per workgroup holds twice the waves to hide its latency (measured, ms per
 // factorization of 512 x N=1000: 256 threads 0.629, 512 threads 0.589, 1024 threads 0.809)
 
-// number of 16-problem rows groups a batch occupies (padded to whole waves of 64 problems)
-__host__ __device__ inline int il_groups(int batch) { return kIlRowsPerChunk * ((batch + 63) / 64); }
-
 // [b][i] (stride `stride` doubles per problem) -> [b / 16][i][16]; problems beyond the batch
 // get 0.  64 x 64 tiles through LDS so that both sides move whole cache lines.
 __global__ __launch_bounds__(256) void il_gather_kernel(const double* __restrict__ src, long long stride,

@@ -23,7 +23,7 @@
 #include "device.hpp"
 #include "device_layout.h"
 #include "kkt_kernels.h"
-#include "tape_kernels.h"  // stage16, q16
+#include "tape_interp.h"  // stage16, q16
 
 namespace slpx {
 

@@ -973,17 +973,7 @@ struct MfTwin {
   const double *lhs = nullptr, *rhs = nullptr;
 };
 
-// The error launch of the iteration before this step, riding in front of its tasks (MfDev::ride_verdict): the
-// arguments of ipm_error_partial_kernel, `n_blocks` workgroups [error workgroups | one per separable sum].
-struct MfRide {
-  uint32_t n_blocks = 0;
-  KktDev K;
-  const double *V = nullptr, *x = nullptr, *s = nullptr, *y = nullptr, *z = nullptr, *scales = nullptr;
-  int nV = 0;
-  double* partial = nullptr;
-  IpmErrFinish fin;
-};
-
+// (struct MfRide, the riding error launch's arguments: ipm_kernels.h)
 template <int THREADS, bool RIDE = false>
 __global__ __launch_bounds__(THREADS) void ldlt_mf_twin_kernel(
     LdltDev L, MfDev Mf, const double* __restrict__ lhs, const double* __restrict__ rhs, const double* __restrict__ reg,

@@ -144,12 +144,12 @@ bool NewtonSystem::skip_first() const { return m_opt.skip_structurally_singular_
 // is redone — V swept again from the unchanged state, the system rebuilt — with the chain off.
 template <class Once>
 void NewtonSystem::read_stats_redoing_a_failed_chain(std::vector<LdltStats>& stats, Once&& once) {
-  m_dev->read_stats(stats);
+  m_dev->ldlt().read_stats(stats);
   if (m_opt.batch != 1 || (stats[0].n_bad & kLdltChainFailure) == 0) return;
   m_dev->recover_from_chain_failure();
   m_dev->build_kkt_for_step(/*with_reduce=*/true);
   once();
-  m_dev->read_stats(stats);
+  m_dev->ldlt().read_stats(stats);
 }
 
 std::vector<FactorInfo> NewtonSystem::compute(bool solve_speculatively) {
@@ -166,7 +166,7 @@ std::vector<FactorInfo> NewtonSystem::compute(bool solve_speculatively, const st
 std::vector<FactorInfo> NewtonSystem::compute_impl(int mode, const std::vector<uint8_t>* mask) {
   const int B = m_opt.batch;
   m_last_twin_launches = m_last_twin_taken = 0;
-  if (mode == 1 && B == 1 && m_twin_attempts && !mask && m_dev->twin_available()) return compute_twin();
+  if (mode == 1 && B == 1 && m_twin_attempts && !mask && m_dev->ldlt().twin_available()) return compute_twin();
   std::vector<uint8_t> active = mask ? *mask : std::vector<uint8_t>(B, 1);
   std::vector<LdltPolicy> pol(B);
   for (int b = 0; b < B; ++b)
@@ -206,7 +206,7 @@ FactorInfo NewtonSystem::remember(int b, const LdltPolicy& p) {
 LdltLaunch NewtonSystem::twin_first_launch() const { return start_policy(0, skip_first()).launch(m_twin_expect); }
 
 bool NewtonSystem::begin_speculative_compute(bool gated) {
-  if (m_spec.valid || m_opt.batch != 1 || !m_twin_attempts || !m_dev->twin_available()) {
+  if (m_spec.valid || m_opt.batch != 1 || !m_twin_attempts || !m_dev->ldlt().twin_available()) {
     m_dev->ipm_ride_disarm();
     return false;
   }
@@ -264,7 +264,7 @@ struct NewtonSystem::TwinLauncher {
     // (a twin launch itself is never chained, the single-attempt fallback of once() can be)
     sys.read_stats_redoing_a_failed_chain(stats, once);
     if (!have_second) return false;
-    second_stats = dev.read_twin_stats();
+    second_stats = dev.ldlt().read_twin_stats();
     const int n = sys.m_s.n, m_e = sys.m_s.m_e;
     const LdltVerdict v = ldlt_judge(stats[0], n, m_e, tl.mode == 2);
     ++sys.m_twin_hist[v == kLdltAccepted || v == kLdltFailed ? v
@@ -319,8 +319,8 @@ struct NewtonSystem::HookedLauncher {
     // ladder would each drag a chain nobody reads)
     if (hooks.after && first_launch) hooks.after(tl.d0, tl.g0);
     first_launch = false;
-    dev.read_stats(stats);
-    if (have_second) second_stats = dev.read_twin_stats();
+    dev.ldlt().read_stats(stats);
+    if (have_second) second_stats = dev.ldlt().read_twin_stats();
     return have_second;
   }
   const LdltStats& first() const { return stats[0]; }
@@ -332,7 +332,7 @@ std::vector<FactorInfo> NewtonSystem::compute_hooked(const AttemptHooks& hooks) 
   if (m_opt.batch != 1) throw std::runtime_error("slpx: compute_hooked handles one problem");
   m_hooked_chain_valid = false;
   LdltPolicy pol = start_policy(0, /*skip_first=*/false);
-  HookedLauncher launcher{*this, hooks, static_cast<bool>(hooks.prepare_second) && m_dev->twin_available()};
+  HookedLauncher launcher{*this, hooks, static_cast<bool>(hooks.prepare_second) && m_dev->ldlt().twin_available()};
   const double extra = hooks.eliminated_min_pivot ? hooks.eliminated_min_pivot() : std::numeric_limits<double>::infinity();
   // (later launches hold the attempt and its delta x 10 only: no memory of what the loop's first attempt drew)
   const LdltTwinRun run = ldlt_run_twin(pol, launcher, nullptr, extra);
@@ -358,7 +358,7 @@ std::vector<FactorInfo> NewtonSystem::compute_hooked_batch(const BatchPrepare& p
         prepare(d, g, a);
         m_dev->system_written_by_caller(true, true);
         m_dev->factor(d, g, a);
-        m_dev->read_stats(stats);
+        m_dev->ldlt().read_stats(stats);
         return stats.data();
       },
       &eliminated_min_pivot);
@@ -376,7 +376,7 @@ bool NewtonSystem::factor_unregularized() {
   std::vector<uint8_t> active(B, 1);
   m_dev->factor(zero, zero, active);
   std::vector<LdltStats> stats;
-  m_dev->read_stats(stats);
+  m_dev->ldlt().read_stats(stats);
   ++m_last_factorizations;
   return std::all_of(stats.begin(), stats.begin() + B, [&](const LdltStats& st) { return ldlt_ideal(st, m_s.n, m_s.m_e); });
 }

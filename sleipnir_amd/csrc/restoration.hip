@@ -691,7 +691,7 @@ FrDevice::Args FrDevice::args(bool ahead) const {
   a.s0 = m_dev.d_s();
   a.y = m_dev.d_y();
   a.z0 = m_dev.d_z();
-  a.p = m_dev.d_p();
+  a.p = m_dev.ldlt().d_p();
   a.ps0 = m_dev.d_ps();
   a.pz0 = m_dev.d_pz();
   a.xr = m_xr.p;
@@ -789,7 +789,7 @@ void FrDevice::accept_lookahead() {
 }
 
 void FrDevice::trial_point(double alpha) {
-  hipLaunchKernelGGL(fr_trial_point_kernel, dim3(grid_for(m_n, 256)), dim3(256), 0, m_dev.stream(), m_n, m_dev.d_x(), m_dev.d_p(), alpha,
+  hipLaunchKernelGGL(fr_trial_point_kernel, dim3(grid_for(m_n, 256)), dim3(256), 0, m_dev.stream(), m_n, m_dev.d_x(), m_dev.ldlt().d_p(), alpha,
                      m_dev.d_trial_in());
   SLPX_HIP_CHECK(hipGetLastError());
 }
@@ -834,7 +834,7 @@ void FrDevice::soc_accumulate(double alpha, bool first) {
 void FrDevice::save_direction() {
   const KktDev K = m_dev.kdev();
   hipLaunchKernelGGL(fr_copy_direction_kernel, dim3(grid_for(std::max(K.dim, m_M), 256)), dim3(256), 0, m_dev.stream(), K.dim, m_mi, m_M,
-                     m_dev.d_p(), m_dev.d_ps(), m_dev.d_pz(), m_dpn.p, m_psx.p, m_pzx.p, m_keep_p.p, m_keep_ps0.p, m_keep_pz0.p, m_keep_dpn.p,
+                     m_dev.ldlt().d_p(), m_dev.d_ps(), m_dev.d_pz(), m_dpn.p, m_psx.p, m_pzx.p, m_keep_p.p, m_keep_ps0.p, m_keep_pz0.p, m_keep_dpn.p,
                      m_keep_psx.p, m_keep_pzx.p);
   SLPX_HIP_CHECK(hipGetLastError());
 }
@@ -842,7 +842,7 @@ void FrDevice::save_direction() {
 void FrDevice::restore_direction() {
   const KktDev K = m_dev.kdev();
   hipLaunchKernelGGL(fr_copy_direction_kernel, dim3(grid_for(std::max(K.dim, m_M), 256)), dim3(256), 0, m_dev.stream(), K.dim, m_mi, m_M,
-                     m_keep_p.p, m_keep_ps0.p, m_keep_pz0.p, m_keep_dpn.p, m_keep_psx.p, m_keep_pzx.p, m_dev.d_p(), m_dev.d_ps(), m_dev.d_pz(),
+                     m_keep_p.p, m_keep_ps0.p, m_keep_pz0.p, m_keep_dpn.p, m_keep_psx.p, m_keep_pzx.p, m_dev.ldlt().d_p(), m_dev.d_ps(), m_dev.d_pz(),
                      m_dpn.p, m_psx.p, m_pzx.p);
   SLPX_HIP_CHECK(hipGetLastError());
 }

@@ -360,7 +360,7 @@ void solve_round(NewtonSystem& model, int dim, const double* rhs, size_t rhs_pit
     info[b].refine_steps += ref.accepted[b];
     if (!(eb.berr[b] <= info[b].berr_max)) info[b].berr_max = eb.berr[b];  // (a NaN shows)
   }
-  copy_rows(sol, sol_pitch, dev.d_p(), dim);
+  copy_rows(sol, sol_pitch, dev.ldlt().d_p(), dim);
 }
 }  // namespace
 
@@ -431,7 +431,7 @@ void Sensitivity::factor(const Point& at, SensitivityInfo& info) {
     m_gamma = fac.gamma[0];
     info.factorizations += fac.factorizations;
     std::vector<LdltStats> stats;
-    dev.read_stats(stats);
+    dev.ldlt().read_stats(stats);
     m_n_pos = stats[0].n_pos;
     m_n_neg = stats[0].n_neg;
     m_n_zero = stats[0].n_zero;
@@ -716,7 +716,7 @@ void BatchSensitivity::factor(Call& c) {
       const Factored fac = factor_from_cleared_memory(*c.model, &mask);
       c.factorizations = fac.factorizations;
       std::vector<LdltStats> stats;
-      c.model->device().read_stats(stats);
+      c.model->device().ldlt().read_stats(stats);
       for (int b = 0; b < B; ++b) {
         if (!mask[b]) continue;
         SensitivityInfo& fi = pb.fact[b];

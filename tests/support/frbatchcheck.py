@@ -18,7 +18,7 @@ HERE = Path(__file__).resolve().parent
 LIB_PATH = HERE / "libslpx_frbatchcheck.so"
 _CSRC = HERE.parents[1] / "sleipnir_amd" / "csrc"
 SOURCES = [HERE / "frbatchcheck.cpp", HERE / "probe_common.hpp", _CSRC / "fr_batch.hpp", _CSRC / "batch_lockstep.hpp",
-           _CSRC / "restoration.hpp", _CSRC / "device.hpp"]
+           _CSRC / "restoration.hpp", _CSRC / "device.hpp", _CSRC / "device_base.hpp", _CSRC / "device_ldlt.hpp"]
 
 # fbc_get / fbc_put selectors (frbatchcheck.cpp: BatchFrProbe::buffer) with the length of an instance's slice
 BUFFERS = ["x", "s0", "y", "z0", "xr", "w", "g_outer", "s_outer", "pn", "sx", "zx", "p", "ps0", "pz0", "dpn", "psx", "pzx",

@@ -17,7 +17,7 @@ import sleipnir_amd
 HERE = Path(__file__).resolve().parent
 LIB_PATH = HERE / "libslpx_frcheck.so"
 _CSRC = HERE.parents[1] / "sleipnir_amd" / "csrc"
-SOURCES = [HERE / "frcheck.cpp", HERE / "probe_common.hpp", _CSRC / "restoration.hpp", _CSRC / "device.hpp"]
+SOURCES = [HERE / "frcheck.cpp", HERE / "probe_common.hpp", _CSRC / "restoration.hpp", _CSRC / "device.hpp", _CSRC / "device_base.hpp", _CSRC / "device_ldlt.hpp"]
 
 # fc_get / fc_put selectors (frcheck.cpp: FrProbe::buffer)
 BUFFERS = ["V", "V_trial", "in", "trial_in", "s", "y", "z", "p", "p_s", "p_z", "lhs_raw", "rhs_raw", "s_ahead", "y_ahead",
