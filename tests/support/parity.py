@@ -316,6 +316,51 @@ def check_policy_loop(system, op_lhs, n, m_e, gamma_min=1e-10, start=None):
     return float(dg[0]), float(dg[1]), nf, onf
 
 
+def check_new_right_hand_sides(system, other, op):
+    """K p = b for right-hand sides that were not there when the step kernel of `system` factored K (ldlt_mf_solve_kernel
+    where the system solves through its fronts): against the residual of the regularized system, against `other` — a
+    second system of the same problem, made under SLPX_MF_SOLVE=0: the pair-list kernels on the same factor — and
+    repeated (the hand-over slots and both x buffers are left armed by every launch); then the step after the solves is
+    the step before them, to the bit."""
+    n, me, mi = system.info["n"], system.info["m_e"], system.info["m_i"]
+    scales = op.scaling()
+    state = cases.newton_state("interior", op.get_x(), n, me, mi, scales[0])
+    x, s, y, z, mu = state
+    for sy in (system, other):
+        sy.set_scaling(scales)
+        sy.set_state(x, s, y, z, np.array([mu]))
+        sy.reset_regularization()
+        assert np.all(sy.newton_step(True) == 0)
+    delta, gamma = (float(v) for v in system.regularization()[0])
+    lhs = system.get("lhs")[0]
+    lcp, lri = system.pattern(5)
+    Kreg = cases.regularized(lcp, lri, lhs, n, delta, gamma)
+    k_inf = float(np.max(cases.lower_csc_matvec(lcp, lri, np.abs(Kreg), np.ones(n + me))))
+    rng = np.random.default_rng(11)
+    for trial in range(3):
+        b = rng.uniform(-1, 1, n + me)
+        ps = []
+        for sy in (system, other):
+            sy.set_rhs(b[None, :])
+            sy.solve()
+            ps.append(sy.get("p")[0])
+        p_fronts, p_pairs = ps
+        resid = float(np.max(np.abs(cases.lower_csc_matvec(lcp, lri, Kreg, p_fronts) - b)))
+        assert resid <= 1e-9 * max(1.0, k_inf * float(np.max(np.abs(p_fronts)))), (trial, resid)
+        resid_pairs = float(np.max(np.abs(cases.lower_csc_matvec(lcp, lri, Kreg, p_pairs) - b)))
+        assert resid <= max(1e-12 * k_inf * float(np.max(np.abs(p_fronts))), 10.0 * resid_pairs), (trial, resid, resid_pairs)
+    # and the step after it is the step before it, to the bit: nothing the solves left behind disturbs a factorization
+    system.get("p")
+    system.reset_regularization()
+    assert np.all(system.newton_step(True) == 0)
+    first = system.get("p")[0].copy()
+    system.set_rhs(rng.uniform(-1, 1, n + me)[None, :])
+    system.solve()
+    system.reset_regularization()
+    assert np.all(system.newton_step(True) == 0)
+    assert np.array_equal(system.get("p")[0], first)
+
+
 STEP_ARRAYS = ("p", "p_s", "p_z", "D", "lhs", "rhs", "V")
 
 

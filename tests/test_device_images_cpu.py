@@ -8,10 +8,13 @@ import pytest
 from tests.support import cases
 
 EPS = 2.0 ** -52
-# (tests/support/cases.py has no model with a shared timestep variable: no hub column among these.  The inequality rows
-# of cart-pole and flywheel are bounds, one column each, so no back-substitution row of theirs reaches into an ancestor
-# task; the g-fold descent's cone rows have up to four columns and do.)
-MODELS = [("cart_pole", 4), ("cart_pole", 37), ("flywheel", 50), ("gfold", 8)]
+# (tests/support/cases.py has no model with a shared timestep variable.  The inequality rows of cart-pole and flywheel
+# are bounds, one column each, so no back-substitution row of theirs reaches into an ancestor task; the g-fold descent's
+# cone rows have up to four columns and do.  The models of tests/support/step_models.py have a hub column: a variable in
+# 24 rows of each kind (chain130), in 3 + 3 (hub40_3_3, one task), and in 255 + 127 (hub530_255_127: the most terms the
+# source word of a multifrontal task image holds, device_layout.h: mf_term_code_fits).)
+STEP_MODELS = ["chain130", "hub40_3_3", "hub530_255_127"]
+MODELS = [("cart_pole", 4), ("cart_pole", 37), ("flywheel", 50), ("gfold", 8)] + [("step", name) for name in STEP_MODELS]
 
 TASK_FIELDS = ["n_ent", "n_col", "n_ext", "ent_off", "col_off", "lvl_off", "n_lvl", "ext_off", "pair_off", "contrib_off", "round",
                "pair_ptr_off", "contrib_ptr_off", "colptr_off", "n_pairs", "n_bwd_items", "n_contrib_idx"]
@@ -33,6 +36,11 @@ class Case:
             from tests.support import gfold, model
 
             self.pp = gfold.build(model.Model(model.ProductBackend("hostcheck")), N).p
+        elif kind == "step":
+            from tests.support import model, step_models
+
+            self.pp = step_models.make(model.Model(model.ProductBackend("hostcheck")), N)[0].p
+            N = self.pp.dims[0]  # (the seed below)
         else:
             self.pp, _ = cases.build_pair(kind, N, slpx, orc)
         self.hc = hc = hostcheck.HostCheck(self.pp)
@@ -212,7 +220,7 @@ def test_inline_kkt_terms_by_value(case):
     owner = task_of_entry(case)
     widest = int(task_terms[:, 1].max())
     assert im.scalar("kkt.factor_lds") == im.scalar("l.factor_lds_bytes") + 16 + 16 * widest + 8 * (widest * 4 // 3)
-    seen_sum = seen_neg = 0
+    seen_sum = seen_neg = most_terms = 0
     for e in np.flatnonzero((ent_src >= 0) & (owner >= 0)):
         src, v, is_rhs = int(ent_src[e]), int(vsrc[e]), bool(flags[e] & 4)
         want = case.rhs[src] if is_rhs else case.lhs[src]
@@ -237,7 +245,10 @@ def test_inline_kkt_terms_by_value(case):
             got = -tot(1) + tot(2) + tot(3) if is_rhs else tot(0) + tot(4)
             assert abs(got - want) <= (cnt + 1) * EPS * float(np.abs(val).sum()), (e, got, want)
             seen_sum += 1
+            most_terms = max(most_terms, cnt)
     assert seen_sum > 0 and seen_neg == case.hc.m_e
+    # (the hub's row of the right-hand side: one gradient term, 255 of A_e^T y, 127 of A_i^T)
+    assert most_terms > 100 or case.model != ("step", "hub530_255_127")
 
 
 def test_backsub_rows_by_value(case):
@@ -282,6 +293,8 @@ def test_backsub_rows_by_value(case):
             assert abs(pz - case.pz[r]) <= sinv * z[r] * bound + 3 * EPS * (mu * sinv + z[r] + sinv * z[r] * abs(ps)), (r, pz, case.pz[r])
     assert sorted(rows_seen) == list(range(m_i))  # each row of A_i in exactly one task
     assert n_ancestor_refs > 0 or case.model[0] != "gfold"
+    # (the hub's rows h^2 + x_j^2 <= 4 belong to the task of x_j; the hub is eliminated last, in the root task)
+    assert n_ancestor_refs > 0 or case.model not in (("step", "chain130"), ("step", "hub530_255_127"))
 
 
 def test_multifrontal_images(case):
@@ -304,6 +317,7 @@ def test_multifrontal_images(case):
     assert len(img) == 16 * (stride16 * case.n_tasks + G) and 1 <= stride16 <= G
     align16 = lambda v: (v + 15) & ~15
     longest = lds = recoded = 0
+    kinds_seen = set()
     for ti in range(case.n_tasks):
         g = {f: int(v[ti]) for f, v in t.items()}
         mm = {f: int(v[ti]) for f, v in m.items()}
@@ -341,6 +355,8 @@ def test_multifrontal_images(case):
             n_b, has_g = (c1 >> (fb + ab)) & ((1 << bb) - 1), c1 >> (fb + ab + bb)
             assert first == (c0 & 0xfffff) and has_g <= 1 and has_g + n_a + n_b == c0 >> 20, (ti, i)
             recoded += 1
+            kinds_seen |= {name for name, met in (("more b than a", n_b > n_a), ("products only", has_g == 0 and n_a == 0),
+                                                  ("the widest word", (n_a, n_b) == ((1 << ab) - 1, (1 << bb) - 1))) if met}
         terms16, bs16 = int(task_terms[ti, 1]), int(bs_task[ti, 1])
         end_terms = o["o_terms"] + 16 * terms16
         assert np.array_equal(region(o["o_terms"], 16 * terms16), terms[16 * int(task_terms[ti, 0]):][:16 * terms16])
@@ -353,6 +369,14 @@ def test_multifrontal_images(case):
     assert stride16 == max(1, longest) and recoded > 0
     assert im.scalar("mf.lds") == align16(lds) + 16
     assert im.mf_declines_short_task_terms() == 1
+    # the words kkt_terms_sum_grouped walks otherwise than on the benchmark models: (hub, hub) of the matrix has its direct
+    # terms and one product per inequality row of the hub (n_b > n_a); (hub, j) of a row h^2 + x_j^2 <= 4 is that row's
+    # product and nothing else (no gradient term, n_a = 0); the hub's row of the right-hand side of hub530_255_127 fills
+    # both count fields of the word (n_a = 255, n_b = 127, the fields' widths asserted here)
+    if case.model[0] == "step":
+        assert {"more b than a", "products only"} <= kinds_seen
+    if case.model == ("step", "hub530_255_127"):
+        assert (ab, bb) == (8, 7) and "the widest word" in kinds_seen
 
 
 def test_one_reader_per_slot_and_diagonal_positions(case):
