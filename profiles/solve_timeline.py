@@ -15,7 +15,7 @@ def window(tail, title):
 
 
 window(rows[-500:-380], "launches 500 .. 380 from the end of the last solve")
-# (r06) a stretch of OUTER iterations (the look-ahead chain of ipm_core_resident) and one of RESTORATION iterations
+# (r06) a stretch of OUTER iterations (the look-ahead chain of ipm_resident.cpp: ResidentIpm::enqueue_step) and one of RESTORATION iterations
 # (restoration.hip's kernels), wherever the last ones of each are
 for name, title in (("ipm_lookahead_kernel", "outer iterations"), ("fr_expand_kernel", "restoration iterations")):
     hits = [i for i, r in enumerate(rows) if name in r["Kernel_Name"]]

@@ -117,7 +117,7 @@ struct EqDriver {
   void direction(Device& bd) { bd.direction(dphi); }  // D_phi; alpha_max = alpha_z = 1
 };
 
-// ---- SQP (sqp.hpp:98-604, as sqp_core restates it) ----
+// ---- SQP (sqp.hpp:98-604, as sqp_core of sqp_newton.cpp restates it) ----
 struct SqpDriver : EqDriver {
   static constexpr const char* kName = "sqp_batch";
   static constexpr const char* kModels = "a problem with equality constraints and no inequality constraints only";
@@ -150,7 +150,7 @@ struct SqpDriver : EqDriver {
   void after_restoration(NewtonSystem& single) const { single.set_gamma_min(1e-10); }
 };
 
-// ---- Newton (newton.hpp:51-292, as newton_core restates it): its own search, never a correction or a restoration ----
+// ---- Newton (newton.hpp:51-292, as newton_core of sqp_newton.cpp restates it): its own search, never a correction or a restoration ----
 struct NewtonDriver : EqDriver {
   static constexpr const char* kName = "newton_batch";
   static constexpr const char* kModels = "a problem without constraints only";

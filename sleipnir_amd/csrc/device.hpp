@@ -57,7 +57,7 @@ class DeviceNlp {
   void build_kkt_for_step(bool with_reduce);  // same, inside the launch of the factor() that must follow
   // Least-squares multiplier estimate system on the same pattern:
   // lhs = [[I + A_i^T S^-2 A_i, A_e^T],[A_e, 0]] (util/lagrange_multiplier_estimate.hpp:56-133
-  // with d, t eliminated; see ipm.cpp)
+  // with d, t eliminated; see ipm_restoration.cpp)
   void assemble_lsq();  // V, s -> lhs
   void build_rhs();     // V, s, y, z, mu -> rhs
   // Re-reads the values of the tapes' parameter leaves (free Variables that are not
@@ -168,7 +168,7 @@ class DeviceNlp {
   void wait();                                // busy-polls the stream
   void wait_published();                      // after ipm_trial_metrics / ipm_errors: their sequence number
   const IpmHost& ipm_host() const { return *m_ipm_host; }
-  // ---- the pipelined common iteration (ipm.cpp: ipm_core_resident; ipm_decide.h) ----
+  // ---- the pipelined common iteration (ipm_resident.cpp: ResidentIpm; ipm_decide.h) ----
   // Two sets of the scalar outputs: the chain of iteration k+1 is enqueued before the host has read iteration k's.
   // ipm_set_slot: where the kernels enqueued from now on leave theirs.
   void ipm_set_slot(int slot) { m_ipm_slot = slot & 1; }

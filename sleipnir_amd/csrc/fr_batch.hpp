@@ -88,7 +88,7 @@ struct BatchFrDevice : BatchDevice {
 };
 
 // ---- the restoration phase of the lockstep loop (fr_batch_lockstep.cpp) ----
-// One instance's part in a phase: feasibility_restoration() (ipm.cpp) as interior_point() / sqp() enter it — the outer
+// One instance's part in a phase: feasibility_restoration() (ipm_restoration.cpp) as interior_point() / sqp() enter it — the outer
 // iterate (x, s, y, z; in / out), its barrier parameter, c_e, c_i and the dense gradient at x, its constraint violation and
 // `outer_accepts(entry, D_phi)`, the outer filter's verdict on a restoration iterate — and what comes back: the status
 // feasibility_restoration() returns (SUCCESS: accepted, multipliers estimated).
@@ -111,7 +111,7 @@ struct BatchRestorationRequest {
 struct BatchRestorationStats {
   int64_t instances = 0, phases = 0, rounds = 0, fallbacks = 0;
 };
-// Every request enters ONE phase together and runs restoration_core()'s iteration (ipm.cpp) with its own mu, tau, filter,
+// Every request enters ONE phase together and runs restoration_core()'s iteration (ipm_restoration.cpp) with its own mu, tau, filter,
 // line search and counters, the device work of all instances still iterating in one masked launch per phase of the
 // iteration; an instance that is through waits masked until the phase ends.  `sys`: the batch system (its
 // regularization memory of the restoring instances is reset for the phase and put back, gamma_min is 0 during it);

@@ -1,5 +1,5 @@
 // The restoration phase of the batched lockstep loop (fr_batch.hpp): restoration_core() and feasibility_restoration()
-// of ipm.cpp for every instance that asked for restoration in one round of the outer loop, in lockstep.  Each
+// of ipm_restoration.cpp for every instance that asked for restoration in one round of the outer loop, in lockstep.  Each
 // instance's decisions are the single path's — LineSearch, Filter, the barrier update and the exits of
 // ipm_line_search.hpp, the error measures of ipm_decide.h, LdltPolicy — on its own scalars; the vectors stay on the
 // device (BatchFrDevice) and every piece of work is one masked launch for the instances that want it.  What differs

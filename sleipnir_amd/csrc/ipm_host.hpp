@@ -1,4 +1,4 @@
-// Host-side pieces of the interior-point iteration shared by the single-problem driver (ipm.cpp) and
+// Host-side pieces of the interior-point iteration shared by the single-problem drivers (ipm_drivers.hpp) and
 // the batched lockstep loop (batch_lockstep.cpp): norms over downloaded vectors, the KKT error measures, the
 // filter (its rules: ipm_decide.h), the fraction-to-the-boundary rule.  (The line search and the scalar decisions
 // around it: ipm_line_search.hpp.)
@@ -46,6 +46,18 @@ inline void add_At_v(const CscPattern& A, const double* vals, const double* row_
     }
     out[c] += sign * acc;
   }
+}
+
+// is_locally_infeasible.hpp:17-60, the equality rows, on host vectors: ‖A_eᵀc_e‖ < 1e-6 and ‖c_e‖ > 1e-2
+// (interior_point.hpp:387-395, sqp.hpp:277-285)
+inline bool equality_rows_locally_infeasible(const NlpStructure& st, const double* Ae, const Vec& c_e) {
+  if (st.m_e == 0) return false;
+  Vec t(st.n, 0.0);
+  add_At_v(st.Ae, Ae, nullptr, c_e.data(), 1.0, t);
+  double nt = 0.0, nc = 0.0;
+  for (double v : t) nt += v * v;
+  for (double v : c_e) nc += v * v;
+  return std::sqrt(nt) < 1e-6 && std::sqrt(nc) > 1e-2;
 }
 
 enum class ErrType { INF_NORM_SCALED, ONE_NORM };

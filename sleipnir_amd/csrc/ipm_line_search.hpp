@@ -4,8 +4,9 @@
 // of ipm_decide.h — the ones the device decides the common iteration with.
 //
 // The machine says which device work it waits for (`want`, at `t_alpha`, `t_alpha_z`, along the Newton direction or
-// the correction's) and is resumed with a handful of scalars.  A sequential driver (ipm.cpp: host, device-resident,
-// restoration, SQP) runs it with `while (ls.want != Done) switch (ls.want)`; the batched loop (batch_lockstep.cpp)
+// the correction's) and is resumed with a handful of scalars.  A sequential driver (host: ipm.cpp; device-resident:
+// ipm_resident.cpp; restoration: ipm_restoration.cpp; SQP: sqp_newton.cpp) runs it with
+// `while (ls.want != Done) switch (ls.want)`; the batched loop (batch_lockstep.cpp)
 // keeps one per instance and answers all instances that want the same work with one masked launch.  What a driver
 // keeps for itself is plumbing: where the four numbers of a trial point come from, and what to commit.
 #pragma once

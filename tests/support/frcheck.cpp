@@ -2,7 +2,7 @@
 //
 // A probe of slpx::FrDevice (restoration.hpp): plain C entry points that drive the REAL launch wrappers of libslpx.so
 // (restoration.hip) one at a time on the NewtonSystem behind an slpx_system handle of batch 1, the sweeps the
-// restoration driver (ipm.cpp: restoration_core) runs between them, and get / put on every buffer those kernels read
+// restoration driver (ipm_restoration.cpp: restoration_core) runs between them, and get / put on every buffer those kernels read
 // or write — the outer system's and the FrDevice's own.  Nothing of the kernels is compiled here.
 // tests/test_restoration_kernels_gpu.py compares what comes back with tests/support/fr_reference.py.
 #include "../../sleipnir_amd/csrc/restoration.hpp"
