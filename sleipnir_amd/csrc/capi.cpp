@@ -660,7 +660,7 @@ int64_t slpx_system_parameter_pool_bytes(slpx_system* s) {
   int64_t bytes = -1;
   const int rc = guard([&] {
     if (s == nullptr) throw std::runtime_error("slpx_system_parameter_pool_bytes: null system");
-    bytes = static_cast<int64_t>(s->get().device().parameter_pool_bytes());
+    bytes = static_cast<int64_t>(s->get().device().tape().parameter_pool_bytes());
   });
   return rc == 0 ? bytes : rc;
 }
@@ -1100,7 +1100,7 @@ int slpx_ldlt_set_matrix(slpx_system* s, const double* values) {
 int slpx_debug_tape_clocks(slpx_system* s, uint64_t* out16) {
   return guard([&] {
     unsigned long long t[16];
-    s->get().device().debug_tape_clocks(t);
+    s->get().device().tape().debug_tape_clocks(t);
     for (int i = 0; i < 16; ++i) out16[i] = t[i];
   });
 }
@@ -1108,7 +1108,7 @@ int slpx_debug_tape_clocks(slpx_system* s, uint64_t* out16) {
 int slpx_debug_tmpl_clocks(slpx_system* s, uint64_t* out, int32_t blocks) {
   int n = -1;
   const int rc = guard([&] {
-    n = s->get().device().debug_tmpl_clocks(reinterpret_cast<unsigned long long*>(out), blocks);
+    n = s->get().device().tape().debug_tmpl_clocks(reinterpret_cast<unsigned long long*>(out), blocks);
   });
   return rc == 0 ? n : rc;
 }

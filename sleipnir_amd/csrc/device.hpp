@@ -1,8 +1,10 @@
 // Device-side state of one compiled NLP on one MI355X: uploaded plans, per-batch
-// value buffers, and launchers for the hot-path kernels (kernels.hip): the tapes, V, the
-// iterate, the KKT system and the interior-point iteration.  The factorization and the solve
-// are its DeviceLdlt (device_ldlt.hpp, device_ldlt.hip), reachable as ldlt(); the types both
-// are made of — DevBuf, the plans on the device, KktFuse / BacksubFuse — are device_base.hpp's.
+// value buffers, and launchers for the hot-path kernels (kernels.hip): V, the iterate, the KKT
+// system and the interior-point iteration.  Three parts of it are classes of their own:
+//   tape()  DeviceTape (device_tape.hpp, device_tape.hip): the uploaded tapes and every sweep launch;
+//   ldlt()  DeviceLdlt (device_ldlt.hpp, device_ldlt.hip): the factorization and the solve;
+//   StepChain (step_chain.hpp): the protocol of chained steps, between a sweep and the step kernel.
+// The types they are made of — DevBuf, the plans on the device, KktFuse / BacksubFuse — are device_base.hpp's.
 //
 // Batch-major layout everywhere: buffer[b * stride + i], b = problem in the batch.
 // All problems of a batch share one structure (tape, KKT plan, symbolic LDLᵀ) and
@@ -12,6 +14,8 @@
 
 #include "device_base.hpp"
 #include "device_ldlt.hpp"
+#include "device_tape.hpp"
+#include "step_chain.hpp"
 
 namespace slpx {
 
@@ -43,14 +47,14 @@ class DeviceNlp {
   // The sweep of a Newton step whose factor_solve_publish() follows at once (no reductions: they ride in
   // that launch).  Where the step is the one-launch multifrontal kernel and this step follows another
   // directly (nothing else was handed the main stream in between), the sweep goes to a stream of its own
-  // and the two kernels order themselves through words in memory (m_chain below): the step kernel is
+  // and the two kernels order themselves through words in memory (StepChain): the step kernel is
   // dispatched and stages its plan WHILE the sweep runs, and the sweep of the next step starts the moment
   // this step's kernel is through — no launch boundary on either side.  DESIGN.md §4, "chained steps".
   void sweep_full_for_step();
   void recover_from_chain_failure();  // after a step whose counters carry kLdltChainFailure
-  int chain_failures() const { return m_chain_failures; }
+  int chain_failures() const { return m_chain.failures(); }
   // test hook: the next chained sweep is launched as if the step kernel before it never signalled
-  void debug_break_next_chain() { m_debug_break_chain = true; }
+  void debug_break_next_chain() { m_chain.debug_break_next(); }
   void sweep_values();  // f, c_e, c_i only                   -> V
   void assemble();      // V, s, z -> lhs
   void build_kkt(bool with_reduce);  // assemble() + build_rhs() [+ reductions] as one launch
@@ -60,21 +64,12 @@ class DeviceNlp {
   // with d, t eliminated; see ipm_restoration.cpp)
   void assemble_lsq();  // V, s -> lhs
   void build_rhs();     // V, s, y, z, mu -> rhs
-  // Re-reads the values of the tapes' parameter leaves (free Variables that are not
-  // decision variables) from the graph and refreshes their constant slots.
-  void refresh_params(const Graph& g);
-  // The same with caller-given values, in the order of NlpStructure::parameter_nodes() (ascending node id).
-  // shared: values[n_p] into the parameter slots of the one pool every instance reads (and that pool is in force);
-  // per instance: values[batch][n_p], instance b's row into its own pool (TapeDevice::consts_inst), in force until
-  // the next shared install.  Buffers are rewritten in place: nothing that holds a pointer to them goes stale.
-  void set_parameters(const double* values, bool per_instance);
-  bool parameters_per_instance() const { return m_full.consts_stride != 0 || m_values.consts_stride != 0; }
-  // bytes of the per-instance pools of both programs (0 until per-instance values were installed)
-  size_t parameter_pool_bytes() const { return (m_full.consts_inst.n + m_values.consts_inst.n) * sizeof(double); }
-  void debug_tape_clocks(unsigned long long* out16);
-  // SLPX_TAPE_JIT_CLOCKS=1: 8 wall clocks (tape_jit.cpp) for each of the first `blocks` workgroups of the
-  // generated kernel's last launch; returns the number of template workgroups, -1 if absent
-  int debug_tmpl_clocks(unsigned long long* out, int blocks);
+  // The tapes: the sweeps above fill a DeviceTape::Sweep and launch it; the parameter pools are asked of it directly
+  // (DeviceTape::set_parameters says what the two forms mean)
+  DeviceTape& tape() { return m_tape; }
+  const DeviceTape& tape() const { return m_tape; }
+  void refresh_params(const Graph& g) { m_tape.refresh_params(g); }
+  void set_parameters(const double* values, bool per_instance) { m_tape.set_parameters(values, per_instance); }
   // The linear solver: its counters, factors, solution and bare launches are asked of it directly.  What follows here
   // is the orchestration that needs both sides — the system brought up to date, the riders built, then m_ldlt called.
   DeviceLdlt& ldlt() { return m_ldlt; }
@@ -195,28 +190,25 @@ class DeviceNlp {
   // speculative launch, put back when the device let it pass
   struct LaunchBook {
     DeviceLdlt::Book ldlt;
+    ChainLedger::Book chain;
     int kkt_pending;
-    bool last_step_chained, lhs_stale, rhs_stale, tape_pending, touched;
+    bool lhs_stale, rhs_stale;
   };
-  LaunchBook save_book() const {
-    return LaunchBook{m_ldlt.save_book(), m_kkt_pending, m_last_step_chained, m_lhs_stale, m_rhs_stale, m_stream.tape_pending, m_stream.touched};
-  }
+  LaunchBook save_book() const { return LaunchBook{m_ldlt.save_book(), m_chain.save(), m_kkt_pending, m_lhs_stale, m_rhs_stale}; }
   // launch_ran: the launch was not let pass at its gate — it ran with its results held back (a step that carried the
   // error launch deciding about it: MfDev::ride_verdict) and so moved the launch's OWN hand-overs on (DeviceLdlt::restore_book)
   void restore_book(const LaunchBook& b, bool launch_ran = false) {
     m_ldlt.restore_book(b.ldlt, launch_ran);
+    m_chain.restore(b.chain);
     m_kkt_pending = b.kkt_pending;
-    m_last_step_chained = b.last_step_chained;
     m_lhs_stale = b.lhs_stale;
     m_rhs_stale = b.rhs_stale;
-    m_stream.tape_pending = b.tape_pending;
-    m_stream.touched = b.touched;
   }
   double* d_V_trial() { return m_V_trial.p; }
   // the tape's separable sums (for a caller's launch that lets them ride: restoration.hip's error launch)
-  const NlpStructure::SumReduce* reduces_dev() const { return m_reduces.p; }
-  int n_reduces() const { return static_cast<int>(m_reduces.n); }
-  const double* tape_scales_dev() const { return m_scales.p; }
+  const NlpStructure::SumReduce* reduces_dev() const { return m_tape.reduces_dev(); }
+  int n_reduces() const { return static_cast<int>(m_tape.n_reduces()); }
+  const double* tape_scales_dev() const { return m_tape.scales_dev(); }
 
   // device pointers for callers that keep everything resident
   double* d_x() { return m_in.p; }
@@ -266,12 +258,9 @@ class DeviceNlp {
   const KktPlan& kkt() const { return m_k_ref; }
 
  private:
-  void launch_tape(const TapeDevice& t, bool reverse);
-  void launch_tape(const TapeDevice& t, bool reverse, hipStream_t small_stream, hipStream_t other);
+  void build_kkt(bool with_reduce, bool defer);  // defer: only note the request, for the factorization that follows
   // the constructor's phases, in its order (kernels.hip)
   void choose_initial_modes();
-  void upload_tapes();
-  void raise_lds_limits();
   void upload_kkt_plan();
   void upload_inline_kkt(const struct InlineKkt& ik);
   void upload_inline_backsub(const struct InlineBacksub& ib);
@@ -290,15 +279,15 @@ class DeviceNlp {
   LaunchModes m_mode;
   PlanFacts m_plan;  // what those stages read of m_l_ref
   int m_cus = 0;  // compute units of the device
-  TrackedStream m_stream;
+  StepChain m_chain;  // (before the stream that reports to it)
+  TrackedStream m_stream{m_chain};
   // one problem: the publishing kernel also bumps a sequence number the host spins on
   volatile unsigned long long* m_h_seq = nullptr;  // pinned
   DevBuf<unsigned long long> m_seq_dev;
   unsigned long long m_seq_expected = 0;  // publishing launches enqueued so far
+  DeviceTape m_tape;
   DeviceLdlt m_ldlt;  // (after what it holds references to)
 
-  TapeDevice m_full, m_values;
-  DevBuf<NlpStructure::SumReduce> m_reduces;
   // the KKT plan, and what the hot path hands the kernels of it
   KktPlanDevice m_kplan;
   KktDev m_kdev{};
@@ -318,16 +307,15 @@ class DeviceNlp {
   DevBuf<int32_t> m_eb_cmd;
   void errbound_require(const std::vector<uint8_t>& mask, const char* what);
   // per-batch values
-  DevBuf<double> m_in, m_in_scale, m_scales, m_V, m_s, m_y, m_z, m_mu, m_lhs, m_rhs, m_ps, m_pz, m_scratch;
-  bool m_defer_kkt = false;           // build_kkt() only notes the request ...
-  int m_kkt_pending = 0;              // ... for the factorization that follows (1: lhs + rhs, 2: + the tape's sums)
+  DevBuf<double> m_in, m_V, m_s, m_y, m_z, m_mu, m_lhs, m_rhs, m_ps, m_pz;
+  int m_kkt_pending = 0;              // the factorization that follows evaluates the system (1: lhs + rhs, 2: + the tape's sums)
   KktFuse take_kkt_fuse();
   BacksubFuse backsub_fuse();  // (the counters it hands over: DeviceLdlt's)
   KktFuse kkt_fuse_for(int kkt_mode) const;
   LdltSystem system() const { return LdltSystem{m_lhs.p, m_rhs.p, m_lhs_il.p, m_rhs_il.p, m_lhs_in_il, m_rhs_in_il}; }
   void backsub_and_publish(bool publish);
   // the riders of a step launch made now (a twin launch adds its own)
-  LdltStepRiders step_riders(const KktFuse& f, bool chained);
+  LdltStepRiders step_riders(const KktFuse& f);
   // the second attempt's p_s, p_z (a pair with m_ps, m_pz: adopt_twin), made with DeviceLdlt's twin buffers
   bool twin_ready();
   DevBuf<double> m_ps_tw, m_pz_tw;
@@ -363,28 +351,6 @@ class DeviceNlp {
   double m_ride_ticket = 1.0;       // of the last riding launch (2, 3, ...: never a plain launch's 0 / 1 in IpmHost::go)
   DevBuf<double> m_ipm_ride_verdict;
   bool m_errors_decide = false;
-  bool m_tape_reduce = true;       // launch_tape runs the separable-sum reductions itself
-  // chained steps (sweep_full_for_step): words 0 / 16 / 32 / 48 of m_chain = workgroups of the sweep
-  // through, last step whose sweep is complete, workgroups of the step kernel through, last step whose
-  // kernel is complete
-  bool m_last_step_chained = false;   // the last multifrontal step kernel launched signals its end through the chain words
-  hipStream_t m_tape_stream = nullptr;
-  hipEvent_t m_chain_ev = nullptr;
-  DevBuf<unsigned int> m_chain;
-  int m_chain_failures = 0;
-  bool m_debug_break_chain = false;
-  unsigned int m_chain_seq = 0;       // number of the last chained step
-  // running totals of the workgroups of chained sweeps / chained step kernels launched: what the kernels wait for
-  // in chain[16] / chain[48] (kept below 2^29: bits 30, 31 of the words are the failure flag)
-  unsigned int m_chain_sweep_wgs = 0, m_chain_step_wgs = 0, m_last_tape_workgroups = 0;
-  struct ChainArgs {
-    unsigned int* chain = nullptr;
-    unsigned int wait_step = 0, this_step = 0;
-    bool skip_flag = false;  // `chain` is the look-ahead chain's "rejected attempt" flag, not a chain buffer
-  };
-  ChainArgs m_chain_args;             // what launch_tape hands the generated kernel (null: an ordinary launch)
-  const double* m_in_override = nullptr;  // launch_tape reads / writes these when set
-  double* m_V_override = nullptr;
 };
 
 }  // namespace slpx

@@ -1,6 +1,6 @@
 // What DeviceNlp (device.hpp) and its linear solver DeviceLdlt (device_ldlt.hpp) are both made of: the error check,
 // the plan arena and DevBuf, the plans on the device, the structs that ride in another kernel's launch (KktFuse,
-// BacksubFuse), the scalars the interior-point kernels hand the host, the tracked stream and the spin on a published word.
+// BacksubFuse), the scalars the interior-point kernels hand the host and the spin on a published word.
 #pragma once
 
 #include <chrono>
@@ -136,46 +136,6 @@ struct DevBuf {
   void zero(hipStream_t s = nullptr) {
     if (n) SLPX_HIP_CHECK(hipMemsetAsync(p, 0, n * sizeof(T), s));
   }
-};
-
-struct TapeDevice {
-  DevBuf<TapeTask> tasks;
-  DevBuf<uint32_t> small_list, large_list, global_list;
-  DevBuf<uint32_t> leaf_src, node_rec, lvl_ptr, slot_edge_ptr, slvl_ptr, vout_src, vout_dst,
-      jout_slot, jout_dst;
-  DevBuf<int32_t> vout_scale, jout_scale;
-  DevBuf<double> consts;
-  // Per-instance parameters (DeviceNlp::set_parameters): [batch][n_consts], the WHOLE pool of every instance —
-  // parameter slots with the instance's values, literals replicated — allocated when per-instance values are first
-  // installed; consts_stride = n_consts while it is in force, 0 while `consts` (shared) is.  Replicated rather than
-  // split into "parameters per instance + literals shared": the kernels keep ONE base pointer, a leaf stays
-  // "constant slot k" (no new leaf kind), and the leaf tables and generated index words do not change.
-  DevBuf<double> consts_inst;
-  uint32_t consts_stride = 0;
-  DevBuf<TapeEdge> edges;
-  DevBuf<uint16_t> node_rec16, slot_edge_ptr16, edges16;
-  uint32_t n_small = 0, n_large = 0, n_global = 0;
-  uint32_t small_lds = 0, large_lds = 0;
-  uint64_t scratch_doubles = 0;
-  bool basic_ops = false;
-  // Tasks served by the run-time generated lane-per-task kernel (tape_jit.hpp); they are
-  // NOT in the small/large lists above.  One launch covers every body: `tmpl_table[mode]`
-  // (mode 0 = values only, 1 = with adjoints) holds (first block, instances, instance
-  // offset, row-group mode) per body, `tmpl_blocks[mode]` the grid size.
-  hipFunction_t tmpl_fn = nullptr;
-  uint32_t tmpl_threads = 64;  // threads of a workgroup of tmpl_fn (TapeJitResult::block_threads)
-  std::vector<unsigned char> tmpl_params;  // the model's numbers a generic code object reads (TemplateParams::blob)
-  DevBuf<uint64_t> tmpl_params_dev;        // ... on the device: the kernel's last argument points here
-  hipModule_t tmpl_mod = nullptr;
-  uint32_t n_bodies = 0;
-  DevBuf<uint32_t> tmpl_inst;  // per body: leaf bindings + output destinations, transposed (device_images.hpp: pack_template_tables)
-  DevBuf<uint32_t> tmpl_table[2];
-  uint32_t tmpl_blocks[2] = {0, 0};
-  uint32_t n_templated_tasks = 0;
-  bool tmpl_wide_for_chain = false;  // 256-thread workgroups only because the sweep runs beside the step kernel (tape_jit.cpp)
-  double jit_seconds = 0.0;
-  void upload(const TapeProgram& p, int batch, uint32_t n_unscaled_inputs, int chain_mode = 0);
-  TapeDev view() const;
 };
 
 struct LdltDev {
@@ -382,33 +342,6 @@ struct IpmHost {
 
 struct StepTimings {
   float sweep = 0, assemble = 0, rhs = 0, factor = 0, solve = 0, backsub = 0, total = 0;
-};
-
-// The stream of a DeviceNlp, remembering whether anything was handed it since the last chained Newton
-// step (DeviceNlp::sweep_full_for_step): every use as a hipStream_t marks it.
-struct TrackedStream {
-  hipStream_t s = nullptr;
-  mutable bool touched = true;
-  // a chained sweep is in flight on `tape` and the step kernel that waits for it has not been launched:
-  // whatever else is handed this stream first has to come after the sweep
-  hipStream_t tape = nullptr;
-  hipEvent_t ev = nullptr;
-  mutable bool tape_pending = false;
-  operator hipStream_t() const {
-    touched = true;
-    if (tape_pending) {
-      tape_pending = false;
-      (void)hipEventRecord(ev, tape);
-      (void)hipStreamWaitEvent(s, ev, 0);
-    }
-    return s;
-  }
-  TrackedStream& operator=(hipStream_t v) {
-    s = v;
-    touched = true;
-    return *this;
-  }
-  hipStream_t raw() const { return s; }
 };
 
 // Spin on a word a kernel publishes into pinned host memory.  The stream itself is consulted only after two

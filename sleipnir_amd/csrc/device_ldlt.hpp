@@ -8,6 +8,7 @@
 #pragma once
 
 #include "device_base.hpp"
+#include "step_chain.hpp"
 
 namespace slpx {
 

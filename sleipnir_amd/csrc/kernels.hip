@@ -1,14 +1,12 @@
-// gfx950 (MI355X) kernels for the interior-point Newton step, and the DeviceNlp
-// host object that owns their buffers.  See DESIGN.md §3 for the roofline of each.
+// DeviceNlp's host code: the device-side state of one compiled NLP, the launches of the KKT system's kernels around
+// the factorization and of the interior-point iteration.  See DESIGN.md §3 for the roofline of each kernel.
 //
-//   tape_sweep     (tape_kernels.h) AD refresh: forward values + local partials, then
-//                  the per-row adjoint gather, all inside LDS (one workgroup per task)
-//                  replaces update_values/append_triplets/setFromTriplets
-//                  (expression_graph.hpp:86-153, jacobian.hpp:134-156, hessian.hpp:132-157)
-//   kkt_assemble   lhs values by gather   (interior_point.hpp:426-440)
+//   kkt_assemble   lhs values by gather   (interior_point.hpp:426-440)      kkt_launch_kernels.h
 //   kkt_rhs        rhs by column gathers  (interior_point.hpp:444-448)
 //   step_backsub   pˢ, pᶻ                 (interior_point.hpp:479-480)
-// The factorization and the solves between them: DeviceLdlt, device_ldlt.hip.
+//   ipm_*          the iteration's scalars and iterates                     ipm_launch_kernels.h
+// The tape sweeps: DeviceTape, device_tape.hip.  The chained-step protocol: StepChain, step_chain.hpp.  The
+// factorization and the solves between them: DeviceLdlt, device_ldlt.hip.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -24,452 +22,16 @@
 #include "device_images.hpp"
 #include "kkt_kernels.h"
 #include "setup_threads.hpp"
-#include "tape_jit.hpp"
 #include "ipm_decide.h"
 #include "ipm_launch_kernels.h"
-#include "tape_kernels.h"
-#include "tape_ops.h"
+#include "kkt_launch_kernels.h"
 #include "setup_timing.hpp"
 
 namespace slpx {
 
 // ============================================================================
-// kkt_assemble / kkt_rhs / step_backsub: pure gathers over static index maps.
-// HBM-bound; algorithmic bytes: assemble 12(h+a+i) + 16 m_i + 8 k, rhs
-// 16 n + 24 m_e + 24 m_i + 12(a+i).  One thread per output entry,
-// consecutive threads write consecutive entries; the sources of consecutive lhs
-// entries are (nearly) consecutive in V because both are CSC-ordered.
-// ============================================================================
-__global__ __launch_bounds__(256) void kkt_assemble_kernel(KktDev K, const double* __restrict__ V,
-                                                           int v_stride,
-                                                           const double* __restrict__ s,
-                                                           const double* __restrict__ z,
-                                                           double* __restrict__ lhs) {
-  const int b = blockIdx.y;
-  kkt_assemble_body(K, V + static_cast<size_t>(b) * v_stride, s + static_cast<size_t>(b) * K.m_i,
-                    z + static_cast<size_t>(b) * K.m_i, lhs + static_cast<size_t>(b) * K.nnz_lhs, blockIdx.x,
-                    gridDim.x);
-}
-
-// Batch variant: one thread serves the SAME entry of kBatchPerThread consecutive problems,
-// so every index of the static maps (fast_src, dptr/dsrc, pptr/pa/pb/pr) is fetched once per
-// kBatchPerThread problems instead of once per problem — the maps are a fifth of the bytes
-// a thread touches — and the problems' gathers are in flight together.
-constexpr int kBatchPerThread = 4;
-
-template <int P>
-__global__ __launch_bounds__(256) void kkt_assemble_batch_kernel(KktDev K, const double* __restrict__ V,
-                                                                 int v_stride,
-                                                                 const double* __restrict__ s,
-                                                                 const double* __restrict__ z,
-                                                                 double* __restrict__ lhs, int batch) {
-  const int b0 = blockIdx.y * P;
-  const int nb = min(P, batch - b0);
-  V += static_cast<size_t>(b0) * v_stride;
-  s += static_cast<size_t>(b0) * K.m_i;
-  z += static_cast<size_t>(b0) * K.m_i;
-  lhs += static_cast<size_t>(b0) * K.nnz_lhs;
-  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < K.nnz_lhs; k += gridDim.x * blockDim.x) {
-    const int f = K.fast_src[k];
-    double v[P];
-#pragma unroll
-    for (int q = 0; q < P; ++q) v[q] = 0.0;
-    if (f >= 0) {
-#pragma unroll
-      for (int q = 0; q < P; ++q)
-        if (q < nb) v[q] = V[static_cast<size_t>(q) * v_stride + f];
-    } else if (f == -2) {
-      double prod[P];
-#pragma unroll
-      for (int q = 0; q < P; ++q) prod[q] = 0.0;
-      for (int d = K.dptr[k]; d < K.dptr[k + 1]; ++d) {
-        const int src = K.dsrc[d];
-#pragma unroll
-        for (int q = 0; q < P; ++q)
-          if (q < nb) v[q] += V[static_cast<size_t>(q) * v_stride + src];
-      }
-      for (int p = K.pptr[k]; p < K.pptr[k + 1]; ++p) {
-        const int r = K.pr[p], a = K.pa[p], bb = K.pb[p];
-#pragma unroll
-        for (int q = 0; q < P; ++q)
-          if (q < nb) {
-            const double* Vq = V + static_cast<size_t>(q) * v_stride;
-            prod[q] += kkt_prod_term(Vq[a], s[q * K.m_i + r], z[q * K.m_i + r], Vq[bb]);
-          }
-      }
-#pragma unroll
-      for (int q = 0; q < P; ++q) v[q] += prod[q];
-    }
-#pragma unroll
-    for (int q = 0; q < P; ++q)
-      if (q < nb) lhs[static_cast<size_t>(q) * K.nnz_lhs + k] = v[q];
-  }
-}
-
-// The batch-interleaved factorization's inputs written WHERE IT READS THEM (ldlt_il_kernels.h:
-// [b / 16][entry][16]) — the batch-major lhs / rhs and the two transposing launches between the
-// assembly and the factorization (il_gather_kernel: 0.084 ms of a 1.15 ms step at 512 x N=1000) are
-// only made when somebody asks for them (DeviceNlp::d_lhs / d_rhs).
-// lhs: a thread = one entry of FOUR consecutive problems, four adjacent lanes = the 16 problems of
-// the entry's row: every 128-byte row is written whole by one quad, and a wave's loads of one
-// problem's V are sixteen consecutive entries' sources.
-__device__ __forceinline__ void kkt_assemble_il_body(const KktDev& K, const double* __restrict__ V, int v_stride,
-                                                     const double* __restrict__ s, const double* __restrict__ z,
-                                                     double* __restrict__ lhs_il, int batch, int vblock, int vgrid) {
-  constexpr int P = 4;
-  const int g = blockIdx.y, sub = threadIdx.x & 3;
-  const int b0 = g * kIlW + sub * P;
-  const int nb = max(0, min(P, batch - b0));
-  const size_t bb0 = static_cast<size_t>(nb > 0 ? b0 : 0);  // (no problem of this quad exists: nothing is dereferenced)
-  V += bb0 * v_stride;
-  s += bb0 * K.m_i;
-  z += bb0 * K.m_i;
-  double* out = lhs_il + static_cast<size_t>(g) * K.nnz_lhs * kIlW + sub * P;
-  for (int k = vblock * 64 + (threadIdx.x >> 2); k < K.nnz_lhs; k += vgrid * 64) {
-    const int f = K.fast_src[k];
-    double v[P];
-#pragma unroll
-    for (int q = 0; q < P; ++q) v[q] = 0.0;
-    if (f >= 0) {
-#pragma unroll
-      for (int q = 0; q < P; ++q)
-        if (q < nb) v[q] = V[static_cast<size_t>(q) * v_stride + f];
-    } else if (f == -2) {
-      double prod[P];
-#pragma unroll
-      for (int q = 0; q < P; ++q) prod[q] = 0.0;
-      for (int d = K.dptr[k]; d < K.dptr[k + 1]; ++d) {
-        const int src = K.dsrc[d];
-#pragma unroll
-        for (int q = 0; q < P; ++q)
-          if (q < nb) v[q] += V[static_cast<size_t>(q) * v_stride + src];
-      }
-      for (int p = K.pptr[k]; p < K.pptr[k + 1]; ++p) {
-        const int r = K.pr[p], a = K.pa[p], c = K.pb[p];
-#pragma unroll
-        for (int q = 0; q < P; ++q)
-          if (q < nb) {
-            const double* Vq = V + static_cast<size_t>(q) * v_stride;
-            prod[q] += kkt_prod_term(Vq[a], s[q * K.m_i + r], z[q * K.m_i + r], Vq[c]);
-          }
-      }
-#pragma unroll
-      for (int q = 0; q < P; ++q) v[q] += prod[q];
-    }
-    double2* o = reinterpret_cast<double2*>(out + static_cast<size_t>(k) * kIlW);
-    o[0] = double2{v[0], v[1]};
-    o[1] = double2{v[2], v[3]};
-  }
-}
-
-__global__ __launch_bounds__(256) void kkt_assemble_il_kernel(KktDev K, const double* __restrict__ V, int v_stride,
-                                                              const double* __restrict__ s, const double* __restrict__ z,
-                                                              double* __restrict__ lhs_il, int batch) {
-  kkt_assemble_il_body(K, V, v_stride, s, z, lhs_il, batch, blockIdx.x, gridDim.x);
-}
-
-// rhs: 64 rows x 16 problems per workgroup through LDS — a row is computed by one lane per problem
-// group of four (consecutive lanes = consecutive rows: the row's sources in V are nearly consecutive),
-// written as whole 128-byte rows.
-__device__ __forceinline__ void kkt_rhs_il_body(const KktDev& K, const double* __restrict__ V, int v_stride,
-                                                const double* __restrict__ s, const double* __restrict__ y,
-                                                const double* __restrict__ z, const double* __restrict__ mu,
-                                                double* __restrict__ rhs_il, int batch, int vblock) {
-  __shared__ double tile[kIlW][65];
-  const int g = blockIdx.y, i0 = vblock * 64;
-  const int il = threadIdx.x & 63, bq = threadIdx.x >> 6;
-  const int j = i0 + il;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int pl = bq * 4 + q, b = g * kIlW + pl;
-    double val = 0.0;
-    if (b < batch && j < K.dim) {
-      const size_t sb = static_cast<size_t>(b);
-      val = kkt_rhs_entry(K, V + sb * v_stride, s + sb * K.m_i, y + sb * K.m_e, z + sb * K.m_i, mu[b], j);
-    }
-    tile[pl][il] = val;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int jj = 0; jj < 4; ++jj) {
-    const int idx = threadIdx.x + 256 * jj, pl = idx & (kIlW - 1), r = idx >> kIlWShift;
-    if (i0 + r < K.dim) rhs_il[(static_cast<size_t>(g) * K.dim + i0 + r) * kIlW + pl] = tile[pl][r];
-  }
-}
-__global__ __launch_bounds__(256) void kkt_rhs_il_kernel(KktDev K, const double* __restrict__ V, int v_stride,
-                                                         const double* __restrict__ s, const double* __restrict__ y,
-                                                         const double* __restrict__ z, const double* __restrict__ mu,
-                                                         double* __restrict__ rhs_il, int batch) {
-  kkt_rhs_il_body(K, V, v_stride, s, y, z, mu, rhs_il, batch, blockIdx.x);
-}
-// lhs and rhs in ONE launch (a Newton step builds both: neither reads the other's output) — workgroups
-// [0, na) assemble, the rest take 64 rows of the right-hand side each.  A small batch's two launches are
-// latency each (64 x N=500: 15 + 16 us); side by side they cost the longer one.
-__global__ __launch_bounds__(256) void kkt_build_il_kernel(KktDev K, const double* __restrict__ V, int v_stride,
-                                                           const double* __restrict__ s, const double* __restrict__ y,
-                                                           const double* __restrict__ z, const double* __restrict__ mu,
-                                                           double* __restrict__ lhs_il, double* __restrict__ rhs_il, int batch,
-                                                           int na) {
-  if (static_cast<int>(blockIdx.x) < na) kkt_assemble_il_body(K, V, v_stride, s, z, lhs_il, batch, blockIdx.x, na);
-  else kkt_rhs_il_body(K, V, v_stride, s, y, z, mu, rhs_il, batch, static_cast<int>(blockIdx.x) - na);
-}
-
-// Least-squares multiplier estimate (util/lagrange_multiplier_estimate.hpp:56-133) on the
-// KKT pattern: the top-left block is I + A_i^T S^-2 A_i (H sources skipped, identity added
-// by kkt_add_identity_kernel), the A_e block is unchanged.
-__global__ __launch_bounds__(256) void kkt_assemble_lsq_kernel(KktDev K, const double* __restrict__ V,
-                                                               int v_stride,
-                                                               const double* __restrict__ s,
-                                                               double* __restrict__ lhs) {
-  const int b = blockIdx.y;
-  V += static_cast<size_t>(b) * v_stride;
-  s += static_cast<size_t>(b) * K.m_i;
-  lhs += static_cast<size_t>(b) * K.nnz_lhs;
-  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < K.nnz_lhs; k += gridDim.x * blockDim.x) {
-    double direct = 0.0;
-    for (int d = K.dptr[k]; d < K.dptr[k + 1]; ++d) {
-      const int src = K.dsrc[d];
-      if (src >= K.off_Ae && src < K.off_Ai) direct += V[src];
-    }
-    double prod = 0.0;
-    for (int p = K.pptr[k]; p < K.pptr[k + 1]; ++p) {
-      const double sinv = 1.0 / s[K.pr[p]];
-      prod += (V[K.pa[p]] * (sinv * sinv)) * V[K.pb[p]];
-    }
-    lhs[k] = direct + prod;
-  }
-}
-
-__global__ __launch_bounds__(256) void kkt_add_identity_kernel(KktDev K, const int32_t* __restrict__ diag_pos,
-                                                               double* __restrict__ lhs) {
-  lhs += static_cast<size_t>(blockIdx.y) * K.nnz_lhs;
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < K.n; j += gridDim.x * blockDim.x)
-    lhs[diag_pos[j]] += 1.0;
-}
-
-__global__ __launch_bounds__(256) void kkt_rhs_kernel(KktDev K, const double* __restrict__ V,
-                                                      int v_stride, const double* __restrict__ s,
-                                                      const double* __restrict__ y,
-                                                      const double* __restrict__ z,
-                                                      const double* __restrict__ mu,
-                                                      double* __restrict__ rhs) {
-  const int b = blockIdx.y;
-  kkt_rhs_body(K, V + static_cast<size_t>(b) * v_stride, s + static_cast<size_t>(b) * K.m_i,
-               y + static_cast<size_t>(b) * K.m_e, z + static_cast<size_t>(b) * K.m_i, mu[b],
-               rhs + static_cast<size_t>(b) * K.dim, blockIdx.x, gridDim.x);
-}
-
-// lhs, rhs and the separable-sum reductions of the tape in ONE launch: all three only read
-// what the sweep left in V, none reads another's output (the sums feed f, which nothing in
-// the Newton step consumes).  Block ranges: [0, na) assembly, [na, na + nr) right-hand
-// side, the rest one reduction each.
-__global__ __launch_bounds__(256) void kkt_build_kernel(KktDev K, double* __restrict__ V, int v_stride,
-                                                        const double* __restrict__ s,
-                                                        const double* __restrict__ y,
-                                                        const double* __restrict__ z,
-                                                        const double* __restrict__ mu,
-                                                        double* __restrict__ lhs, double* __restrict__ rhs,
-                                                        int na, int nr,
-                                                        const NlpStructure::SumReduce* __restrict__ red,
-                                                        const double* __restrict__ scales) {
-  __shared__ double part[64];
-  const int b = blockIdx.y;
-  V += static_cast<size_t>(b) * v_stride;
-  s += static_cast<size_t>(b) * K.m_i;
-  z += static_cast<size_t>(b) * K.m_i;
-  const int blk = blockIdx.x;
-  if (blk < na) {
-    kkt_assemble_body(K, V, s, z, lhs + static_cast<size_t>(b) * K.nnz_lhs, blk, na);
-  } else if (blk < na + nr) {
-    kkt_rhs_body(K, V, s, y + static_cast<size_t>(b) * K.m_e, z, mu[b], rhs + static_cast<size_t>(b) * K.dim,
-                 blk - na, nr);
-  } else {
-    const NlpStructure::SumReduce r = red[blk - na - nr];
-    const int tid = threadIdx.x;
-    separable_sum_tree(V, r, part, tid);
-    if (tid == 0) V[r.dst] = separable_sum_scale(r, scales) * part[0];
-  }
-}
-
-__global__ __launch_bounds__(256) void step_backsub_kernel(KktDev K, const double* __restrict__ V,
-                                                           int v_stride,
-                                                           const double* __restrict__ p,
-                                                           const double* __restrict__ s,
-                                                           const double* __restrict__ z,
-                                                           const double* __restrict__ mu,
-                                                           double* __restrict__ ps,
-                                                           double* __restrict__ pz,
-                                                           const LdltStats* __restrict__ stats_src,
-                                                           LdltStats* __restrict__ stats_host,
-                                                           unsigned long long* __restrict__ seq_dev,
-                                                           volatile unsigned long long* seq_host) {
-  const int b = blockIdx.y;
-  // last kernel of a step: hand the inertia counters of the factorization to the host
-  // (pinned memory) instead of spending a copy node on them; with one problem also a
-  // sequence number the host spins on — it learns of the result a few microseconds before
-  // the stream would report the kernel complete, and what it does next (another attempt or
-  // the next step) is ordered behind this kernel by the stream anyway
-  if (stats_host != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
-    stats_host[b] = stats_src[b];
-    if (seq_host != nullptr) {
-      __threadfence_system();
-      const unsigned long long v = *seq_dev + 1;
-      *seq_dev = v;
-      *seq_host = v;
-    }
-  }
-  V += static_cast<size_t>(b) * v_stride;
-  p += static_cast<size_t>(b) * K.dim;
-  s += static_cast<size_t>(b) * K.m_i;
-  z += static_cast<size_t>(b) * K.m_i;
-  ps += static_cast<size_t>(b) * K.m_i;
-  pz += static_cast<size_t>(b) * K.m_i;
-  step_backsub_body(K, V, p, s, z, mu[b], ps, pz, static_cast<int>(blockIdx.x * blockDim.x + threadIdx.x),
-                    static_cast<int>(gridDim.x * blockDim.x));
-}
-
-// Iterative refinement of a solve (used where the regularization would otherwise show in the
-// answer: the least-squares multiplier estimate): r = b - K p for the UNREGULARIZED symmetric K
-// given by its lower CSC values in `lhs`.  One thread per row i: the column i of the lower
-// triangle gives K(r, i), r >= i, and a row index of the same triangle (rowptr / rowent / rowcol)
-// gives K(i, c), c < i — a fixed order of summation, so the same bits on every run (scattering
-// the mirrored half with floating-point atomics made the multiplier estimate, and with it the
-// whole trajectory of a solve, differ from run to run in the last bits).
-__global__ __launch_bounds__(256) void sym_residual_kernel(int dim, const int32_t* __restrict__ colptr,
-                                                           const int32_t* __restrict__ rowidx,
-                                                           const int32_t* __restrict__ rowptr,
-                                                           const int32_t* __restrict__ rowent,
-                                                           const int32_t* __restrict__ rowcol,
-                                                           const double* __restrict__ lhs,
-                                                           const double* __restrict__ p,
-                                                           double* __restrict__ res) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < dim; i += gridDim.x * blockDim.x) {
-    double acc = 0.0;
-    for (int q = rowptr[i]; q < rowptr[i + 1]; ++q) acc += lhs[rowent[q]] * p[rowcol[q]];  // K(i, c), c < i
-    for (int q = colptr[i]; q < colptr[i + 1]; ++q) acc += lhs[q] * p[rowidx[q]];          // K(r, i), r >= i
-    res[i] -= acc;
-  }
-}
-__global__ __launch_bounds__(256) void axpy_kernel(int count, const double* __restrict__ x, double* __restrict__ y) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) y[i] += x[i];
-}
-
-// Separable sums on their own (tape_reduce_body, tape_kernels.h) — used when the reductions
-// cannot ride along with the interpreted tail of the tape (launch_tape).
-__global__ __launch_bounds__(64) void tape_reduce_kernel(const NlpStructure::SumReduce* __restrict__ red,
-                                                         const double* __restrict__ scales,
-                                                         double* __restrict__ V, int v_stride) {
-  __shared__ double part[64];
-  V += static_cast<size_t>(blockIdx.y) * v_stride;
-  tape_reduce_body(red[blockIdx.x], scales, V, part, threadIdx.x);
-}
-
-// Can two kernels of this process run at once?  Chained steps (DeviceNlp::sweep_full_for_step) need the
-// sweep and the step kernel resident together; a profiler collecting hardware counters (rocprofv3 --pmc)
-// or AMD_SERIALIZE_KERNEL runs one kernel at a time, and a step kernel waiting for a sweep that cannot
-// start would sit out its spin bound (seen: 247 ms per step under --pmc).  So, once per system: a kernel
-// on the sweep's stream waits — a few milliseconds at most — for a word a kernel on the main stream sets.
-__global__ void chain_probe_wait_kernel(unsigned int* w) {
-  unsigned int seen = 0;
-  for (int k = 0; k < 3000 && !seen; ++k) {
-    seen = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __builtin_amdgcn_s_sleep(32);
-  }
-  w[1] = seen ? 1u : 2u;
-}
-__global__ void chain_probe_set_kernel(unsigned int* w) { __hip_atomic_store(w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// ============================================================================
 // DeviceNlp
 // ============================================================================
-
-void TapeDevice::upload(const TapeProgram& p, int batch, uint32_t n_unscaled_inputs, int chain_mode) {
-  tasks.upload(p.tasks);
-  // families of structurally identical tasks and the big singles get a body in the
-  // generated lane-per-task kernel; everything else is interpreted
-  TapeJitOptions jit_opt;
-  jit_opt.n_unscaled_inputs = n_unscaled_inputs;  // x: set_scaling leaves their factor at 1
-  jit_opt.chain_mode = chain_mode;
-  const TapeJitResult jit = build_tape_templates(p, jit_opt);
-  jit_seconds = jit.compile_seconds;
-  tmpl_fn = jit.fn;
-  tmpl_params = jit.params;
-  {
-    std::vector<uint64_t> words((tmpl_params.size() + 7) / 8, 0);
-    std::memcpy(words.data(), tmpl_params.data(), tmpl_params.size());
-    tmpl_params_dev.upload(words);
-  }
-  tmpl_mod = jit.mod;
-  tmpl_threads = jit.block_threads;
-  n_bodies = static_cast<uint32_t>(jit.groups.size());
-  n_templated_tasks = 0;
-  tmpl_blocks[0] = tmpl_blocks[1] = 0;
-  if (n_bodies) {
-    const TemplateTables tt = pack_template_tables(p, jit.groups, batch, tmpl_threads);
-    n_templated_tasks = tt.n_templated_tasks;
-    tmpl_inst.upload(tt.inst);
-    for (int m = 0; m < 2; ++m) {
-      tmpl_table[m].upload(tt.table[m]);
-      tmpl_blocks[m] = tt.blocks[m];
-    }
-  }
-  auto interpreted = [&](const std::vector<uint32_t>& list) {
-    std::vector<uint32_t> out;
-    for (uint32_t ti : list)
-      if (!jit.task_is_templated[ti]) out.push_back(ti);
-    return out;
-  };
-  std::vector<uint32_t> small_rest = interpreted(p.small_tasks), large_rest = interpreted(p.large_tasks);
-  uint32_t ride_lds = p.small_lds_bytes;
-  tmpl_wide_for_chain = n_bodies && tmpl_threads == 256 && large_rest.empty() && chain_mode != 0;
-  if (n_bodies && tmpl_threads == 256) {
-    // (tape_jit.cpp: the generated kernel's workgroups are 256 threads: every interpreted task rides in its launch)
-    small_rest.insert(small_rest.end(), large_rest.begin(), large_rest.end());
-    large_rest.clear();
-    ride_lds = std::max(p.small_lds_bytes, p.large_lds_bytes);
-  }
-  small_list.upload(small_rest);
-  large_list.upload(large_rest);
-  global_list.upload(p.global_tasks);
-  if (std::getenv("SLPX_TAPE_JIT_VERBOSE") && jit.fn)
-    std::fprintf(stderr, "slpx tape kernel: %zu bodies, %s code object (%zu bytes of model numbers), %.3f s\n",
-                 jit.groups.size(), jit.specialized ? "specialized" : "generic", jit.params.size(), jit.compile_seconds);
-  if (std::getenv("SLPX_TAPE_JIT_VERBOSE"))
-    for (uint32_t ti : p.global_tasks)
-      std::fprintf(stderr, "slpx tape GLOBAL task: leaf %u node %u slot %u vout %u jout %u levels %u+%u\n", p.tasks[ti].n_leaf,
-                   p.tasks[ti].n_node, p.tasks[ti].n_slot, p.tasks[ti].n_vout, p.tasks[ti].n_jout, p.tasks[ti].n_lvl, p.tasks[ti].n_slvl);
-  leaf_src.upload(p.leaf_src);
-  // never empty: the generated bodies read consts[0] in lanes whose leaf is not a constant
-  consts.upload(p.consts.empty() ? std::vector<double>{0.0} : p.consts);
-  node_rec.upload(p.node_rec);
-  lvl_ptr.upload(p.lvl_ptr);
-  slot_edge_ptr.upload(p.slot_edge_ptr);
-  slvl_ptr.upload(p.slvl_ptr);
-  edges.upload(p.edges);
-  vout_src.upload(p.vout_src);
-  vout_dst.upload(p.vout_dst);
-  vout_scale.upload(p.vout_scale);
-  jout_slot.upload(p.jout_slot);
-  jout_dst.upload(p.jout_dst);
-  jout_scale.upload(p.jout_scale);
-  node_rec16.upload(p.node_rec16);
-  slot_edge_ptr16.upload(p.slot_edge_ptr16);
-  edges16.upload(p.edges16);
-  n_small = static_cast<uint32_t>(small_rest.size());
-  n_large = static_cast<uint32_t>(large_rest.size());
-  n_global = static_cast<uint32_t>(p.global_tasks.size());
-  small_lds = ride_lds;
-  large_lds = p.large_lds_bytes;
-  scratch_doubles = p.global_scratch_doubles;
-  basic_ops = p.basic_ops;
-}
-
-TapeDev TapeDevice::view() const {
-  return TapeDev{tasks.p,         leaf_src.p,   consts_stride ? consts_inst.p : consts.p,   node_rec.p,   lvl_ptr.p,
-                 slot_edge_ptr.p, slvl_ptr.p,   edges.p,    vout_src.p,   vout_dst.p,
-                 vout_scale.p,    jout_slot.p,  jout_dst.p, jout_scale.p, node_rec16.p,
-                 slot_edge_ptr16.p, edges16.p,  consts_stride};
-}
 
 void KktPlanDevice::upload(const NlpStructure& s, const KktPlan& k) {
   dptr.upload(k.dptr);
@@ -518,7 +80,7 @@ KktDev KktPlanDevice::view() const {
 // copy each (commit at the end) — so their order is also the order of the plan arrays in memory.
 DeviceNlp::DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l, int batch,
                      int device, const Switches& sw)
-    : m_s_ref(s), m_k_ref(k), m_l_ref(l), m_batch(batch), m_device(device), m_sw(sw),
+    : m_s_ref(s), m_k_ref(k), m_l_ref(l), m_batch(batch), m_device(device), m_sw(sw), m_tape(s, batch, m_stream),
       m_ldlt(l, k, batch, DeviceLdlt::Shared{m_stream, m_mode, m_plan, m_sw, m_cus, m_h_seq, s.reduces.size()}) {
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
@@ -531,9 +93,9 @@ DeviceNlp::DeviceNlp(const NlpStructure& s, const KktPlan& k, const LdltPlan& l,
   DeviceArena::current() = &m_arena;
 
   choose_initial_modes();
-  upload_tapes();
+  m_tape.upload(m_mode.chain_mode);
   lap("  upload: tapes (+ code objects)");
-  raise_lds_limits();
+  m_tape.raise_lds_limits();
   m_ldlt.raise_lds_limits();
   upload_kkt_plan();
   lap("  upload: kernel attributes, KKT plan");
@@ -574,22 +136,6 @@ void DeviceNlp::choose_initial_modes() {
   m_mode = initial_launch_modes(m_batch, m_plan, m_s_ref.reduces.size(), m_cus, m_sw);
 }
 
-void DeviceNlp::upload_tapes() {
-  const NlpStructure& s = m_s_ref;
-  m_full.upload(s.full, m_batch, static_cast<uint32_t>(s.n), m_mode.chain_mode);
-  m_values.upload(s.values, m_batch, static_cast<uint32_t>(s.n));
-  m_reduces.upload(s.reduces);
-}
-
-// allow > 64 KB dynamic LDS
-void DeviceNlp::raise_lds_limits() {
-  for (const void* fn : {reinterpret_cast<const void*>(&tape_sweep_lds_kernel<256, true>),
-                         reinterpret_cast<const void*>(&tape_sweep_lds_kernel<256, false>),
-                         reinterpret_cast<const void*>(&tape_sweep_lds_kernel<64, true>),
-                         reinterpret_cast<const void*>(&tape_sweep_lds_kernel<64, false>)})
-    SLPX_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-}
-
 void DeviceNlp::upload_kkt_plan() {
   m_kplan.upload(m_s_ref, m_k_ref);
   m_kdev = m_kplan.view();
@@ -625,8 +171,7 @@ void DeviceNlp::alloc_value_buffers() {
   m_rhs.alloc(B * k.dim);
   m_ps.alloc(B * std::max(1, s.m_i));
   m_pz.alloc(B * std::max(1, s.m_i));
-  const uint64_t scratch = std::max(s.full.global_scratch_doubles, s.values.global_scratch_doubles);
-  m_scratch.alloc(B * std::max<uint64_t>(1, scratch));
+  m_tape.alloc_scratch();
   // every value buffer starts at zero, the solver's too (DeviceLdlt::alloc_value_buffers says why)
   for (DevBuf<double>* buf : {&m_V, &m_s, &m_y, &m_z, &m_mu, &m_lhs, &m_rhs, &m_ps, &m_pz}) buf->zero();
   m_ldlt.alloc_value_buffers();
@@ -658,23 +203,13 @@ DeviceNlp::~DeviceNlp() {
   if (m_ipm_host) (void)hipHostFree(m_ipm_host);
   if (m_ipm_ctl_host) (void)hipHostFree(m_ipm_ctl_host);
   if (m_ipm_ctl_dev) (void)hipFree(m_ipm_ctl_dev);
-  if (m_tape_stream) {
-    (void)hipStreamSynchronize(m_tape_stream);
-    (void)hipStreamDestroy(m_tape_stream);
-  }
-  if (m_chain_ev) (void)hipEventDestroy(m_chain_ev);
-  if (m_stream.ev) (void)hipEventDestroy(m_stream.ev);
 }
 
 void DeviceNlp::set_scaling(const std::vector<double>& scales) {
   const NlpStructure& s = m_s_ref;
   if (static_cast<int>(scales.size()) != s.n_scales())
     throw std::runtime_error("set_scaling: wrong length");
-  m_scales.upload(scales);
-  std::vector<double> in_scale(s.n_inputs(), 1.0);
-  for (int j = 0; j < s.m_e; ++j) in_scale[s.n + j] = scales[1 + j];
-  for (int j = 0; j < s.m_i; ++j) in_scale[s.n + s.m_e + j] = scales[1 + s.m_e + j];
-  m_in_scale.upload(in_scale);
+  m_tape.set_scaling(scales);
   m_V_static.assign(s.nV, 0.0);
   for (int k = 0; k < s.nV; ++k) {
     const int32_t sc = s.V_scale_idx[k];
@@ -723,197 +258,44 @@ void DeviceNlp::download(const double* dev, double* host, size_t count) {
   SLPX_HIP_CHECK(hipStreamSynchronize(m_stream));
 }
 
-void DeviceNlp::launch_tape(const TapeDevice& t, bool reverse) {
-  launch_tape(t, reverse, m_stream, m_stream);
-}
-
-// The task classes are independent; `other`: the stream of the few large / global tasks.
-void DeviceNlp::launch_tape(const TapeDevice& t, bool reverse, hipStream_t small_stream,
-                            hipStream_t other) {
-  const TapeDev view = t.view();
-  const int in_stride = m_s_ref.n_inputs(), v_stride = m_s_ref.nV;
-  const unsigned long long sstride = m_scratch.n / m_batch;
-  const double* in_p = m_in_override ? m_in_override : m_in.p;
-  double* V_p = m_V_override ? m_V_override : m_V.p;
-  // basic_ops: the program only uses + - * / sin cos sqrt and the piecewise ops, so
-  // the kernel specialization without pow/exp/log/erf/... (fewer VGPRs, less code)
-  // generated template kernels: one lane per task instance (tape_jit.hpp)
-  // interpreted 64-thread tasks ride along in the generated kernel's launch when there is one
-  const bool small_rides = t.n_bodies > 0 && t.n_small > 0;
-  if (t.n_bodies) {
-    const int mode = reverse ? 1 : 0;
-    const unsigned* table = t.tmpl_table[mode].p;
-    int n_bodies = static_cast<int>(t.n_bodies);
-    const unsigned* inst = t.tmpl_inst.p;
-    const unsigned* leaf_src = view.leaf_src;
-    const double* consts = view.consts;
-    const double* in = in_p;
-    int in_stride_arg = in_stride;
-    const double* in_scale = m_in_scale.p;
-    const double* scales = m_scales.p;
-    double* V = V_p;
-    int v_stride_arg = v_stride;
-    const unsigned* vout_dst = view.vout_dst;
-    const int* vout_scale = view.vout_scale;
-    const unsigned* jout_dst = view.jout_dst;
-    const int* jout_scale = view.jout_scale;
-    TapeDev view_arg = view;
-    const unsigned* task_list = t.small_list.p;
-    int n_template_blocks = static_cast<int>(t.tmpl_blocks[mode]);
-    int do_reverse = reverse ? 1 : 0;
-    const uint64_t* params_dev = t.tmpl_params_dev.p;
-    unsigned int* chain = m_chain_args.chain;
-    unsigned int wait_step = m_chain_args.wait_step, this_step = m_chain_args.this_step;
-    const unsigned grid = t.tmpl_blocks[mode] + (small_rides ? t.n_small : 0u);
-    unsigned int n_workgroups = m_chain_args.skip_flag ? 0u : grid * static_cast<unsigned>(m_batch);
-    m_last_tape_workgroups = grid * static_cast<unsigned>(m_batch);
-    void* args[] = {&table,  &n_bodies, &inst,         &leaf_src, &consts,     &in,       &in_stride_arg,
-                    &in_scale, &scales, &V,            &v_stride_arg, &vout_dst, &vout_scale, &jout_dst,
-                    &jout_scale, &view_arg, &task_list, &n_template_blocks, &do_reverse,
-                    &params_dev, &chain, &wait_step, &this_step, &n_workgroups};
-    SLPX_HIP_CHECK(hipModuleLaunchKernel(t.tmpl_fn, grid, m_batch, 1, t.tmpl_threads, 1, 1, small_rides ? t.small_lds : 0u,
-                                         small_stream, args, nullptr));
-  }
-  auto small_fn = t.basic_ops ? tape_sweep_lds_kernel<64, false> : tape_sweep_lds_kernel<64, true>;
-  auto large_fn = t.basic_ops ? tape_sweep_lds_kernel<256, false> : tape_sweep_lds_kernel<256, true>;
-  if (t.n_small && !small_rides)
-    hipLaunchKernelGGL(small_fn, dim3(t.n_small, m_batch), dim3(64), t.small_lds, small_stream, view,
-                       t.small_list.p, in_p, in_stride, m_in_scale.p, m_scales.p, V_p, v_stride,
-                       reverse ? 1 : 0);
-  if (t.n_large)
-    hipLaunchKernelGGL(large_fn, dim3(t.n_large, m_batch), dim3(256), t.large_lds, other, view,
-                       t.large_list.p, in_p, in_stride, m_in_scale.p, m_scales.p, V_p, v_stride,
-                       reverse ? 1 : 0);
-  if (t.n_global)
-    hipLaunchKernelGGL(tape_sweep_global_kernel, dim3(t.n_global, m_batch), dim3(1024), 0, other,
-                       view, t.global_list.p, in_p, in_stride, m_in_scale.p, m_scales.p, V_p,
-                       v_stride, m_scratch.p, sstride, reverse ? 1 : 0);
-  if (m_reduces.n && m_tape_reduce)
-    hipLaunchKernelGGL(tape_reduce_kernel, dim3(static_cast<uint32_t>(m_reduces.n), m_batch), dim3(64), 0,
-                       small_stream, m_reduces.p, m_scales.p, V_p, v_stride);
-  SLPX_HIP_CHECK(hipGetLastError());
-}
-
 void DeviceNlp::sweep_full(bool with_reduce) {
-  m_tape_reduce = with_reduce;
-  launch_tape(m_full, true);
-  m_tape_reduce = true;
+  const hipStream_t stream = m_stream;
+  m_tape.launch(DeviceTape::Full, true, {m_in.p, m_V.p, with_reduce, stream, {}});
 }
 void DeviceNlp::sweep_full_for_step() {
-  const TapeDevice& t = m_full;
-  // one generated kernel is the whole sweep (nothing interpreted beside it), the step is the one-launch
-  // multifrontal kernel
-  // (and its workgroups are single waves: g-fold's sweep, 256-thread workgroups interpreting its packs of
-  // rows, shares the chip badly with the step kernel — 13.3 k steps/s chained against 13.6 k)
-  const bool one_kernel = t.n_bodies > 0 && t.n_large == 0 && t.n_global == 0 && (t.tmpl_threads == 64 || t.tmpl_wide_for_chain);
-  if (!m_mode.chain_on || !one_kernel || m_batch != 1 || !m_ldlt.step_possible() || !m_mode.fuse_solve) {
+  // the tape's side of a chained step, and the step is the one-launch multifrontal kernel
+  if (!m_mode.chain_on || !m_tape.full_sweep_can_chain() || m_batch != 1 || !m_ldlt.step_possible() || !m_mode.fuse_solve) {
     sweep_full(/*with_reduce=*/false);
     return;
   }
-  if (m_tape_stream == nullptr) {
-    SLPX_HIP_CHECK(hipStreamCreateWithFlags(&m_tape_stream, hipStreamNonBlocking));
-    SLPX_HIP_CHECK(hipEventCreateWithFlags(&m_chain_ev, hipEventDisableTiming));
-    SLPX_HIP_CHECK(hipEventCreateWithFlags(&m_stream.ev, hipEventDisableTiming));
-    m_stream.tape = m_tape_stream;
-    {
-      // (tests: the running totals start so far below their bound, so that a few thousand chained steps cross it —
-      // SLPX_DEBUG_CHAIN_TOTALS_HEADROOM workgroups of headroom — and the restart of the counts is exercised)
-      std::vector<unsigned int> words(128, 0u);
-      if (const char* env = std::getenv("SLPX_DEBUG_CHAIN_TOTALS_HEADROOM")) {
-        const unsigned int headroom = static_cast<unsigned int>(std::max(1L, std::atol(env)));
-        m_chain_sweep_wgs = m_chain_step_wgs = (1u << 29) - std::min(headroom, 1u << 28);
-        words[16] = m_chain_sweep_wgs;
-        words[48] = m_chain_step_wgs;
-      }
-      m_chain.upload(words);
-    }
-    // (words 96, 97: the concurrency probe, see chain_probe_wait_kernel)
-    hipLaunchKernelGGL(chain_probe_wait_kernel, dim3(1), dim3(1), 0, m_tape_stream, m_chain.p + 96);
-    hipLaunchKernelGGL(chain_probe_set_kernel, dim3(1), dim3(1), 0, m_stream.raw(), m_chain.p + 96);
-    SLPX_HIP_CHECK(hipStreamSynchronize(m_tape_stream));
-    SLPX_HIP_CHECK(hipStreamSynchronize(m_stream.raw()));
-    unsigned int verdict = 0;
-    SLPX_HIP_CHECK(hipMemcpy(&verdict, m_chain.p + 97, sizeof(verdict), hipMemcpyDeviceToHost));
-    if (verdict != 1u) {
-      unchain(m_mode);  // kernels run one at a time here: the sweep stays in the main stream
-      if (std::getenv("SLPX_LDLT_VERBOSE")) std::fprintf(stderr, "slpx: kernels of two streams do not run at once here: steps are not chained\n");
-      sweep_full(/*with_reduce=*/false);
-      return;
-    }
-  }
-  m_tape_reduce = false;
-  if (m_stream.tape_pending) {
-    // The last chained sweep was never consumed (its step threw before the step kernel was launched, or
-    // the caller swept twice): no step kernel will signal the word a chained sweep would wait for.  Order
-    // the streams by an event and start over.
-    (void)static_cast<hipStream_t>(m_stream);  // waits for that sweep, marks the stream touched
-    m_last_step_chained = false;
-  }
-  if (m_chain_seq >= (1u << 30) - 1u || m_chain_sweep_wgs >= (1u << 29) || m_chain_step_wgs >= (1u << 29)) {
-    // step numbers stay in [1, 2^30) (the kernels compare them as signed differences, use 0 for "no wait"
-    // and bit 31 for failure): every ~14 hours of chained steps, one unchained step and a fresh count
-    SLPX_HIP_CHECK(hipStreamSynchronize(m_tape_stream));
-    SLPX_HIP_CHECK(hipStreamSynchronize(m_stream.raw()));
-    SLPX_HIP_CHECK(hipMemset(m_chain.p, 0, 64 * sizeof(unsigned int)));
-    m_chain_seq = 0;
-    m_chain_sweep_wgs = m_chain_step_wgs = 0;
-    m_last_step_chained = false;
-    m_stream.touched = true;
-  }
-  if (m_stream.touched) {
-    // Something else went to the main stream since the last step (an upload of the state, a download of
-    // the result, another kernel): this step's sweep goes there too, behind all of it — the pattern of a
-    // caller that looks at every step costs nothing extra.  Only steps that FOLLOW a step directly chain.
-    m_stream.touched = false;
-    launch_tape(m_full, true, m_stream.raw(), m_stream.raw());
-    m_tape_reduce = true;
+  const StepChain::Route route = m_chain.begin_sweep(m_stream.raw(), m_mode);
+  if (route.kind == StepChain::Route::NotChained) {
+    sweep_full(/*with_reduce=*/false);
     return;
   }
-  // the step kernel before this sweep: a chained one tells the sweep itself when its last workgroup is
-  // through; any other (the first step of a run, a re-attempt of the policy loop) through an event, once
-  unsigned int wait_step = m_chain_step_wgs;  // (every workgroup of the chained step kernels so far)
-  if (!m_last_step_chained) {
-    SLPX_HIP_CHECK(hipEventRecord(m_chain_ev, m_stream.raw()));
-    SLPX_HIP_CHECK(hipStreamWaitEvent(m_tape_stream, m_chain_ev, 0));
-    wait_step = 0;
-  }
-  if (m_debug_break_chain && wait_step != 0u) {
-    m_debug_break_chain = false;
-    wait_step += 1u << 20;  // (slpx_debug_chain) step kernels nobody launched
-  }
-  ++m_chain_seq;
-  m_chain_args = ChainArgs{m_chain.p, wait_step, m_chain_seq};
-  launch_tape(m_full, true, m_tape_stream, m_tape_stream);
-  m_chain_sweep_wgs += m_last_tape_workgroups;
-  m_tape_reduce = true;
-  m_chain_args = ChainArgs{};
-  m_stream.tape_pending = true;  // until the step kernel that waits for this sweep is launched
+  const bool chained = route.kind == StepChain::Route::Chained;
+  const hipStream_t stream = chained ? m_chain.tape_stream() : m_stream.raw();
+  const DeviceTape::Link link = chained ? DeviceTape::Link::chain(route.words, route.wait_step, route.this_step) : DeviceTape::Link{};
+  const unsigned int workgroups = m_tape.launch(DeviceTape::Full, true, {m_in.p, m_V.p, false, stream, link});
+  if (chained) m_chain.sweep_launched(workgroups);
 }
 // A chained step reported kLdltChainFailure: one of the two kernels gave up waiting for the other (never
 // expected — a shared / preempted / serialized GPU).  Drain both streams, clear the words, keep this
 // system's steps unchained from now on and leave V as a fresh sweep of the current state writes it.
 void DeviceNlp::recover_from_chain_failure() {
-  if (m_tape_stream != nullptr) SLPX_HIP_CHECK(hipStreamSynchronize(m_tape_stream));
-  SLPX_HIP_CHECK(hipStreamSynchronize(m_stream.raw()));
-  if (m_chain.p != nullptr) SLPX_HIP_CHECK(hipMemset(m_chain.p, 0, 64 * sizeof(unsigned int)));
+  m_chain.recover(m_stream.raw());
   unchain(m_mode);
-  m_chain_sweep_wgs = m_chain_step_wgs = 0;
-  m_last_step_chained = false;
-  m_stream.tape_pending = false;
-  m_stream.touched = true;
-  ++m_chain_failures;
   if (std::getenv("SLPX_LDLT_VERBOSE")) std::fprintf(stderr, "slpx: a chained step lost its hand-over: the step is redone, steps are unchained from here on\n");
   sweep_full(/*with_reduce=*/false);
 }
-void DeviceNlp::sweep_values() { launch_tape(m_values, false); }
+void DeviceNlp::sweep_values() {
+  const hipStream_t stream = m_stream;
+  m_tape.launch(DeviceTape::Values, false, {m_in.p, m_V.p, true, stream, {}});
+}
+// (no reductions: ipm_trial_metrics_kernel, the only reader of these values, finishes the sums)
 void DeviceNlp::sweep_values_trial() {
-  m_in_override = m_trial_in.p;
-  m_V_override = m_V_trial.p;
-  m_tape_reduce = false;  // ipm_trial_metrics_kernel, the only reader of these values, finishes the sums
-  launch_tape(m_values, false);
-  m_tape_reduce = true;
-  m_in_override = nullptr;
-  m_V_override = nullptr;
+  const hipStream_t stream = m_stream;
+  m_tape.launch(DeviceTape::Values, false, {m_trial_in.p, m_V_trial.p, false, stream, {}});
 }
 
 static inline int grid_for(int work, int block, int cap = 2048) {
@@ -969,7 +351,7 @@ void DeviceNlp::assemble() {
 }
 
 // lhs + rhs (+ the separable-sum reductions a sweep_full(false) left out) in one launch
-void DeviceNlp::build_kkt(bool with_reduce) {
+void DeviceNlp::build_kkt(bool with_reduce, bool defer) {
   if (m_batch >= kBatchPerThread) {  // throughput regime: the batch kernels, separately
     if (m_mode.il) {
       // (interleaved lhs and rhs: one launch, kkt_build_il_kernel)
@@ -982,13 +364,11 @@ void DeviceNlp::build_kkt(bool with_reduce) {
       assemble();
       build_rhs();
     }
-    if (with_reduce && m_reduces.n)
-      hipLaunchKernelGGL(tape_reduce_kernel, dim3(static_cast<uint32_t>(m_reduces.n), m_batch), dim3(64), 0,
-                         m_stream, m_reduces.p, m_scales.p, m_V.p, m_s_ref.nV);
+    if (with_reduce && m_tape.n_reduces()) m_tape.reduce(m_V.p, m_stream);
     SLPX_HIP_CHECK(hipGetLastError());
     return;
   }
-  if (m_defer_kkt) {  // evaluated inside the factorization's launch (take_kkt_fuse)
+  if (defer) {  // evaluated inside the factorization's launch (take_kkt_fuse)
     m_kkt_pending = with_reduce ? 2 : 1;
     m_lhs_stale = m_rhs_stale = true;
     return;
@@ -996,18 +376,17 @@ void DeviceNlp::build_kkt(bool with_reduce) {
   m_lhs_stale = m_rhs_stale = false;
   m_lhs_in_il = m_rhs_in_il = false;
   const int na = grid_for((m_kdev.nnz_lhs + 3) / 4, 256), nr = grid_for(m_kdev.dim, 256);
-  const int nred = with_reduce ? static_cast<int>(m_reduces.n) : 0;
+  const int nred = with_reduce ? static_cast<int>(m_tape.n_reduces()) : 0;
   hipLaunchKernelGGL(kkt_build_kernel, dim3(na + nr + nred, m_batch), dim3(256), 0, m_stream, m_kdev, m_V.p,
-                     m_s_ref.nV, m_s.p, m_y.p, m_z.p, m_mu.p, m_lhs.p, m_rhs.p, na, nr, m_reduces.p, m_scales.p);
+                     m_s_ref.nV, m_s.p, m_y.p, m_z.p, m_mu.p, m_lhs.p, m_rhs.p, na, nr, m_tape.reduces_dev(), m_tape.scales_dev());
   SLPX_HIP_CHECK(hipGetLastError());
 }
 
 // build_kkt() when a factorization attempt is the next thing enqueued (a Newton step): the
 // assembly then rides in that launch (device.hpp: KktFuse)
+void DeviceNlp::build_kkt(bool with_reduce) { build_kkt(with_reduce, /*defer=*/false); }
 void DeviceNlp::build_kkt_for_step(bool with_reduce) {
-  m_defer_kkt = m_mode.fuse_kkt;
-  build_kkt(with_reduce);
-  m_defer_kkt = false;
+  build_kkt(with_reduce, /*defer=*/m_mode.fuse_kkt);
 }
 
 void DeviceNlp::assemble_lsq() {
@@ -1018,71 +397,6 @@ void DeviceNlp::assemble_lsq() {
   hipLaunchKernelGGL(kkt_add_identity_kernel, dim3(grid_for(m_kdev.n, 256), m_batch), dim3(256), 0,
                      m_stream, m_kdev, m_kplan.diag_pos.p, m_lhs.p);
   SLPX_HIP_CHECK(hipGetLastError());
-}
-
-int DeviceNlp::debug_tmpl_clocks(unsigned long long* out, int blocks) {
-  SLPX_HIP_CHECK(hipStreamSynchronize(m_stream));
-  hipDeviceptr_t p = nullptr;
-  size_t bytes = 0;
-  if (!m_full.tmpl_mod || hipModuleGetGlobal(&p, &bytes, m_full.tmpl_mod, "slpx_tmpl_clocks") != hipSuccess) {
-    (void)hipGetLastError();
-    return -1;
-  }
-  const size_t want = std::min<size_t>(bytes, static_cast<size_t>(blocks) * 8 * sizeof(unsigned long long));
-  SLPX_HIP_CHECK(hipMemcpy(out, p, want, hipMemcpyDeviceToHost));
-  return static_cast<int>(m_full.tmpl_blocks[1]);
-}
-
-void DeviceNlp::debug_tape_clocks(unsigned long long* out16) {
-  SLPX_HIP_CHECK(hipStreamSynchronize(m_stream));
-  SLPX_HIP_CHECK(hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_tape_clocks), 16 * sizeof(unsigned long long)));
-}
-
-void DeviceNlp::refresh_params(const Graph& g) {
-  std::vector<double> values;
-  for (NodeId node : m_s_ref.parameter_nodes()) values.push_back(g.val[node]);
-  set_parameters(values.data(), /*per_instance=*/false);
-}
-
-void DeviceNlp::set_parameters(const double* values, bool per_instance) {
-  const std::vector<NodeId> nodes = m_s_ref.parameter_nodes();
-  if (nodes.empty()) {
-    if (per_instance) throw std::runtime_error("slpx: set_parameters: the model has no parameters");
-    return;
-  }
-  if (values == nullptr) throw std::runtime_error("slpx: set_parameters: values is null");
-  SLPX_HIP_CHECK(hipStreamSynchronize(m_stream));  // (no sweep in flight reads the pool that is rewritten)
-  const size_t n_p = nodes.size(), B = static_cast<size_t>(m_batch);
-  auto install = [&](const TapeProgram& prog, TapeDevice& dev) {
-    if (prog.params.empty()) return;
-    const size_t nc = prog.consts.size();
-    // where parameter j of the caller's vector sits in this program's pool (slot j: both programs claim
-    // `param_order` first — looked up all the same, so that a program that reaches fewer parameters is served too)
-    std::vector<std::pair<size_t, uint32_t>> slot_of;  // (j, slot)
-    for (const auto& [node, slot] : prog.params) {
-      const size_t j = static_cast<size_t>(std::lower_bound(nodes.begin(), nodes.end(), node) - nodes.begin());
-      if (slot >= nc) throw std::runtime_error("slpx: set_parameters: a parameter slot outside the constant pool");
-      slot_of.emplace_back(j, slot);
-    }
-    if (!per_instance) {
-      std::vector<double> c = prog.consts;
-      for (const auto& [j, slot] : slot_of) c[slot] = values[j];
-      SLPX_HIP_CHECK(hipMemcpy(dev.consts.p, c.data(), nc * sizeof(double), hipMemcpyHostToDevice));
-      dev.consts_stride = 0;
-      return;
-    }
-    std::vector<double> c(B * nc);
-    for (size_t b = 0; b < B; ++b) {
-      std::copy(prog.consts.begin(), prog.consts.end(), c.begin() + b * nc);
-      for (const auto& [j, slot] : slot_of) c[b * nc + slot] = values[b * n_p + j];
-    }
-    if (dev.consts_inst.n != c.size()) dev.consts_inst.alloc(c.size());
-    SLPX_HIP_CHECK(hipMemcpy(dev.consts_inst.p, c.data(), c.size() * sizeof(double), hipMemcpyHostToDevice));
-    dev.consts_stride = static_cast<uint32_t>(nc);
-  };
-  install(m_s_ref.full, m_full);
-  install(m_s_ref.values, m_values);
-  // (a program without parameters keeps its shared pool, stride 0, in either mode)
 }
 
 void DeviceNlp::build_rhs() {
@@ -1108,7 +422,7 @@ KktFuse DeviceNlp::kkt_fuse_for(int kkt_mode) const {
   KktFuse f;
   if (kkt_mode) {
     f.inline_kkt = 1;
-    f.n_blocks = kkt_mode == 2 ? static_cast<int>(m_reduces.n) : 0;
+    f.n_blocks = kkt_mode == 2 ? static_cast<int>(m_tape.n_reduces()) : 0;
     f.V = m_V.p;
     f.s = m_s.p;
     f.y = m_y.p;
@@ -1122,8 +436,8 @@ KktFuse DeviceNlp::kkt_fuse_for(int kkt_mode) const {
       f.store_lhs = m_lhs.p;
       f.store_rhs = m_rhs.p;
     }
-    f.red = m_reduces.p;
-    f.scales = m_scales.p;
+    f.red = m_tape.reduces_dev();
+    f.scales = m_tape.scales_dev();
   }
   return f;
 }
@@ -1161,17 +475,18 @@ void DeviceNlp::factor(const std::vector<double>& delta, const std::vector<doubl
 
 // What rides in a launch of the step kernel made now: the system or its evaluation in place, the back-substitution,
 // the chain link of a chained step (sweep_full_for_step) and the gate of a step enqueued ahead.
-LdltStepRiders DeviceNlp::step_riders(const KktFuse& f, bool chained) {
+LdltStepRiders DeviceNlp::step_riders(const KktFuse& f) {
   LdltStepRiders r;
   r.kkt = f;
   r.backsub = backsub_fuse();
   r.lhs = m_lhs.p;
   r.rhs = m_rhs.p;
-  if (chained) {
-    r.chain = m_chain.p;
-    r.wait_step = m_chain_sweep_wgs;  // (every workgroup of the chained sweeps so far, this step's included)
+  const ChainLedger::StepLink link = m_chain.step_link();
+  if (link.chained) {
+    r.chain = m_chain.words();
+    r.wait_step = link.wait_step;  // (every workgroup of the chained sweeps so far, this step's included)
   }
-  r.this_step = m_chain_seq;
+  r.this_step = link.this_step;
   if (m_gate_next_step) {  // (one launch: the step enqueued before the iteration in front of it was decided)
     r.gate = m_ipm_gate.p;
     m_gate_next_step = false;
@@ -1190,11 +505,7 @@ void DeviceNlp::factor_solve_publish(const std::vector<double>& delta, const std
   const KktFuse f = take_kkt_fuse();
   // a chained step: the kernel variant that waits for its sweep itself and whose last workgroup tells the next step's
   // sweep; the main stream stays "untouched" by a step's own launches
-  const bool chained = m_stream.tape_pending;
-  const unsigned int workgroups = m_ldlt.step(delta, gamma, active, step_riders(f, chained));
-  if (chained) m_chain_step_wgs += workgroups;  // (what the next chained sweep waits for in chain[48])
-  m_stream.tape_pending = false;
-  m_last_step_chained = chained;
+  m_chain.step_launched(m_ldlt.step(delta, gamma, active, step_riders(f)));  // (its workgroups: what the next chained sweep waits for)
   m_ldlt.stats_handed_to_host(++m_seq_expected);
 }
 
@@ -1213,7 +524,7 @@ bool DeviceNlp::twin_ready() {
 
 void DeviceNlp::launch_twin(double delta0, double gamma0, double delta1, double gamma1, int mode, const KktFuse& f, const double* lhs2,
                             const double* rhs2) {
-  LdltStepRiders r = step_riders(f, false);
+  LdltStepRiders r = step_riders(f);  // (never chained: no twin is launched over a pending sweep)
   r.ps2 = m_ps_tw.p;
   r.pz2 = m_pz_tw.p;
   r.lhs2 = lhs2;
@@ -1225,13 +536,12 @@ void DeviceNlp::launch_twin(double delta0, double gamma0, double delta1, double 
     r.gate = nullptr;  // (nothing in front of this launch is undecided: its own riding workgroups decide)
   }
   m_ldlt.step_twin(delta0, gamma0, delta1, gamma1, mode, r);
-  m_stream.tape_pending = false;
-  m_last_step_chained = false;
+  m_chain.twin_launched();
   m_ldlt.stats_handed_to_host(++m_seq_expected);
 }
 
 bool DeviceNlp::factor_solve_publish_twin(double delta0, double gamma0, double delta1, double gamma1, int mode) {
-  if (!twin_ready() || m_stream.tape_pending) return false;
+  if (!twin_ready() || m_chain.sweep_pending()) return false;
   if (!m_kkt_pending) materialize_kkt();
   launch_twin(delta0, gamma0, delta1, gamma1, mode, take_kkt_fuse(), nullptr, nullptr);
   return true;
@@ -1239,7 +549,7 @@ bool DeviceNlp::factor_solve_publish_twin(double delta0, double gamma0, double d
 
 bool DeviceNlp::factor_solve_publish_twin_written(double delta0, double gamma0, double delta1, double gamma1, int mode, const double* lhs2,
                                                   const double* rhs2) {
-  if (!twin_ready() || m_stream.tape_pending || m_kkt_pending || m_lhs_stale || m_rhs_stale) return false;
+  if (!twin_ready() || m_chain.sweep_pending() || m_kkt_pending || m_lhs_stale || m_rhs_stale) return false;
   launch_twin(delta0, gamma0, delta1, gamma1, mode, KktFuse{}, lhs2, rhs2);
   return true;
 }
@@ -1445,20 +755,13 @@ void DeviceNlp::ipm_lookahead(double tau) {
 }
 
 void DeviceNlp::sweep_full_lookahead(bool with_reduce, bool skippable) {
-  m_in_override = m_trial_in.p;
-  m_V_override = m_V_trial.p;
-  m_tape_reduce = with_reduce;  // false: the separable sums ride in ipm_errors(.., sums_ride, ahead)
-  // (the generated kernel leaves at once when the look-ahead launch flagged the attempt as rejected: `chain` with
-  // n_workgroups = 0 is that flag, tape_jit.cpp)
-  if (skippable && m_full.n_bodies && m_ipm_alpha.p != nullptr) {
-    m_chain_args = ChainArgs{reinterpret_cast<unsigned int*>(m_ipm_alpha.p + 2), 0u, 0u};
-    m_chain_args.skip_flag = true;
-  }
-  launch_tape(m_full, true);
-  m_chain_args = ChainArgs{};
-  m_tape_reduce = true;
-  m_in_override = nullptr;
-  m_V_override = nullptr;
+  // with_reduce false: the separable sums ride in ipm_errors(.., sums_ride, ahead)
+  // (the generated kernel leaves at once when the look-ahead launch flagged the attempt as rejected)
+  DeviceTape::Link link;
+  if (skippable && m_tape.full_has_generated_kernel() && m_ipm_alpha.p != nullptr)
+    link = DeviceTape::Link::skip_if(reinterpret_cast<unsigned int*>(m_ipm_alpha.p + 2));
+  const hipStream_t stream = m_stream;
+  m_tape.launch(DeviceTape::Full, true, {m_trial_in.p, m_V_trial.p, with_reduce, stream, link});
 }
 
 void DeviceNlp::ipm_accept_lookahead() {
@@ -1480,7 +783,7 @@ void DeviceNlp::ipm_trial_point(double alpha) {
 void DeviceNlp::ipm_trial_metrics(double alpha, bool s_from_ci) {
   hipLaunchKernelGGL(ipm_trial_metrics_kernel, dim3(1), dim3(kIpmThreads), 0, m_stream, m_kdev, m_V_trial.p,
                      m_s.p, m_ps.p, alpha, m_ipm_alpha.p, s_from_ci ? 1 : 0, &m_ipm_host[m_ipm_slot].trial, m_seq_dev.p, m_h_seq,
-                     m_reduces.p, static_cast<int>(m_reduces.n), m_scales.p);
+                     m_tape.reduces_dev(), static_cast<int>(m_tape.n_reduces()), m_tape.scales_dev());
   ++m_seq_expected;
   SLPX_HIP_CHECK(hipGetLastError());
 }
@@ -1501,12 +804,12 @@ void DeviceNlp::ipm_errors(bool check_all_V, bool sums_ride, bool ahead) {
   const int blocks = grid_for(8 * work, kIpmErrThreads, 64);
   if (m_ipm_partial.n < static_cast<size_t>(blocks) * kIpmErrQ) m_ipm_partial.alloc(static_cast<size_t>(256) * kIpmErrQ);
   if (m_ipm_err_done.n == 0) m_ipm_err_done.upload(std::vector<unsigned int>(1, 0u));
-  const int n_sums = sums_ride ? static_cast<int>(m_reduces.n) : 0;
+  const int n_sums = sums_ride ? static_cast<int>(m_tape.n_reduces()) : 0;
   IpmErrFinish fin;
   fin.n_err_blocks = blocks;
   fin.n_total_blocks = blocks + n_sums;
-  fin.red = m_reduces.p;
-  fin.tape_scales = m_scales.p;
+  fin.red = m_tape.reduces_dev();
+  fin.tape_scales = m_tape.scales_dev();
   fin.Vw = ahead ? m_V_trial.p : m_V.p;
   fin.done = m_ipm_err_done.p;
   fin.out = ahead ? &m_ipm_host[m_ipm_slot].err_ahead : &m_ipm_host[m_ipm_slot].err;
@@ -1541,9 +844,9 @@ bool DeviceNlp::ipm_ride_possible() {
       per_cu = m_ldlt.riding_twin_workgroups_per_cu();
       if (m_ipm_ride_verdict.n == 0) m_ipm_ride_verdict.upload(std::vector<double>(1, 0.0));
     }
-    choose_ride(m_mode, m_plan, m_reduces.n, static_cast<size_t>(per_cu) * m_cus, m_sw);
+    choose_ride(m_mode, m_plan, m_tape.n_reduces(), static_cast<size_t>(per_cu) * m_cus, m_sw);
     if (m_sw.ipm_ride && std::getenv("SLPX_LDLT_VERBOSE"))
-      std::fprintf(stderr, "ldlt riding error launch: %zu workgroups, %d of %d threads per CU x %d CUs%s\n", riding_workgroups(m_plan, m_reduces.n),
+      std::fprintf(stderr, "ldlt riding error launch: %zu workgroups, %d of %d threads per CU x %d CUs%s\n", riding_workgroups(m_plan, m_tape.n_reduces()),
                    per_cu, m_mode.twin_threads, m_cus, m_mode.ride ? "" : ": NOT resident at once");
   }
   return m_mode.ride != 0;
@@ -1557,7 +860,7 @@ MfRide DeviceNlp::ipm_take_ride() {
   const int blocks = grid_for(8 * work, kIpmErrThreads, 64);
   if (m_ipm_partial.n < static_cast<size_t>(blocks) * kIpmErrQ) m_ipm_partial.alloc(static_cast<size_t>(256) * kIpmErrQ);
   if (m_ipm_err_done.n == 0) m_ipm_err_done.upload(std::vector<unsigned int>(1, 0u));
-  const int n_sums = static_cast<int>(m_reduces.n);
+  const int n_sums = static_cast<int>(m_tape.n_reduces());
   m_ride_ticket += 1.0;
   MfRide ride;
   ride.n_blocks = static_cast<uint32_t>(blocks + n_sums);
@@ -1573,8 +876,8 @@ MfRide DeviceNlp::ipm_take_ride() {
   IpmErrFinish& fin = ride.fin;
   fin.n_err_blocks = blocks;
   fin.n_total_blocks = blocks + n_sums;
-  fin.red = m_reduces.p;
-  fin.tape_scales = m_scales.p;
+  fin.red = m_tape.reduces_dev();
+  fin.tape_scales = m_tape.scales_dev();
   fin.Vw = m_V.p;
   fin.done = m_ipm_err_done.p;
   fin.out = &m_ipm_host[m_ride_slot].err_ahead;

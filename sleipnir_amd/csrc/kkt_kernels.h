@@ -1,5 +1,5 @@
 // KKT assembly (interior_point.hpp:426-448): per-entry functions and the grid-stride bodies
-// built on them.  Shared by the stand-alone kernels of kernels.hip and by the factorization
+// built on them.  Shared by the stand-alone kernels of kkt_launch_kernels.h and by the factorization
 // kernel, whose tasks can evaluate the entries they need themselves (device.hpp: KktFuse).
 // COHERENT: the results cross workgroups inside the launch.
 #pragma once
